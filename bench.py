@@ -13,7 +13,9 @@ One "step" = one pass of the hot path over one synthetic scan whose frame stack 
   solex_do_work in one call, the way a folder of files is: the reference overlaps the post-processing of up to
   four files (Pool(4), Solex_recon.py:30-42), here `--workers` scan threads (default 4) each drive their own HIP
   stream, so one file's host control plane overlaps the others' kernels.  No file is read or written inside
-  that timed region; `value` is frames / wall time of the K steps (max over ranks).
+  that timed region; `value` is frames / wall time of the K steps (max over ranks), `ms_per_step` that wall time / K.
+  `--dump-outputs DIR` writes the products of the last timed scan to DIR/<name>.npy afterwards (see dump_products);
+  the synthetic stacks are seeded, so the same arguments give the same inputs on every run.
 
 Beside `value` the line carries:
   roofline      pass A (k_accumulate_vec), algorithmic bytes / average launch duration from HIP events recorded on
@@ -47,20 +49,23 @@ if REPO not in sys.path:
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); measured copy ceiling ~6290
 REFERENCE_CPU_FPS = 310.0      # the reference's own two frame loops on a C2 file, 1 core, read from disk
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: larger products are written as a fixed, seeded sample of their pixels
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
-    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=5, help='untimed scans before the timed region; one more untimed batch of --steps scans '
+                                                            '(at least 2 x (workers + 2)) follows them: warmup_scans counts both')
     ap.add_argument('--frames', type=int, default=2000, help='frames per GPU')
     ap.add_argument('--width', type=int, default=2000)
     ap.add_argument('--height', type=int, default=200)
     ap.add_argument('--bits', type=int, default=16)
     ap.add_argument('--mode', choices=['folder', 'sharded'], default='folder')
     ap.add_argument('--workers', type=int, default=0, help='scans in flight per process (0 = SHG_WORKERS or 4)')
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps scans each; the median one is quoted')
+    ap.add_argument('--repeats', type=int, default=1, help='timed regions of --steps scans each; the median one is quoted (the default, '
+                                                            '1, makes --steps the number of timed scans)')
     ap.add_argument('--stacks', type=int, default=0, help='distinct resident stacks the timed scans cycle over (0 = workers + 1)')
     ap.add_argument('--no-extra', action='store_true', help='skip the C4 (21 disks) and one-C5-file legs')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -71,6 +76,10 @@ def parse():
     ap.add_argument('--cpu-frames', type=int, default=0, help='frames of the CPU-baseline sample (0 = the whole scan)')
     ap.add_argument('--stages', action='store_true', help='print a per-stage wall-clock table to stderr')
     ap.add_argument('--shifts', default='0', help="requested pixel shifts, CLI syntax of -w: '0', 'a,b,c' or 'x:y:w' (C4 = -10:10:1)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the products of the last timed scan (what solex_do_work hands its caller: '
+                         'cc and protus of every requested shift) as DIR/<name>.npy, float32 (float64 where the product is), '
+                         'at most %d bytes in all' % DUMP_MAX_BYTES)
     return ap.parse_args()
 
 
@@ -256,6 +265,12 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
+    # The first batch after that collection allocates again what the collection released (about 1 ms: 0.42-0.44 instead of
+    # 0.37-0.38 ms a step in a 20-scan batch, with the profiler on or off), so one untimed batch of a region's size runs
+    # between it and the timed region -- at least two rounds through the pool's slots, as in extra_leg.
+    settle = max(args.steps, 2 * (workers + 2))
+    run_scans(settle, workers, first=max(args.warmup, 0))
+    warmup_scans = max(args.warmup, 0) + settle
     _lib.profile_reset()
     _lib.profile_enable(True, only=('accumulate', 'extract'))       # pass A (on the lane) and pass B (on the scans' own streams)
     region_s = timed_regions(args.steps, max(1, args.repeats))
@@ -273,6 +288,31 @@ def main():
     u = len(distinct)                                                   # distinct samples per row (4 for S=2: c, c+1, c+10, c+11)
     bytes_b = n_local * ih * (u * bpp + 2 * n_disks)
     ach = bytes_a / (acc_ms / acc_n * 1e-3) / 1e9 if acc_n else 0.0
+
+    # ---- --dump-outputs: the products of the last timed scan ------------------------------------------
+    # Keeping every scan's products inside the timed region would hold `steps` result buffers and change what is timed.  So the
+    # tail of the last region runs again, untimed, through the same route (same worker count, same stacks, ending on the same
+    # scan), this time handing its products back.  The path is deterministic -- the GPU tests hold every product bit for bit
+    # across routes, worker counts and runs -- so these are the arrays the timed scan computed.
+    dumped = None
+    if args.dump_outputs:
+        last_first = (len(region_s) - 1) * args.steps
+        tail = min(args.steps, 2 * workers)
+        first = last_first + args.steps - tail
+        got = run_scans(tail, workers, results=True, first=first)
+        torch.cuda.synchronize()
+        if rank == 0:
+            owned = [i for i, r in enumerate(got) if r is not None]      # (a frame-sharded scan's products are on its owner only)
+            if not owned:
+                raise SystemExit('bench.py: --dump-outputs: rank 0 holds the products of none of the last %d scans' % tail)
+            opts = options()
+            order = [s for s in dict.fromkeys([opts['ellipse_fit_shift'], 0] + list(opts['shift'])) if s in opts['shift']]
+            dumped = dump_products(args.dump_outputs, got[owned[-1]], order)
+            dumped['scan'] = first + owned[-1]
+            dumped['of_scans'] = '%d timed scans in %d region(s); scan i reads resident stack i mod %d' % (
+                len(region_s) * args.steps, len(region_s), n_stacks)
+        del got
+        barrier()
 
     # serial pass: one scan at a time, every entry point bracketed by events -> uncontended kernel durations
     serial_steps = max(3, min(10, args.steps))
@@ -435,7 +475,7 @@ def main():
             'value': round(total_frames / elapsed, 1), 'unit': 'frames/s',
             'value_decode_inclusive': e2e.get('value') if isinstance(e2e, dict) else None,
             'n_gpus': world, 'ranks_seen': td.get_world_size() if world > 1 else 1, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3), 'higher_is_better': True,
+            'warmup': args.warmup, 'warmup_scans': warmup_scans, 'ms_per_step': round(ms_per_step, 3), 'higher_is_better': True,
             'scaling': 'strong' if sharded else 'weak', 'vs_baseline': None, 'dtype': 'u16' if bpp == 2 else 'u8', 'data': 'synthetic',
             'config': {'workload': '%d-frame %d-bit SER, %dx%d frames, %s (S=%d disks), '
                                    'transversalium+ellipse on%s' % (
@@ -467,11 +507,42 @@ def main():
                                '(%.3f ms wall per scan there); gpu_busy_frac = that / ms_per_step' % (
                                    all_n // serial_steps, t_serial / serial_steps * 1e3),
             'roofline': roofline, 'cpu_baseline': cpu, 'e2e': e2e, 'sharded_c3': c3, 'c4': c4, 'c5_file': c5,
+            'dump_outputs': dumped,
         }
         print(json.dumps(line), flush=True)
     if world > 1:
         td.barrier()
         td.destroy_process_group()
+
+
+def dump_products(out_dir, products, shifts):
+    """products: one scan's [(cc, protus), ...] as solex_do_work returns it, one pair per requested shift in `shifts` order ->
+    out_dir/cc_shift<s>.npy and out_dir/protus_shift<s>.npy, float32 (float64 for a float64 product).  When the whole set would
+    exceed DUMP_MAX_BYTES, every array is written as the same fixed, seeded sample of its pixels (sorted flat indices,
+    numpy default_rng(0)), each array's share of the budget in proportion to its size.  -> what was written."""
+    import numpy as np
+    if len(products) != len(shifts):
+        raise RuntimeError('--dump-outputs: %d products for shifts %s' % (len(products), shifts))
+    arrays = {}
+    for s, (cc, protus) in zip(shifts, products):
+        for name, img in (('cc', cc), ('protus', protus)):
+            a = np.asarray(img)
+            arrays['%s_shift%d' % (name, s)] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_MAX_BYTES - 256 * len(arrays)                 # (room for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, a in arrays.items():
+        entry = {'shape': list(a.shape), 'dtype': str(a.dtype), 'sampled_px': None}
+        if total > budget:
+            keep = min(a.size, int(budget * a.nbytes / total) // a.itemsize)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.ravel()[idx]
+            entry['sampled_px'] = keep
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        info[name] = entry
+    return {'dir': os.path.abspath(out_dir), 'arrays': info,
+            'sampled': total > budget, 'bytes': sum(os.path.getsize(os.path.join(out_dir, n + '.npy')) for n in info)}
 
 
 def sharded_parity(sharded_tasks, whole_task, world):
