@@ -144,6 +144,20 @@ int shg_row_argmin_u16(const uint16_t* img, int64_t h, int64_t w, int64_t x0, in
 /* np.mean(img, axis=1) in float64 (solex_util.py:167). out[h]. */
 int shg_row_mean_u16(const uint16_t* img, int64_t h, int64_t w, double* out, shg_stream_t stream);
 
+/* ---- the spectral analyser's auto-dispersion loop ----- spectralAnalyserUI.py:271-300 (not on the SHG path)
+ * For each guess g (one workgroup each), s = scales[g], the atlas point k at x[k] = ((first + k * step_d) - anchor_wavelength)
+ * / s + anchor_x (NumPy's arange of :61 gives first + k * step_d exactly, step_d = (first + step) - first); the run of points
+ * with 0 <= x < w (select, :41-48) interpolated at pixels 0 .. w-1 by np.interp's rules from atlas_y[k] / 255 (:280);
+ * u[fill_lo:fill_hi] = np.mean(u) (:284, NumPy's pairwise sum: the rows are NumPy's to the bit); corr[g] =
+ * np.corrcoef(u, log_spectrum)[0, 1] (:289) within 1e-12.  log_spectrum[w] is float32 np.log(spectrum2) with its own window
+ * already filled (:286-287, the caller's).  run[g][2] (may be NULL) = the run's first and last point, first > last (and
+ * corr[g] NaN) when the run is empty.  row_of_guess[n_guesses] (NULL when n_rows = 0): the slot of rows[n_rows][w] that
+ * receives guess g's filled u, -1 for none.  2 <= w <= 8192, else SHG_E_ARG / SHG_E_UNSUPPORTED. */
+int shg_atlas_correlate(const uint8_t* atlas_y, int64_t n_atlas, double first, double step_d, double anchor_wavelength,
+                        double anchor_x, const float* log_spectrum, int64_t w, int64_t fill_lo, int64_t fill_hi,
+                        const double* scales, int64_t n_guesses, double* corr, int32_t* run, const int32_t* row_of_guess,
+                        int64_t n_rows, double* rows, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -747,3 +747,34 @@ def stream_read_ceiling(buf, mode=0, vecs_per_frame=0, shapes=None, reps=5):
         if rate > best[0]:
             best = (rate, (blocks, unroll))
     return best
+
+
+# ---- the spectral analyser (not on the SHG path) ------------------------------------------------
+def atlas_correlate(atlas_y, first, step_d, anchor_wavelength, anchor_x, log_spectrum, fill_lo, fill_hi, scales, row_guesses=()):
+    """The auto-dispersion loop of spectralAnalyserUI.py:271-300 (shg_atlas_correlate): atlas_y uint8 [n], log_spectrum float32 [w]
+    (window filled), scales float64 [G], all on one GPU -> (corr float64 [G], run int32 [G, 2], rows float64 [len(row_guesses), w]
+    holding the filled interpolated rows of those guesses, or None)."""
+    _dev(atlas_y, 'atlas_y')
+    _dev(log_spectrum, 'log_spectrum')
+    _dev(scales, 'scales')
+    for t, name, dt in ((atlas_y, 'atlas_y', torch.uint8), (log_spectrum, 'log_spectrum', torch.float32), (scales, 'scales', torch.float64)):
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise TypeError('%s must be a contiguous 1-D %s tensor' % (name, dt))
+    dev = scales.device
+    g, w = scales.shape[0], log_spectrum.shape[0]
+    corr = torch.empty(g, dtype=torch.float64, device=dev)
+    run = torch.empty((g, 2), dtype=torch.int32, device=dev)
+    row_guesses = [int(i) for i in row_guesses]
+    rows = slot = None
+    if row_guesses:
+        if min(row_guesses) < 0 or max(row_guesses) >= g or len(set(row_guesses)) != len(row_guesses):
+            raise ValueError('row_guesses must be distinct guess indices below %d' % g)
+        m = np.full(g, -1, dtype=np.int32)
+        m[row_guesses] = np.arange(len(row_guesses), dtype=np.int32)
+        slot = torch.from_numpy(m).to(dev)
+        rows = torch.empty((len(row_guesses), w), dtype=torch.float64, device=dev)
+    _lib.check(lib.shg_atlas_correlate(atlas_y.data_ptr(), atlas_y.shape[0], float(first), float(step_d), float(anchor_wavelength),
+                                       float(anchor_x), log_spectrum.data_ptr(), w, int(fill_lo), int(fill_hi), scales.data_ptr(), g,
+                                       corr.data_ptr(), run.data_ptr(), None if slot is None else slot.data_ptr(), len(row_guesses),
+                                       None if rows is None else rows.data_ptr(), _stream()), 'shg_atlas_correlate')
+    return corr, run, rows
