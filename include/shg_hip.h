@@ -158,6 +158,30 @@ int shg_atlas_correlate(const uint8_t* atlas_y, int64_t n_atlas, double first, d
                         const double* scales, int64_t n_guesses, double* corr, int32_t* run, const int32_t* row_of_guess,
                         int64_t n_rows, double* rows, shg_stream_t stream);
 
+/* ---- the Dopplergram (not a reference stage; tests/doppler_ref.py restates both calls in NumPy, bit for bit)
+ * shg_line_core_shift: the line-core position of every (slit row y, frame k) of a frame stack in file layout (n_frames, height,
+ * width, bytes_per_px, frame_stride_px as shg_extract_columns takes them).  p(j) = sample (y, j) of frame k after a1's rotation
+ * (out[i, j] = raw[j, W - 1 - i] when width > height), 8-bit samples x 256.  fit[ih][4] float64 (device); c = int(fit[y][0])
+ * (truncated, as a5), lo = max(c - H, 1), hi = min(c + H, iw - 2); NaN when fit[y][0] is not finite or hi - lo < 2.  j* = the
+ * first j in [lo, hi] with minimal p(j); NaN when j* == lo or j* == hi.  a, b, e = p(j* - 1), p(j*), p(j* + 1);
+ * delta = (double)(a - e) / (double)(2 * (a + e - 2 b)); d = (float)(((double)j* + delta) - fit[y][3]).
+ * map[y * row_pitch + col(k)] = d, col(k) = k_offset + k, or n_cols - 1 - (k_offset + k) with flip_x (as the disks).
+ * 1 <= half_width H <= 32, else SHG_E_UNSUPPORTED; a frame must hold < 4 GiB and n_cols < 2^31 (SHG_E_UNSUPPORTED). */
+int shg_line_core_shift(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px, int64_t frame_stride_px,
+                        const double* fit, int half_width, int flip_x, float* map, int64_t row_pitch, int64_t n_cols, int64_t k_offset,
+                        shg_stream_t stream);
+
+/* shg_doppler_finish: the raw map raw[h][w] (row pitch raw_pitch) in the products' geometry.  For every output pixel (r, c) of the
+ * corrected image (out_h x out_w, h00 h01 h02 = mat3 row 0 of ellipse_to_circle._warp_geometry, as shg_warp_rows_u16):
+ * x = (h00 c + h01 r) + h02, taps floor(x) and ceil(x) of raw row r, a tap outside [0, w) (or a row r >= h) NaN;
+ * v = (float)((1 - t) L + t R) in float64, t = x - floor(x), NaN propagating.  circle3 (host: cx, cy, rad; NULL or (-1, -1, -1): no mask):
+ * v = NaN where (c - cx)^2 + (r - cy)^2 > rad^2 (float64).  crop4 (host, NULL: none) = Solex_recon.crop_plan's (nw, lo, dx0, n):
+ * map[r][dx0 + i] = v(r, lo + i) for i < n, NaN elsewhere; map is out_h x nw (nw = out_w without a crop), row pitch map_pitch.
+ * png (may be NULL, row pitch png_pitch): 0 where v is NaN, else clip(rint(32768 + (double)v * (32767 / display_range)), 1, 65535). */
+int shg_doppler_finish(const float* raw, int64_t h, int64_t w, int64_t raw_pitch, double h00, double h01, double h02,
+                       int64_t out_h, int64_t out_w, const double* circle3, const int64_t* crop4, float* map, int64_t map_pitch,
+                       uint16_t* png, int64_t png_pitch, double display_range, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -84,6 +84,9 @@ SIGNATURES = {
     'shg_row_mean_u16': (c_int, [P, c_int64, c_int64, P, P]),
     'shg_atlas_correlate': (c_int, [P, c_int64, c_double, c_double, c_double, c_double, P, c_int64, c_int64, c_int64, P, c_int64,
                                     P, P, P, c_int64, P, P]),
+    'shg_line_core_shift': (c_int, [P, c_int64, c_int64, c_int64, c_int, c_int64, P, c_int, c_int, P, c_int64, c_int64, c_int64, P]),
+    'shg_doppler_finish': (c_int, [P, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_int64, c_int64, P, P, P, c_int64,
+                                   P, c_int64, c_double, P]),
     'shg_blur_fits_fused': (c_int, [c_int64, c_int]),
     'shg_blur_row_mean_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, P, P]),
     'shg_blur_argmin_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int64, c_int64, P, P, P]),

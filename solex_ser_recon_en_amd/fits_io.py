@@ -1,4 +1,4 @@
-"""Minimal FITS writer for the uint16 images the pipeline saves.
+"""Minimal FITS writer for the uint16 images the pipeline saves (and the float images of de-vignetting and the Dopplergram).
 
 The reference writes them with astropy (`fits.PrimaryHDU(img, header=hdr).writeto`,
 Solex_recon.py:80-82, 137-152; solex_util.py:204-206, 584-587).  For a uint16 array
@@ -54,9 +54,11 @@ def _card(key, value, comment=''):
 
 def fits_bytes(array, header=None):
     array = np.asarray(array)
-    if array.dtype == np.float64 and array.ndim == 2:
-        # a de-vignetted frame is float64 in the reference (solex_util.py:654): BITPIX = -64, no scaling
-        cards = [_card('SIMPLE', True, 'conforms to FITS standard'), _card('BITPIX', -64, 'array data type'),
+    if array.dtype in (np.float64, np.float32) and array.ndim == 2:
+        # a de-vignetted frame is float64 in the reference (solex_util.py:654): BITPIX = -64, no scaling; a Dopplergram is
+        # float32 (BITPIX = -32, NaN where there is no data)
+        bitpix = -64 if array.dtype == np.float64 else -32
+        cards = [_card('SIMPLE', True, 'conforms to FITS standard'), _card('BITPIX', bitpix, 'array data type'),
                  _card('NAXIS', 2, 'number of array dimensions'), _card('NAXIS1', array.shape[1]),
                  _card('NAXIS2', array.shape[0])]
         for key, value in (header or {}).items():
@@ -65,10 +67,10 @@ def fits_bytes(array, header=None):
         cards.append('END'.ljust(80))
         head = ''.join(cards).encode('ascii')
         head += b' ' * (-len(head) % BLOCK)
-        data = array.astype('>f8').tobytes()
+        data = array.astype('>f8' if bitpix == -64 else '>f4').tobytes()
         return head + data + b'\0' * (-len(data) % BLOCK)
     if array.dtype != np.uint16 or array.ndim != 2:
-        raise TypeError('fits_bytes writes 2-D uint16 (or float64) images, got %s %s' % (array.dtype, array.shape))
+        raise TypeError('fits_bytes writes 2-D uint16 (or float64 / float32) images, got %s %s' % (array.dtype, array.shape))
     cards = [_card('SIMPLE', True, 'conforms to FITS standard'), _card('BITPIX', 16, 'array data type'),
              _card('NAXIS', 2, 'number of array dimensions'), _card('NAXIS1', array.shape[1]),
              _card('NAXIS2', array.shape[0])]
@@ -88,9 +90,8 @@ def write_fits(path, array, header=None):
         f.write(fits_bytes(array, header))
 
 
-def read_fits_u16(path):
-    """Inverse of write_fits (tests and the CLI round trip)."""
-    raw = open(path, 'rb').read()
+def _cards(raw):
+    """The header's cards (key -> value text) and the offset of the data."""
     cards = {}
     pos = 0
     while True:
@@ -99,8 +100,34 @@ def read_fits_u16(path):
         if card.startswith('END'):
             break
         if '=' in card[:10]:
-            cards[card[:8].strip()] = card[10:].split('/')[0].strip()
-    pos += -pos % BLOCK
+            value = card[10:].strip()
+            if value.startswith("'"):                 # a string ends at its closing quote ('' is a quote inside it)
+                end = 1
+                while True:
+                    end = value.index("'", end)
+                    if value[end + 1:end + 2] != "'":
+                        break
+                    end += 2
+                cards[card[:8].strip()] = value[:end + 1]
+            else:
+                cards[card[:8].strip()] = value.split('/')[0].strip()
+    return cards, pos + (-pos % BLOCK)
+
+
+def read_fits_u16(path):
+    """Inverse of write_fits (tests and the CLI round trip)."""
+    raw = open(path, 'rb').read()
+    cards, pos = _cards(raw)
     w, h = int(cards['NAXIS1']), int(cards['NAXIS2'])
     data = np.frombuffer(raw, dtype='>i2', count=w * h, offset=pos).astype(np.int32) + int(float(cards.get('BZERO', 0)))
     return data.reshape(h, w).astype(np.uint16), cards
+
+
+def read_fits_f32(path):
+    """Inverse of write_fits for a float32 (BITPIX = -32) image -> (float32 [h, w], cards)."""
+    raw = open(path, 'rb').read()
+    cards, pos = _cards(raw)
+    if int(cards['BITPIX']) != -32:
+        raise ValueError('%s: BITPIX %s, not -32' % (path, cards['BITPIX']))
+    w, h = int(cards['NAXIS1']), int(cards['NAXIS2'])
+    return np.frombuffer(raw, dtype='>f4', count=w * h, offset=pos).astype(np.float32).reshape(h, w), cards

@@ -778,3 +778,47 @@ def atlas_correlate(atlas_y, first, step_d, anchor_wavelength, anchor_x, log_spe
                                        corr.data_ptr(), run.data_ptr(), None if slot is None else slot.data_ptr(), len(row_guesses),
                                        None if rows is None else rows.data_ptr(), _stream()), 'shg_atlas_correlate')
     return corr, run, rows
+
+
+# ---- the Dopplergram -------------------------------------------------------------------------------
+def line_core_shift(stack, fit, half_width, flip_x=False, n_cols=None, k_offset=0, out=None):
+    """shg_line_core_shift: the line-core shift (pixels, float32) of every slit row and frame -> map [ih, n_cols] (a view of a
+    row-pitched buffer; columns of frames this call does not hold stay NaN).  fit float64 [ih, 4] (host array or GPU tensor)."""
+    n, h, w, bpp = stack_geometry(stack)
+    dev = stack.device
+    ih = max(h, w)
+    fit = torch.as_tensor(np.ascontiguousarray(fit, dtype=np.float64) if not isinstance(fit, torch.Tensor) else fit).to(dev)
+    if fit.dtype != torch.float64 or tuple(fit.shape) != (ih, 4):
+        raise ValueError('fit must be float64 [%d, 4]' % ih)
+    fit = fit.contiguous()
+    n_cols = n if n_cols is None else int(n_cols)
+    if out is None:
+        pitch = (n_cols + 63) // 64 * 64
+        out = torch.empty((ih, pitch), dtype=torch.float32, device=dev)[:, :n_cols]
+        if n_cols != n or int(k_offset) != 0:
+            out.fill_(float('nan'))
+    if tuple(out.shape) != (ih, n_cols) or out.dtype != torch.float32 or out.stride(1) != 1:
+        raise ValueError('out must be a float32 [%d, %d] view with unit column stride' % (ih, n_cols))
+    _lib.check(lib.shg_line_core_shift(stack.data_ptr(), n, h, w, bpp, frame_stride(stack), fit.data_ptr(), int(half_width),
+                                       int(bool(flip_x)), out.data_ptr(), out.stride(0), n_cols, int(k_offset), _stream()),
+               'shg_line_core_shift')
+    return out
+
+
+def doppler_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None, display_range=None):
+    """shg_doppler_finish: the raw map float32 [ih, N] resampled as the ellipse -> circle warp (mat3 row 0: h00 h01 h02) with NaN
+    for taps outside, masked outside `circle` (cx, cy, r; None or (-1, -1, -1): no mask), cropped / padded by `crop` (crop_plan's
+    (nw, lo, dx0, n), None: none) with NaN -> (map float32 [out_h, nw], png uint16 [out_h, nw] or None).  display_range R: also the
+    16-bit display plane, 0 for NaN, clip(rint(32768 + d * 32767 / R), 1, 65535) elsewhere."""
+    ptr, h, w, pitch = _img(raw, 'raw', torch.float32)
+    dev = raw.device
+    nw = int(out_w) if crop is None else int(crop[0])
+    out = torch.empty((int(out_h), nw), dtype=torch.float32, device=dev)
+    png = None if display_range is None else torch.empty((int(out_h), nw), dtype=torch.uint16, device=dev)
+    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    c4 = None if crop is None else np.ascontiguousarray([int(v) for v in crop], dtype=np.int64)
+    _lib.check(lib.shg_doppler_finish(ptr, h, w, pitch, float(h00), float(h01), float(h02), int(out_h), int(out_w),
+                                      None if c3 is None else c3.ctypes.data, None if c4 is None else c4.ctypes.data,
+                                      out.data_ptr(), out.stride(0), None if png is None else png.data_ptr(), nw,
+                                      0.0 if display_range is None else float(display_range), _stream()), 'shg_doppler_finish')
+    return out, png
