@@ -182,6 +182,37 @@ int shg_doppler_finish(const float* raw, int64_t h, int64_t w, int64_t raw_pitch
                        int64_t out_h, int64_t out_w, const double* circle3, const int64_t* crop4, float* map, int64_t map_pitch,
                        uint16_t* png, int64_t png_pitch, double display_range, shg_stream_t stream);
 
+/* ---- line-profile maps (not a reference stage; tests/lineprofile_ref.py restates both calls in NumPy, bit for bit)
+ * shg_line_profile: five planes of every (slit row y, frame k) of a frame stack in shg_line_core_shift's layout and with its p(j),
+ * measured around the line shifted by the integer S (`shift`, the -w shift; 0 = the fitted line).  c = (int64)(fit[y][0] + (double)S)
+ * (truncated), lo = max(c - H, 1), hi = min(c + H, iw - 2); every plane NaN when fit[y][0] is not finite or hi - lo < 2.
+ * ref = fit[y][3] + (double)S.  j* = the first j in [lo, hi] with minimal p(j); a, b, e = p(j* - 1), p(j*), p(j* + 1), den = a + e - 2b;
+ * shift, core and width are NaN when j* == lo or j* == hi.  Every integer below is exact in float64, every step one IEEE operation:
+ *   shift = (float)(((double)j* + (double)(a - e) / (double)(2 den)) - ref)            (= shg_line_core_shift's at S = 0)
+ *   core_d = (double)b - (double)((a - e)^2) / (8.0 (double)den), core = (float)core_d
+ *   C2 = p(lo) + p(hi) (integer), half = 0.5 (0.5 (double)C2 + core_d); width NaN unless p(j*) < half;
+ *   jl = the largest j in [lo, j*) with p(j) >= half, xl = (double)jl + ((double)p(jl) - half) / (double)(p(jl) - p(jl + 1));
+ *   jr = the smallest j in (j*, hi] with p(j) >= half, xr = (double)jr - ((double)p(jr) - half) / (double)(p(jr) - p(jr - 1));
+ *   width = (float)(xr - xl), NaN when jl or jr does not exist
+ *   n = hi - lo + 1, int64 S0 = n C2 - 2 sum p, S1 = C2 sum j - 2 sum j p over [lo, hi];
+ *   cog = (float)((double)S1 / (double)S0 - ref), NaN when S0 <= 0;  ew = (float)((double)S0 / (double)C2), NaN when C2 == 0.
+ * planes[q * plane_stride + y * row_pitch + col(k)], q = 0 shift, 1 core, 2 width, 3 cog, 4 ew; col(k) as shg_line_core_shift.
+ * 1 <= H <= 32, a frame < 4 GiB, n_cols < 2^31 (else SHG_E_UNSUPPORTED); 3 - iw - H < S < iw - 3 + H (else no line inside the
+ * frame has a window: SHG_E_ARG). */
+int shg_line_profile(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px, int64_t frame_stride_px,
+                     const double* fit, int half_width, int shift, int flip_x, float* planes, int64_t plane_stride, int64_t row_pitch,
+                     int64_t n_cols, int64_t k_offset, shg_stream_t stream);
+
+/* shg_line_profile_finish: the five raw planes raw[q][h][w] (plane stride raw_plane_stride, row pitch raw_pitch) in the products'
+ * geometry, each plane bit-identical to shg_doppler_finish with png = NULL: maps[q * map_plane_stride + r * map_pitch + c].
+ * png (may be NULL; png[q * png_plane_stride + r * png_pitch + c]): 0 where the value v is NaN, else clip(rint(e), 1, 65535) with
+ * e = 32768 + (double)v * (32767 / display_range) for shift and cog, (double)v for core, 1 + (double)v * (65534 / (2 H + 1)) for
+ * width and ew (H = half_width, 1 <= H <= 32). */
+int shg_line_profile_finish(const float* raw, int64_t raw_plane_stride, int64_t h, int64_t w, int64_t raw_pitch, double h00,
+                            double h01, double h02, int64_t out_h, int64_t out_w, const double* circle3, const int64_t* crop4,
+                            float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
+                            int64_t png_pitch, int half_width, double display_range, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

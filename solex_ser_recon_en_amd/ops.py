@@ -822,3 +822,58 @@ def doppler_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None, dis
                                       out.data_ptr(), out.stride(0), None if png is None else png.data_ptr(), nw,
                                       0.0 if display_range is None else float(display_range), _stream()), 'shg_doppler_finish')
     return out, png
+
+
+# ---- line-profile maps ----------------------------------------------------------------------------
+LINE_PROFILE_PLANES = ('shift', 'core', 'width', 'cog', 'ew')
+
+
+def line_profile(stack, fit, half_width, shift=0, flip_x=False, n_cols=None, k_offset=0, out=None):
+    """shg_line_profile: the five planes (LINE_PROFILE_PLANES, float32) of every slit row and frame, measured around the line
+    shifted by `shift` pixels -> planes [5, ih, n_cols] (a view of a row-pitched buffer; columns of frames this call does not hold
+    stay NaN).  fit float64 [ih, 4] (host array or GPU tensor)."""
+    n, h, w, bpp = stack_geometry(stack)
+    dev = stack.device
+    ih = max(h, w)
+    fit = torch.as_tensor(np.ascontiguousarray(fit, dtype=np.float64) if not isinstance(fit, torch.Tensor) else fit).to(dev)
+    if fit.dtype != torch.float64 or tuple(fit.shape) != (ih, 4):
+        raise ValueError('fit must be float64 [%d, 4]' % ih)
+    fit = fit.contiguous()
+    n_cols = n if n_cols is None else int(n_cols)
+    if out is None:
+        pitch = (n_cols + 63) // 64 * 64
+        out = torch.empty((len(LINE_PROFILE_PLANES), ih, pitch), dtype=torch.float32, device=dev)[:, :, :n_cols]
+        if n_cols != n or int(k_offset) != 0:
+            out.fill_(float('nan'))
+    if tuple(out.shape) != (len(LINE_PROFILE_PLANES), ih, n_cols) or out.dtype != torch.float32 or out.stride(2) != 1:
+        raise ValueError('out must be a float32 [5, %d, %d] view with unit column stride' % (ih, n_cols))
+    _lib.check(lib.shg_line_profile(stack.data_ptr(), n, h, w, bpp, frame_stride(stack), fit.data_ptr(), int(half_width), int(shift),
+                                    int(bool(flip_x)), out.data_ptr(), out.stride(0), out.stride(1), n_cols, int(k_offset), _stream()),
+               'shg_line_profile')
+    return out
+
+
+def line_profile_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None, half_width=None, display_range=None):
+    """shg_line_profile_finish: the five raw planes float32 [5, ih, N] through doppler_finish's geometry, all in one launch ->
+    (maps float32 [5, out_h, nw], png uint16 [5, out_h, nw] or None).  With half_width H and display_range R also the display
+    planes: 0 for NaN; shift and cog as the Dopplergram's, core clip(rint(v), 1, 65535), width and ew
+    clip(rint(1 + v * 65534 / (2H + 1)), 1, 65535)."""
+    _dev(raw, 'raw')
+    if raw.dim() != 3 or raw.shape[0] != len(LINE_PROFILE_PLANES) or raw.dtype != torch.float32 or raw.stride(2) != 1:
+        raise ValueError('raw must be a float32 [5, h, w] view with unit column stride')
+    if (half_width is None) != (display_range is None):
+        raise ValueError('the display planes need both half_width and display_range')
+    _, h, w = raw.shape
+    dev = raw.device
+    nw = int(out_w) if crop is None else int(crop[0])
+    out = torch.empty((len(LINE_PROFILE_PLANES), int(out_h), nw), dtype=torch.float32, device=dev)
+    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=dev)
+    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    c4 = None if crop is None else np.ascontiguousarray([int(v) for v in crop], dtype=np.int64)
+    _lib.check(lib.shg_line_profile_finish(raw.data_ptr(), raw.stride(0), h, w, raw.stride(1), float(h00), float(h01), float(h02),
+                                           int(out_h), int(out_w), None if c3 is None else c3.ctypes.data,
+                                           None if c4 is None else c4.ctypes.data, out.data_ptr(), out.stride(0), out.stride(1),
+                                           None if png is None else png.data_ptr(), out.stride(0), out.stride(1),
+                                           0 if half_width is None else int(half_width),
+                                           0.0 if display_range is None else float(display_range), _stream()), 'shg_line_profile_finish')
+    return out, png
