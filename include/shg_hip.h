@@ -152,7 +152,9 @@ int shg_row_mean_u16(const uint16_t* img, int64_t h, int64_t w, double* out, shg
  * np.corrcoef(u, log_spectrum)[0, 1] (:289) within 1e-12.  log_spectrum[w] is float32 np.log(spectrum2) with its own window
  * already filled (:286-287, the caller's).  run[g][2] (may be NULL) = the run's first and last point, first > last (and
  * corr[g] NaN) when the run is empty.  row_of_guess[n_guesses] (NULL when n_rows = 0): the slot of rows[n_rows][w] that
- * receives guess g's filled u, -1 for none.  2 <= w <= 8192, else SHG_E_ARG / SHG_E_UNSUPPORTED. */
+ * receives guess g's filled u, -1 for none.  2 <= w <= 8192, else SHG_E_ARG / SHG_E_UNSUPPORTED.  Every scale must be finite
+ * and positive (not checked: the run search assumes x rises with k; another scale gives a run with no meaning, and a negative one
+ * walks the whole atlas per thread). */
 int shg_atlas_correlate(const uint8_t* atlas_y, int64_t n_atlas, double first, double step_d, double anchor_wavelength,
                         double anchor_x, const float* log_spectrum, int64_t w, int64_t fill_lo, int64_t fill_hi,
                         const double* scales, int64_t n_guesses, double* corr, int32_t* run, const int32_t* row_of_guess,

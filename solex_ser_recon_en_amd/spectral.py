@@ -124,16 +124,21 @@ def scale_guesses(w, n_guesses=None):
 
 def correlate(spectrum2, anchor_x, anchor_wavelength, atlas, scales, row_guesses=(), device=None):
     """corr [len(scales)] of the auto-dispersion loop for the given scales, and the filled interpolated rows of `row_guesses`
-    (float64 [len(row_guesses), W], or None) -> (corr, rows), NumPy arrays."""
+    (float64 [len(row_guesses), W], or None) -> (corr, rows), NumPy arrays.  ValueError for a scale that is not finite or not
+    positive (the kernel's run search assumes x rises with k)."""
     w = int(np.asarray(spectrum2).shape[0])
     if not atlas.first <= anchor_wavelength <= atlas.a_last:
         raise ValueError('anchor wavelength %r lies outside the atlas [%r, %r]' % (anchor_wavelength, atlas.first, atlas.a_last))
     if w < 2:
         raise ValueError('a spectrum of %d pixel(s) has no correlation' % w)
+    scales = np.ascontiguousarray(scales, dtype=np.float64)
+    bad = np.flatnonzero(~(np.isfinite(scales) & (scales > 0)))
+    if bad.size:
+        raise ValueError('scale %r (guess %d) is not a finite positive dispersion' % (float(scales[bad[0]]), bad[0]))
     lspec = log_spectrum(spectrum2, anchor_x)
     lo, hi = window(anchor_x, w)
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    sc = torch.from_numpy(np.ascontiguousarray(scales, dtype=np.float64)).to(device)
+    sc = torch.from_numpy(scales).to(device)
     corr, run, rows = ops.atlas_correlate(atlas.on(device), atlas.first, atlas.d, anchor_wavelength, anchor_x,
                                           torch.from_numpy(lspec).to(device), lo, hi, sc, row_guesses)
     run = run.cpu().numpy()
