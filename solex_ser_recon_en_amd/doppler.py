@@ -52,19 +52,17 @@ def velocity_factor(dispersion, wavelength):
     return (float(dispersion) / float(wavelength)) * C_KM_S
 
 
-def dopplergram(file_or_reader, options=None, half_width=5, display_range=2.0, dispersion=None, wavelength=None):
-    """The Dopplergram of one scan -> dict(raw = float32 [ih, N] shift in pixels per slit row and frame; map = float32, the raw map
-    resampled to the corrected image, NaN off the disk and in the crop's padding, in `units`; png = uint16 display plane of the
-    pixel map (0 = NaN, 32768 +- 32767 at +-display_range pixels); circle (-1, -1, -1 without a limb fit), ratio, phi, crop (the
-    crop_plan, or None), fit [ih, 4], units ('pixel', or 'km/s' when dispersion and wavelength are both given)).
-    options: SHG_MAIN's (flip_x, ratio_fixe, slant_fix, crop_width_square, fixed_width, ellipse_fit_shift are used)."""
+def _line_maps(file_or_reader, options, half_width, display_range, dispersion, wavelength, sharded, measure, finish, check_frame=None):
+    """The driver dopplergram() and lineprofile.line_profile_maps() share: argument checks, reader (`sharded`: the refusal of a
+    frame-sharded scan), line fit, raw = measure(stack, fit, flip_x) and (maps, png) = finish(raw, h00, h01, h02, out_h, out_w, circle,
+    crop) in the products' geometry.  check_frame(iw) may refuse the frame before the fit.  -> (raw, maps, png as NumPy arrays, the
+    fields of the result dict both share, km/s per pixel or None)."""
     from . import SHG_MAIN, dist
     from .ellipse_to_circle import _warp_geometry
     from .fits_io import make_header
     from .Solex_recon import crop_plan
     from .solex_util import compute_mean_return_fit
     from .video_reader import video_reader
-    half_width = int(half_width)
     if not 1 <= half_width <= MAX_HALF_WIDTH:
         raise ValueError('half_width must lie in [1, %d], got %d' % (MAX_HALF_WIDTH, half_width))
     if not (math.isfinite(display_range) and display_range > 0):
@@ -77,23 +75,41 @@ def dopplergram(file_or_reader, options=None, half_width=5, display_range=2.0, d
     opts.update(save_fit=False, flag_display=False, _nolog=True, basefich0='')
     rdr = file_or_reader if hasattr(file_or_reader, 'device_stack') else video_reader(file_or_reader)
     if dist.is_sharded(rdr):
-        raise ValueError('the Dopplergram of a frame-sharded scan is not supported')
+        raise ValueError(sharded)
     ih, iw, n = int(rdr.ih), int(rdr.iw), int(rdr.FrameCount)
+    if check_frame is not None:
+        check_frame(iw)
     _, fit, _, _ = compute_mean_return_fit(rdr, opts, make_header(rdr), iw, ih, '')
-    flip = bool(opts['flip_x'])
-    raw = ops.line_core_shift(rdr.device_stack(), fit, half_width, flip_x=flip)
+    raw = measure(rdr.device_stack(), fit, bool(opts['flip_x']))
     circle, ratio, phi = _geometry(rdr, fit, opts)
     _, _, mat3, out_h, out_w, _, _ = _warp_geometry(phi, ratio, ih, n)
     crop, circle_out = crop_plan(out_h, out_w, circle, opts)
-    dmap, png = ops.doppler_finish(raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, circle, crop, display_range)
-    dmap = dmap.cpu().numpy()
-    units = 'pixel'
-    if dispersion is not None:
-        dmap = (dmap.astype(np.float64) * velocity_factor(dispersion, wavelength)).astype(np.float32)
-        units = 'km/s'
-    return {'raw': raw.contiguous().cpu().numpy(), 'map': dmap, 'png': png.cpu().numpy(), 'circle': circle, 'circle_out': circle_out,
-            'ratio': ratio, 'phi': phi, 'crop': crop, 'fit': fit, 'units': units, 'half_width': half_width,
-            'display_range': float(display_range), 'dispersion': dispersion, 'wavelength': wavelength}
+    maps, png = finish(raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, circle, crop)
+    common = {'circle': circle, 'circle_out': circle_out, 'ratio': ratio, 'phi': phi, 'crop': crop, 'fit': fit, 'half_width': half_width,
+              'display_range': float(display_range), 'dispersion': dispersion, 'wavelength': wavelength}
+    factor = None if dispersion is None else velocity_factor(dispersion, wavelength)
+    return raw.contiguous().cpu().numpy(), maps.cpu().numpy(), png.cpu().numpy(), common, factor
+
+
+def _km_s(m, factor):
+    """A pixel-shift map in km/s."""
+    return (m.astype(np.float64) * factor).astype(np.float32)
+
+
+def dopplergram(file_or_reader, options=None, half_width=5, display_range=2.0, dispersion=None, wavelength=None):
+    """The Dopplergram of one scan -> dict(raw = float32 [ih, N] shift in pixels per slit row and frame; map = float32, the raw map
+    resampled to the corrected image, NaN off the disk and in the crop's padding, in `units`; png = uint16 display plane of the
+    pixel map (0 = NaN, 32768 +- 32767 at +-display_range pixels); circle (-1, -1, -1 without a limb fit), ratio, phi, crop (the
+    crop_plan, or None), fit [ih, 4], units ('pixel', or 'km/s' when dispersion and wavelength are both given)).
+    options: SHG_MAIN's (flip_x, ratio_fixe, slant_fix, crop_width_square, fixed_width, ellipse_fit_shift are used)."""
+    half_width = int(half_width)
+    raw, dmap, png, res, factor = _line_maps(
+        file_or_reader, options, half_width, display_range, dispersion, wavelength,
+        'the Dopplergram of a frame-sharded scan is not supported',
+        lambda stack, fit, flip: ops.line_core_shift(stack, fit, half_width, flip_x=flip),
+        lambda raw, *geometry: ops.doppler_finish(raw, *geometry, display_range))
+    res.update(raw=raw, map=dmap if factor is None else _km_s(dmap, factor), png=png, units='pixel' if factor is None else 'km/s')
+    return res
 
 
 def disk_stats(res):
@@ -118,46 +134,47 @@ def disk_stats(res):
 
 
 # ---- command line ---------------------------------------------------------------------------------
-def _parser():
-    p = argparse.ArgumentParser(prog='python -m solex_ser_recon_en_amd.doppler',
-                                usage='%(prog)s FILE [--half-width H] [--range R] [--dispersion D --wavelength L | --atlas A --anchor L] '
-                                      '[SHG_MAIN flags]',
-                                description='Line-of-sight velocity map (Dopplergram) of a scan, in the geometry of its products.')
-    p.add_argument('--half-width', type=int, default=5, help='pixels either side of the fitted line searched for the core (1..32)')
-    p.add_argument('--range', type=float, default=2.0, help='PNG display range: +-R pixels of shift map to 1 .. 65535')
-    p.add_argument('--dispersion', type=float, help='A / pixel (with --wavelength: the map in km/s)')
-    p.add_argument('--wavelength', type=float, help='A, the line the scan is centred on')
+def _parser(prog, usage, description, half_width, helps, extra=None):
+    """The parser of the flags both CLIs take; helps = the help of --half-width, --range, --dispersion, --wavelength; extra(p) adds
+    a CLI's own flags after --half-width."""
+    p = argparse.ArgumentParser(prog=prog, usage=usage, description=description)
+    p.add_argument('--half-width', type=int, default=half_width, help=helps[0])
+    if extra is not None:
+        extra(p)
+    p.add_argument('--range', type=float, default=2.0, help=helps[1])
+    p.add_argument('--dispersion', type=float, help=helps[2])
+    p.add_argument('--wavelength', type=float, help=helps[3])
     p.add_argument('--atlas', help='atlas in alps.npz layout: the dispersion from the spectral analyser\'s fit')
     p.add_argument('--anchor', type=float, help='A, the line the scan is centred on (with --atlas)')
     return p
 
 
-def main(argv=None):
+def _cli(p, argv, single, w_flag, extra_checks=None, positive=()):
+    """The command line both CLIs share: parse, validate (`single`, `w_flag`: the refusals under torchrun and of -w; extra_checks(args)
+    after --range, `positive`: more flags that must be positive), the SHG_MAIN flags, the one file and the atlas -> (args, opts, path,
+    atlas or None).  Errors exit through p.error."""
     from . import CLI_handler, SHG_MAIN, spectral
-    from .fits_io import make_header, write_fits
-    from .png_io import write_png
-    from .solex_util import output_path
-    from .video_reader import video_reader
-    p = _parser()
     args, rest = p.parse_known_args(sys.argv[1:] if argv is None else list(argv))
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        p.error('the Dopplergram is single-process: run it without torchrun')
+        p.error(single)
     if not 1 <= args.half_width <= MAX_HALF_WIDTH:
         p.error('--half-width must lie in [1, %d]' % MAX_HALF_WIDTH)
     if not (math.isfinite(args.range) and args.range > 0):
         p.error('--range must be positive')
+    if extra_checks is not None:
+        extra_checks(args)
     if (args.dispersion is None) != (args.wavelength is None):
         p.error('--dispersion and --wavelength go together')
     if (args.atlas is None) != (args.anchor is None):
         p.error('--atlas and --anchor go together')
     if args.atlas is not None and args.dispersion is not None:
         p.error('--atlas / --anchor and --dispersion / --wavelength exclude each other')
-    for name in ('dispersion', 'wavelength', 'anchor'):
+    for name in ('dispersion', 'wavelength', 'anchor') + tuple(positive):
         v = getattr(args, name)
         if v is not None and not (math.isfinite(v) and v > 0):
             p.error('--%s must be positive' % name)
     if any(a.startswith('-') and 'w' in a for a in rest):
-        p.error('-w is not a Dopplergram flag: the line core is searched around the fitted line')
+        p.error(w_flag)
     opts = SHG_MAIN.default_options()
     try:
         with contextlib.redirect_stdout(sys.stderr):            # the SHG_MAIN parser reports on stdout: keep it for the JSON line
@@ -174,30 +191,61 @@ def main(argv=None):
         atlas = spectral.load_atlas(args.atlas) if args.atlas is not None else None
     except (OSError, KeyError, ValueError) as e:
         p.error('--atlas: %s' % e)
+    return args, opts, path, atlas
+
+
+def _cli_dispersion(rdr, opts, args, atlas):
+    """(dispersion, wavelength, the spectral analysis or None): the flags', or with --atlas / --anchor the analyser's fit at the anchor."""
+    from . import spectral
+    if atlas is None:
+        return args.dispersion, args.wavelength, None
+    a = spectral.analyse(rdr, opts)
+    return spectral.auto_dispersion(a['spectrum2'], a['anchor_x'], args.anchor, atlas)[0], args.anchor, a
+
+
+def _write_pair(stem, opts, rdr, m, png, units, half_width, dispersion, wavelength, **keys):
+    """<stem>.fits (float32 map, header BUNIT, HALFWID, keys, DISPERS / WAVELEN with a dispersion) and <stem>.png (16-bit display
+    plane), both rotated by img_rotate -> (fits path, png path, shape written)."""
+    from .fits_io import make_header, write_fits
+    from .png_io import write_png
+    from .solex_util import output_path
+    hdr = make_header(rdr)
+    hdr['BUNIT'] = units
+    hdr['HALFWID'] = half_width
+    for k, v in keys.items():
+        hdr[k] = v
+    if dispersion is not None:
+        hdr['DISPERS'] = float(dispersion)
+        hdr['WAVELEN'] = float(wavelength)
+    k = opts['img_rotate'] // 90
+    fits_path, png_path = output_path(stem + '.fits', opts), output_path(stem + '.png', opts)
+    m = np.ascontiguousarray(np.rot90(m, k))
+    write_fits(fits_path, m, hdr)
+    write_png(png_path, np.ascontiguousarray(np.rot90(png, k)), 0)
+    return fits_path, png_path, list(m.shape)
+
+
+def main(argv=None):
+    from .video_reader import video_reader
+    p = _parser('python -m solex_ser_recon_en_amd.doppler',
+                '%(prog)s FILE [--half-width H] [--range R] [--dispersion D --wavelength L | --atlas A --anchor L] [SHG_MAIN flags]',
+                'Line-of-sight velocity map (Dopplergram) of a scan, in the geometry of its products.', 5,
+                ('pixels either side of the fitted line searched for the core (1..32)',
+                 'PNG display range: +-R pixels of shift map to 1 .. 65535', 'A / pixel (with --wavelength: the map in km/s)',
+                 'A, the line the scan is centred on'))
+    args, opts, path, atlas = _cli(p, argv, 'the Dopplergram is single-process: run it without torchrun',
+                                   '-w is not a Dopplergram flag: the line core is searched around the fitted line')
     try:
         rdr = video_reader(path)
-        dispersion, wavelength = args.dispersion, args.wavelength
-        if atlas is not None:
-            a = spectral.analyse(rdr, opts)
-            dispersion = spectral.auto_dispersion(a['spectrum2'], a['anchor_x'], args.anchor, atlas)[0]
-            wavelength = args.anchor
+        dispersion, wavelength, _ = _cli_dispersion(rdr, opts, args, atlas)
         res = dopplergram(rdr, opts, args.half_width, args.range, dispersion, wavelength)
     except ValueError as e:
         print('error: %s' % e, file=sys.stderr)
         return 1
-    base = os.path.splitext(path)[0]
-    k = opts['img_rotate'] // 90
-    hdr = make_header(rdr)
-    hdr['BUNIT'] = res['units']
-    hdr['HALFWID'] = res['half_width']
-    if dispersion is not None:
-        hdr['DISPERS'] = float(dispersion)
-        hdr['WAVELEN'] = float(wavelength)
-    fits_path, png_path = output_path(base + '_doppler.fits', opts), output_path(base + '_doppler.png', opts)
-    write_fits(fits_path, np.ascontiguousarray(np.rot90(res['map'], k)), hdr)
-    write_png(png_path, np.ascontiguousarray(np.rot90(res['png'], k)), 0)
-    out = {'fits': fits_path, 'png': png_path, 'shape': list(np.rot90(res['map'], k).shape), 'units': res['units'],
-           'half_width': res['half_width'], 'display_range': res['display_range'], 'dispersion': dispersion, 'wavelength': wavelength}
+    fits_path, png_path, shape = _write_pair(os.path.splitext(path)[0] + '_doppler', opts, rdr, res['map'], res['png'], res['units'],
+                                             res['half_width'], dispersion, wavelength)
+    out = {'fits': fits_path, 'png': png_path, 'shape': shape, 'units': res['units'], 'half_width': res['half_width'],
+           'display_range': res['display_range'], 'dispersion': dispersion, 'wavelength': wavelength}
     out.update(disk_stats(res))
     out.update(circle=list(res['circle']), ratio=res['ratio'], phi=res['phi'], crop=None if res['crop'] is None else list(res['crop']))
     print(json.dumps(out), flush=True)

@@ -780,25 +780,48 @@ def atlas_correlate(atlas_y, first, step_d, anchor_wavelength, anchor_x, log_spe
     return corr, run, rows
 
 
-# ---- the Dopplergram -------------------------------------------------------------------------------
-def line_core_shift(stack, fit, half_width, flip_x=False, n_cols=None, k_offset=0, out=None):
-    """shg_line_core_shift: the line-core shift (pixels, float32) of every slit row and frame -> map [ih, n_cols] (a view of a
-    row-pitched buffer; columns of frames this call does not hold stay NaN).  fit float64 [ih, 4] (host array or GPU tensor)."""
+# ---- the Dopplergram and the line-profile maps ------------------------------------------------------
+LINE_PROFILE_PLANES = ('shift', 'core', 'width', 'cog', 'ew')
+
+
+def _line_map_setup(stack, fit, n_cols, k_offset, out, planes=()):
+    """What line_core_shift and line_profile share -> (n, h, w, bpp, fit as a contiguous float64 [ih, 4] tensor on the stack's device,
+    n_cols, out float32 [*planes, ih, n_cols]: the caller's, or a view of a new row-pitched buffer, NaN when this call does not fill it)."""
     n, h, w, bpp = stack_geometry(stack)
     dev = stack.device
     ih = max(h, w)
     fit = torch.as_tensor(np.ascontiguousarray(fit, dtype=np.float64) if not isinstance(fit, torch.Tensor) else fit).to(dev)
     if fit.dtype != torch.float64 or tuple(fit.shape) != (ih, 4):
         raise ValueError('fit must be float64 [%d, 4]' % ih)
-    fit = fit.contiguous()
     n_cols = n if n_cols is None else int(n_cols)
+    shape = tuple(planes) + (ih, n_cols)
     if out is None:
         pitch = (n_cols + 63) // 64 * 64
-        out = torch.empty((ih, pitch), dtype=torch.float32, device=dev)[:, :n_cols]
+        out = torch.empty(shape[:-1] + (pitch,), dtype=torch.float32, device=dev)[..., :n_cols]
         if n_cols != n or int(k_offset) != 0:
             out.fill_(float('nan'))
-    if tuple(out.shape) != (ih, n_cols) or out.dtype != torch.float32 or out.stride(1) != 1:
-        raise ValueError('out must be a float32 [%d, %d] view with unit column stride' % (ih, n_cols))
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or out.stride(-1) != 1:
+        raise ValueError('out must be a float32 [%s] view with unit column stride' % ', '.join(str(d) for d in shape))
+    return n, h, w, bpp, fit.contiguous(), n_cols, out
+
+
+def _finish_setup(out_w, circle, crop):
+    """What doppler_finish and line_profile_finish share -> (nw: the output width after crop_plan's crop, circle as a host float64
+    [3] array, crop as a host int64 [4] array; None where not given).  The caller keeps the arrays alive across the C call."""
+    nw = int(out_w) if crop is None else int(crop[0])
+    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    c4 = None if crop is None else np.ascontiguousarray([int(v) for v in crop], dtype=np.int64)
+    return nw, c3, c4
+
+
+def _host_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def line_core_shift(stack, fit, half_width, flip_x=False, n_cols=None, k_offset=0, out=None):
+    """shg_line_core_shift: the line-core shift (pixels, float32) of every slit row and frame -> map [ih, n_cols] (a view of a
+    row-pitched buffer; columns of frames this call does not hold stay NaN).  fit float64 [ih, 4] (host array or GPU tensor)."""
+    n, h, w, bpp, fit, n_cols, out = _line_map_setup(stack, fit, n_cols, k_offset, out)
     _lib.check(lib.shg_line_core_shift(stack.data_ptr(), n, h, w, bpp, frame_stride(stack), fit.data_ptr(), int(half_width),
                                        int(bool(flip_x)), out.data_ptr(), out.stride(0), n_cols, int(k_offset), _stream()),
                'shg_line_core_shift')
@@ -811,42 +834,20 @@ def doppler_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None, dis
     (nw, lo, dx0, n), None: none) with NaN -> (map float32 [out_h, nw], png uint16 [out_h, nw] or None).  display_range R: also the
     16-bit display plane, 0 for NaN, clip(rint(32768 + d * 32767 / R), 1, 65535) elsewhere."""
     ptr, h, w, pitch = _img(raw, 'raw', torch.float32)
-    dev = raw.device
-    nw = int(out_w) if crop is None else int(crop[0])
-    out = torch.empty((int(out_h), nw), dtype=torch.float32, device=dev)
-    png = None if display_range is None else torch.empty((int(out_h), nw), dtype=torch.uint16, device=dev)
-    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
-    c4 = None if crop is None else np.ascontiguousarray([int(v) for v in crop], dtype=np.int64)
-    _lib.check(lib.shg_doppler_finish(ptr, h, w, pitch, float(h00), float(h01), float(h02), int(out_h), int(out_w),
-                                      None if c3 is None else c3.ctypes.data, None if c4 is None else c4.ctypes.data,
-                                      out.data_ptr(), out.stride(0), None if png is None else png.data_ptr(), nw,
+    nw, c3, c4 = _finish_setup(out_w, circle, crop)
+    out = torch.empty((int(out_h), nw), dtype=torch.float32, device=raw.device)
+    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=raw.device)
+    _lib.check(lib.shg_doppler_finish(ptr, h, w, pitch, float(h00), float(h01), float(h02), int(out_h), int(out_w), _host_ptr(c3),
+                                      _host_ptr(c4), out.data_ptr(), out.stride(0), None if png is None else png.data_ptr(), nw,
                                       0.0 if display_range is None else float(display_range), _stream()), 'shg_doppler_finish')
     return out, png
-
-
-# ---- line-profile maps ----------------------------------------------------------------------------
-LINE_PROFILE_PLANES = ('shift', 'core', 'width', 'cog', 'ew')
 
 
 def line_profile(stack, fit, half_width, shift=0, flip_x=False, n_cols=None, k_offset=0, out=None):
     """shg_line_profile: the five planes (LINE_PROFILE_PLANES, float32) of every slit row and frame, measured around the line
     shifted by `shift` pixels -> planes [5, ih, n_cols] (a view of a row-pitched buffer; columns of frames this call does not hold
     stay NaN).  fit float64 [ih, 4] (host array or GPU tensor)."""
-    n, h, w, bpp = stack_geometry(stack)
-    dev = stack.device
-    ih = max(h, w)
-    fit = torch.as_tensor(np.ascontiguousarray(fit, dtype=np.float64) if not isinstance(fit, torch.Tensor) else fit).to(dev)
-    if fit.dtype != torch.float64 or tuple(fit.shape) != (ih, 4):
-        raise ValueError('fit must be float64 [%d, 4]' % ih)
-    fit = fit.contiguous()
-    n_cols = n if n_cols is None else int(n_cols)
-    if out is None:
-        pitch = (n_cols + 63) // 64 * 64
-        out = torch.empty((len(LINE_PROFILE_PLANES), ih, pitch), dtype=torch.float32, device=dev)[:, :, :n_cols]
-        if n_cols != n or int(k_offset) != 0:
-            out.fill_(float('nan'))
-    if tuple(out.shape) != (len(LINE_PROFILE_PLANES), ih, n_cols) or out.dtype != torch.float32 or out.stride(2) != 1:
-        raise ValueError('out must be a float32 [5, %d, %d] view with unit column stride' % (ih, n_cols))
+    n, h, w, bpp, fit, n_cols, out = _line_map_setup(stack, fit, n_cols, k_offset, out, (len(LINE_PROFILE_PLANES),))
     _lib.check(lib.shg_line_profile(stack.data_ptr(), n, h, w, bpp, frame_stride(stack), fit.data_ptr(), int(half_width), int(shift),
                                     int(bool(flip_x)), out.data_ptr(), out.stride(0), out.stride(1), n_cols, int(k_offset), _stream()),
                'shg_line_profile')
@@ -864,16 +865,12 @@ def line_profile_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None
     if (half_width is None) != (display_range is None):
         raise ValueError('the display planes need both half_width and display_range')
     _, h, w = raw.shape
-    dev = raw.device
-    nw = int(out_w) if crop is None else int(crop[0])
-    out = torch.empty((len(LINE_PROFILE_PLANES), int(out_h), nw), dtype=torch.float32, device=dev)
-    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=dev)
-    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
-    c4 = None if crop is None else np.ascontiguousarray([int(v) for v in crop], dtype=np.int64)
+    nw, c3, c4 = _finish_setup(out_w, circle, crop)
+    out = torch.empty((len(LINE_PROFILE_PLANES), int(out_h), nw), dtype=torch.float32, device=raw.device)
+    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=raw.device)
     _lib.check(lib.shg_line_profile_finish(raw.data_ptr(), raw.stride(0), h, w, raw.stride(1), float(h00), float(h01), float(h02),
-                                           int(out_h), int(out_w), None if c3 is None else c3.ctypes.data,
-                                           None if c4 is None else c4.ctypes.data, out.data_ptr(), out.stride(0), out.stride(1),
-                                           None if png is None else png.data_ptr(), out.stride(0), out.stride(1),
+                                           int(out_h), int(out_w), _host_ptr(c3), _host_ptr(c4), out.data_ptr(), out.stride(0),
+                                           out.stride(1), None if png is None else png.data_ptr(), out.stride(0), out.stride(1),
                                            0 if half_width is None else int(half_width),
                                            0.0 if display_range is None else float(display_range), _stream()), 'shg_line_profile_finish')
     return out, png

@@ -1,6 +1,7 @@
 """Time the line-profile kernels on HBM-resident synthetic stacks next to the Dopplergram's: shg_line_profile and
 shg_line_core_shift at C2 (2000 x 2000x200, 16-bit), C2 8-bit and C5's frame shape (4000 x 2560x256) at H = 5 and H = 12, and
-shg_line_profile_finish on the C2 planes (limb circle, square crop, display planes).  HIP events bracket each call (run it under
+shg_doppler_finish on the C2 map at H = 5 and shg_line_profile_finish on the C2 planes at H = 12 (limb circle, square crop, display
+planes).  HIP events bracket each call (run it under
 rocprofv3 --kernel-trace --stats for the kernels alone).  Algorithmic bytes: n x ih x (band rows) x B read once, band = [min lo,
 max hi] of the whole scan, plus n x ih x 4 per plane written (20 B for the profile, 4 B for the line core)."""
 import os
@@ -47,29 +48,34 @@ def case(n, w, h, bits, half_width):
           '(%.1f MB, %.2f of 8 TB/s) = %.2fx; widths valid %.3f'
           % (n, w, h, bits, half_width, band, t_core * 1e6, a_core / 1e6, a_core / t_core / PEAK, t_prof * 1e6, best * 1e6, a_prof / 1e6,
              a_prof / t_prof / PEAK, t_prof / t_core, float(torch.isfinite(planes[2]).float().mean())))
-    return planes
+    return core, planes
 
 
-def finish(raw, half_width):
+def finish(raw, half_width=None):
+    """shg_doppler_finish on a map [h, w], or shg_line_profile_finish on planes [5, h, w] with half_width."""
     from solex_ser_recon_en_amd import SHG_MAIN
     from solex_ser_recon_en_amd.ellipse_to_circle import _warp_geometry
     from solex_ser_recon_en_amd.Solex_recon import crop_plan
-    _, h, w = raw.shape
+    planes = 1 if raw.dim() == 2 else raw.shape[0]
+    h, w = raw.shape[-2:]
     _, _, mat3, out_h, out_w, _, _ = _warp_geometry(0.05, 1.1, h, w)
     circle = (out_w / 2.0, out_h / 2.0, 0.42 * out_h)
     crop, _ = crop_plan(out_h, out_w, circle, dict(SHG_MAIN.default_options(), crop_width_square=True))
-    args = (raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, circle, crop, half_width, 2.0)
-    ops.line_profile_finish(*args)
-    med, best = timeit(lambda: ops.line_profile_finish(*args))
+    args = (raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, circle, crop) + ((2.0,) if planes == 1 else (half_width, 2.0))
+    fn = ops.doppler_finish if planes == 1 else ops.line_profile_finish
+    fn(*args)
+    med, best = timeit(lambda: fn(*args))
     nw = crop[0]
-    alg = 5 * (out_h * nw * (4 + 2) + h * w * 4)
-    print('line_profile_finish 5 x %dx%d -> %dx%d (circle, square crop, display planes): %.1f us median %.1f best; algorithmic %.1f MB '
-          '-> %.2f TB/s (includes the output allocations)' % (h, w, out_h, nw, med * 1e6, best * 1e6, alg / 1e6, alg / med / 1e12))
+    alg = planes * (out_h * nw * (4 + 2) + h * w * 4)         # maps + display planes written, the raw planes read once
+    print('%s %d x %dx%d -> %dx%d (circle, square crop, display planes): %.1f us median %.1f best; algorithmic %.1f MB -> %.2f TB/s '
+          '(includes the output allocations)' % (fn.__name__, planes, h, w, out_h, nw, med * 1e6, best * 1e6, alg / 1e6, alg / med / 1e12))
 
 
 if __name__ == '__main__':
     for hw in (5, 12):
-        raw = case(2000, 2000, 200, 16, hw)
+        core, planes = case(2000, 2000, 200, 16, hw)
         case(2000, 2000, 200, 8, hw)
         case(4000, 2560, 256, 16, hw)
-    finish(raw, 12)
+        if hw == 5:
+            finish(core)
+    finish(planes, 12)
