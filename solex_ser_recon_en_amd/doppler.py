@@ -47,6 +47,16 @@ def _geometry(rdr, fit, opts):
     return (-1, -1, -1), float(ratio), float(phi)
 
 
+def finish_circle(circle, crop, circle_out):
+    """The circle the finish masks with, in the corrected image's columns: the products' circle (crop_plan's circle_out) taken back
+    through the crop.  crop_plan centres the crop on int(cx) and moves the circle to the crop's middle column nw // 2, dropping the
+    fraction of cx; masking with `circle` itself would put the map's disk that fraction of a pixel off the products' disk."""
+    if crop is None or tuple(circle) == (-1, -1, -1):
+        return circle
+    nw, lo, dx0, n = crop
+    return (float(circle_out[0] - dx0 + lo), circle[1], circle[2])
+
+
 def velocity_factor(dispersion, wavelength):
     """km/s per pixel of shift: (dispersion / wavelength) * c."""
     return (float(dispersion) / float(wavelength)) * C_KM_S
@@ -84,7 +94,7 @@ def _line_maps(file_or_reader, options, half_width, display_range, dispersion, w
     circle, ratio, phi = _geometry(rdr, fit, opts)
     _, _, mat3, out_h, out_w, _, _ = _warp_geometry(phi, ratio, ih, n)
     crop, circle_out = crop_plan(out_h, out_w, circle, opts)
-    maps, png = finish(raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, circle, crop)
+    maps, png = finish(raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, finish_circle(circle, crop, circle_out), crop)
     common = {'circle': circle, 'circle_out': circle_out, 'ratio': ratio, 'phi': phi, 'crop': crop, 'fit': fit, 'half_width': half_width,
               'display_range': float(display_range), 'dispersion': dispersion, 'wavelength': wavelength}
     factor = None if dispersion is None else velocity_factor(dispersion, wavelength)
