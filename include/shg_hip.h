@@ -215,6 +215,32 @@ int shg_line_profile_finish(const float* raw, int64_t raw_plane_stride, int64_t 
                             float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
                             int64_t png_pitch, int half_width, double display_range, shg_stream_t stream);
 
+/* ---- line-bisector maps (not a reference stage; tests/bisector_ref.py restates both calls in NumPy, bit for bit)
+ * shg_line_bisector: the line's bisector and chord at K = n_levels depths of every (slit row y, frame k), in shg_line_profile's layout,
+ * with its p(j), window [lo, hi] (and SHG_E_ARG for S), ref = fit[y][3] + (double)S, j*, a, b, e, den, core_d and C2.  levels: a host
+ * array of K fractions f_i, 1 <= K <= 8, finite, strictly increasing, 0 < f_1 and f_K < 1 (else SHG_E_ARG, nothing written);
+ * f = 0 is the core, f = 1 the continuum C2 / 2.  For each level, one IEEE operation a step:
+ *   level = ((1.0 - f) * core_d) + (f * (0.5 * (double)C2))
+ * (at f = 0.5 this is shg_line_profile's half bit for bit: each half-scaling is exact), and shg_line_profile's width rule with half
+ * replaced by level: NaN unless lo < j* < hi and p(j*) < level; jl = the largest j in [lo, j*) with p(j) >= level, jr = the smallest
+ * j in (j*, hi] with p(j) >= level (for integer p: p >= ceil(level)); xl, xr interpolated as the width's; NaN when jl or jr does not
+ * exist.  bis_i = (float)((0.5 * (xl + xr)) - ref), chord_i = (float)(xr - xl) (= shg_line_profile's width at f = 0.5, bit for bit).
+ * planes[q * plane_stride + y * row_pitch + col(k)], q = i for bis_i and K + i for chord_i; col(k) as shg_line_core_shift.  Each
+ * level's values depend on that level alone, not on the other levels requested.  Limits and the other codes as shg_line_profile. */
+int shg_line_bisector(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px, int64_t frame_stride_px,
+                      const double* fit, int half_width, int shift, const double* levels, int n_levels, int flip_x, float* planes,
+                      int64_t plane_stride, int64_t row_pitch, int64_t n_cols, int64_t k_offset, shg_stream_t stream);
+
+/* shg_line_bisector_finish: the 2K raw planes raw[q][h][w] of shg_line_bisector (K = n_levels, 1 <= K <= 8, else SHG_E_ARG) in the
+ * products' geometry, each plane bit-identical to shg_doppler_finish with png = NULL: maps[q * map_plane_stride + r * map_pitch + c].
+ * png (may be NULL): 0 where v is NaN, else clip(rint(e), 1, 65535) with e = 32768 + (double)v * (32767 / display_range) for the
+ * bisector planes (q < K) and 1 + (double)v * (65534 / (2 H + 1)) for the chords (H = half_width, 1 <= H <= 32).  Argument checks and
+ * SHG_E_UNSUPPORTED limits as shg_line_profile_finish's. */
+int shg_line_bisector_finish(const float* raw, int64_t raw_plane_stride, int n_levels, int64_t h, int64_t w, int64_t raw_pitch,
+                             double h00, double h01, double h02, int64_t out_h, int64_t out_w, const double* circle3, const int64_t* crop4,
+                             float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
+                             int64_t png_pitch, int half_width, double display_range, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -22,8 +22,18 @@
 // the same L2.  No atomics.
 // k_line_core_plain, k_line_profile_plain (un-rotated files): a wave is one slit row of 64 frames, the window wave-uniform, each lane
 // walks its window (twice for the profile), the stores coalesced.
-// k_map_finish<1> (the Dopplergram's), k_map_finish<5> (the profile's): the ellipse -> circle resample of k_warp_rows with NaN for taps
-// outside, the limb mask, the crop / pad of crop_plan, and the 16-bit display planes; one thread per output pixel, all planes of it.
+// k_line_bisector_rot (shg_line_bisector, K <= 8 levels): the profile's shape, walk 1 carrying only the vertex state and C2.  Walk 2
+// for K levels at once would hold 8 rows x K levels x (jl, jr, two packed sample pairs, the level's threshold) = 40 K registers, and
+// an output tile [2K][8][512] floats is 256 KiB at K = 8.  So the levels go in passes of kLevelsPerPass = 2: each pass walks the band
+// again (served on-die, as the profile's walk 2) for two levels, with 8 rows x 2 levels x 5 = 80 registers of crossing state (the
+// sample pairs packed as the profile's, the crossings interpolated once, after the walk), and leaves through a [4][8][512] tile
+// (64 KiB).  A level's decisions stay its own: its planes do not depend on the other levels requested.  The kernel keeps 252 VGPRs
+// without spills (two waves per SIMD, one workgroup per CU, as the profile's 190); four waves per SIMD would spill about 400
+// registers, and passes of four levels would not fit 256.  k_line_bisector_plain: the profile's plain kernel, one walk of the
+// lane's window per level.
+// k_map_finish<1> (the Dopplergram's), k_map_finish<5> (the profile's), k_map_finish<2K, K> (the bisectors'): the ellipse -> circle
+// resample of k_warp_rows with NaN for taps outside, the limb mask, the crop / pad of crop_plan, and the 16-bit display planes; one
+// thread per output pixel, all planes of it.
 #include "shg_common.h"
 
 #include <limits.h>
@@ -39,6 +49,8 @@ constexpr int kWaves = 8;
 constexpr int kTileFrames = 16;                // frames of a workgroup: two a wave
 constexpr int kPhases = kTileFrames / kWaves;  // the profile's: one frame a wave at a time
 constexpr int kInFlight = 8;                   // raw rows a lane has loads in flight for
+constexpr int kMaxLevels = 8;                  // bisector levels of one call
+constexpr int kLevelsPerPass = 2;              // bisector levels of one walk 2 (see the top of the file)
 
 struct LineCoreArgs {
     const void* stack;
@@ -60,6 +72,19 @@ struct ProfileArgs {
     float* planes;
     int64_t plane_stride, pitch, n_cols, k_offset;
     int flip_x;
+};
+
+struct BisectorArgs {
+    const void* stack;
+    int n;
+    int64_t height, width, fstride;            // file layout
+    const double* fit;                         // [ih][4]
+    int hw, shift;
+    float* planes;
+    int64_t plane_stride, pitch, n_cols, k_offset;
+    int flip_x;
+    int nl;                                    // K: planes 0 .. K-1 bisectors, K .. 2K-1 chords
+    double f[kMaxLevels];                      // the levels' fractions
 };
 
 // Window of a slit row around fit[y][0] + S: lo > hi when the row has none (then its shift, and every plane, is NaN).
@@ -425,6 +450,191 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_profile_plain(const Profil
     out[4 * a.plane_stride] = v.ew;
 }
 
+// ---- line bisectors (shg_line_bisector) ----
+// Walk 1 of the bisectors: the vertex state and C2 = p(lo) + p(hi).
+struct Walk1B {
+    Core c;
+    int c2;
+};
+
+__device__ __forceinline__ void walk1b_step(Walk1B& s, int j, int p, int lo, int hi) {
+    core_step(s.c, j, p, lo, hi, [&] {
+        if (j == lo || j == hi) s.c2 += p;
+    });
+}
+
+// core_d of a row with a vertex (lo < j* < hi), as vertex_of computes it.
+__device__ __forceinline__ double core_d_of(const Core& c) {
+    const int den = c.a + c.e - 2 * c.best;
+    const int64_t d = c.a - c.e;
+    return (double)c.best - (double)(d * d) / (8.0 * (double)den);
+}
+
+// level = ((1 - f) core_d) + (f (0.5 C2)), one IEEE operation a step (f = 0.5: the profile's half, bit for bit).
+__device__ __forceinline__ double level_of(double f, double core_d, int c2) { return ((1.0 - f) * core_d) + (f * (0.5 * (double)c2)); }
+
+// The crossing threshold ceil(level) of a row with a vertex, INT_MAX when p(j*) >= level (|level| < 2^30: core_d > -2^30, C2 < 2^17).
+__device__ __forceinline__ int thr_of(double level, int best) { return (double)best < level ? (int)ceil(level) : INT_MAX; }
+
+// The crossings of walk 2's state at `level` (width_of's xl and xr); false when the row has no crossing pair.
+__device__ __forceinline__ bool crossings(int jl, int jr, uint32_t l, uint32_t r, double level, int thr, double& xl, double& xr) {
+    if (thr == INT_MAX || jl < 0 || jr < 0) return false;
+    const int pl = (int)(l & 0xffffu), pl1 = (int)(l >> 16), pr = (int)(r & 0xffffu), pr1 = (int)(r >> 16);
+    xl = (double)jl + ((double)pl - level) / (double)(pl - pl1);
+    xr = (double)jr - ((double)pr - level) / (double)(pr - pr1);
+    return true;
+}
+
+__device__ __forceinline__ void bisector_of(int jl, int jr, uint32_t l, uint32_t r, double level, int thr, double ref, float& bis,
+                                            float& chord) {
+    double xl, xr;
+    bis = chord = __builtin_nanf("");
+    if (!crossings(jl, jr, l, r, level, thr, xl, xr)) return;
+    bis = (float)((0.5 * (xl + xr)) - ref);
+    chord = (float)(xr - xl);
+}
+
+// Walk 2's crossing state of one (row, level): walk2_step's, the previous sample shared by a row's levels.
+struct Cross {
+    int jl, jr;
+    uint32_t l, r;
+};
+
+__device__ __forceinline__ void cross_step(Cross& s, int j, int p, int prev, int lo, int hi, int jb, int thr) {
+    if (j > lo && j <= jb && prev >= thr) {
+        s.jl = j - 1;
+        s.l = (uint32_t)prev | ((uint32_t)p << 16);      // p(jl), p(jl + 1)
+    }
+    if (j > jb && j <= hi && s.jr < 0 && p >= thr) {
+        s.jr = j;
+        s.r = (uint32_t)p | ((uint32_t)prev << 16);      // p(jr), p(jr - 1)
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(64 * kWaves) void k_line_bisector_rot(const BisectorArgs a) {
+    constexpr int L = kLevelsPerPass;
+    __shared__ float tile[2 * L * kWaves * kTileRows];              // 64 KiB: two workgroups per CU
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const Band b = band_of<T>(a, a.shift);
+    const int passes = (a.nl + L - 1) / L;
+    for (int ph = 0; ph < kPhases; ++ph) {
+        const int64_t kb = (int64_t)blockIdx.y * kTileFrames + ph * kWaves;
+        const int64_t k = kb + wave;
+        const char* frame = static_cast<const char*>(a.stack) + k * a.fstride * (int64_t)sizeof(T);
+        double core[kRowsPerLane];
+        int c2[kRowsPerLane], best[kRowsPerLane], jb[kRowsPerLane];
+        if (k < a.n) {
+            Walk1B s[kRowsPerLane];
+#pragma unroll
+            for (int r = 0; r < kRowsPerLane; ++r) {
+                core_init(s[r].c);
+                s[r].c2 = 0;
+            }
+            walk_band<T, VEC>(frame, b, [&](int j, int r, int p) { walk1b_step(s[r], j, p, b.lo[r], b.hi[r]); });
+#pragma unroll
+            for (int r = 0; r < kRowsPerLane; ++r) {
+                const bool vertex = s[r].c.jb > b.lo[r] && s[r].c.jb < b.hi[r];     // (false without a window: lo > hi)
+                core[r] = vertex ? core_d_of(s[r].c) : 0.0;
+                c2[r] = s[r].c2;
+                best[r] = s[r].c.best;
+                jb[r] = vertex ? s[r].c.jb : -1;
+            }
+        }
+        for (int ps = 0; ps < passes; ++ps) {
+            const int l0 = ps * L, nl = min(L, a.nl - l0);
+            if (k < a.n) {
+                Cross t[kRowsPerLane][L];
+                int thr[kRowsPerLane][L], prev[kRowsPerLane];
+#pragma unroll
+                for (int r = 0; r < kRowsPerLane; ++r) {
+                    prev[r] = 0;
+#pragma unroll
+                    for (int l = 0; l < L; ++l) {
+                        thr[r][l] = jb[r] >= 0 && l < nl ? thr_of(level_of(a.f[l0 + l], core[r], c2[r]), best[r]) : INT_MAX;
+                        t[r][l].jl = t[r][l].jr = -1;
+                        t[r][l].l = t[r][l].r = 0;
+                    }
+                }
+                walk_band<T, VEC>(frame, b, [&](int j, int r, int p) {
+#pragma unroll
+                    for (int l = 0; l < L; ++l)
+                        if (l < nl) cross_step(t[r][l], j, p, prev[r], b.lo[r], b.hi[r], jb[r], thr[r][l]);
+                    prev[r] = p;
+                });
+#pragma unroll
+                for (int h = 0; h < kRowsPerLane; h += 4) {
+#pragma unroll
+                    for (int l = 0; l < L; ++l) {
+                        float bis[4], chord[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int64_t x = b.x0 + h + r;
+                            const double ref = x < b.width ? a.fit[(b.width - 1 - x) * 4 + 3] + (double)a.shift : 0.0;
+                            const Cross& c = t[h + r][l];
+                            bisector_of(c.jl, c.jr, c.l, c.r, l < nl ? level_of(a.f[l0 + l], core[h + r], c2[h + r]) : 0.0,
+                                        thr[h + r][l], ref, bis[r], chord[r]);
+                        }
+                        const int row = lane * kRowsPerLane + h;
+                        *reinterpret_cast<float4*>(&tile[tile_at(l, wave, row)]) = make_float4(bis[0], bis[1], bis[2], bis[3]);
+                        *reinterpret_cast<float4*>(&tile[tile_at(L + l, wave, row)]) =
+                            make_float4(chord[0], chord[1], chord[2], chord[3]);
+                    }
+                }
+            }
+            __syncthreads();
+            // 8 threads write 8 consecutive columns of one map row of one plane: tile plane qt < L is level l0 + qt's bisector, L + i
+            // its chord
+            for (int idx = threadIdx.x; idx < 2 * L * kTileRows * kWaves; idx += 64 * kWaves) {
+                const int qt = idx / (kTileRows * kWaves), rl = (idx / kWaves) % kTileRows, f = idx % kWaves;
+                const int li = qt % L;
+                const int64_t x = (int64_t)blockIdx.x * kTileRows + rl, kf = kb + f;
+                if (li < nl && x < b.width && kf < a.n) {
+                    const int64_t q = (qt < L ? 0 : a.nl) + l0 + li;
+                    const int64_t c = a.k_offset + kf;
+                    a.planes[q * a.plane_stride + (b.width - 1 - x) * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c)] = tile[tile_at(qt, f, rl)];
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * kWaves) void k_line_bisector_plain(const BisectorArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t y = (int64_t)blockIdx.y * kWaves + (threadIdx.x >> 6);
+    const int64_t k = (int64_t)blockIdx.x * 64 + lane;
+    const int64_t ih = a.height;
+    if (y >= ih || k >= a.n) return;
+    constexpr int scale = sizeof(T) == 1 ? 256 : 1;
+    int lo, hi;
+    window_of(a.fit[y * 4], a.shift, a.hw, (int)a.width, lo, hi);
+    const T* row = static_cast<const T*>(a.stack) + k * a.fstride + y * a.width;
+    Walk1B s;
+    core_init(s.c);
+    s.c2 = 0;
+    for (int j = lo; j <= hi; ++j) walk1b_step(s, j, (int)row[j] * scale, lo, hi);
+    const bool vertex = s.c.jb > lo && s.c.jb < hi;
+    const double core = vertex ? core_d_of(s.c) : 0.0;
+    const double ref = a.fit[y * 4 + 3] + (double)a.shift;
+    const int64_t c = a.k_offset + k;
+    float* out = a.planes + y * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c);
+    for (int i = 0; i < a.nl; ++i) {
+        const double level = level_of(a.f[i], core, s.c2);
+        const int thr = vertex ? thr_of(level, s.c.best) : INT_MAX;
+        Walk2 t;
+        walk2_init(t);
+        if (thr != INT_MAX)
+            for (int j = lo; j <= hi; ++j) walk2_step(t, j, (int)row[j] * scale, lo, hi, s.c.jb, thr);
+        float bis, chord;
+        bisector_of(t.jl, t.jr, t.l, t.r, level, thr, ref, bis, chord);
+        out[i * a.plane_stride] = bis;
+        out[(a.nl + i) * a.plane_stride] = chord;
+    }
+}
+
 struct FinishArgs {
     const float* raw;
     int64_t raw_plane, h, w, raw_pitch;
@@ -440,9 +650,10 @@ struct FinishArgs {
     double shift_scale, width_scale;           // 32767 / R, 65534 / (2H + 1)
 };
 
-// One thread per output pixel, its P planes: P = 1 for the Dopplergram's shift map, kPlanes for the profile's.  Display planes: shift
-// and cog around 32768, core as it is, width and ew from 1 up.
-template <int P>
+// One thread per output pixel, its P planes: P = 1 for the Dopplergram's shift map, kPlanes for the profile's, 2 KB for KB bisector
+// levels.  Display planes: shift and cog around 32768, core as it is, width and ew from 1 up; with KB > 0, planes q < KB (the
+// bisectors) around 32768 and the chords from 1 up.
+template <int P, int KB = 0>
 __global__ __launch_bounds__(256) void k_map_finish(const FinishArgs a) {
     const int64_t oc = (int64_t)blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
     if (oc >= a.nw) return;
@@ -476,9 +687,10 @@ __global__ __launch_bounds__(256) void k_map_finish(const FinishArgs a) {
         if (a.png) {
             uint16_t d = 0;
             if (!isnan(v)) {
-                const double e = q == 0 || q == 3 ? 32768.0 + (double)v * a.shift_scale
-                                 : q == 1         ? (double)v
-                                                  : 1.0 + (double)v * a.width_scale;
+                const double e = KB > 0 ? (q < KB ? 32768.0 + (double)v * a.shift_scale : 1.0 + (double)v * a.width_scale)
+                                 : q == 0 || q == 3 ? 32768.0 + (double)v * a.shift_scale
+                                 : q == 1           ? (double)v
+                                                    : 1.0 + (double)v * a.width_scale;
                 d = (uint16_t)fmin(fmax(rint(e), 1.0), 65535.0);
             }
             a.png[q * a.png_plane + r * a.png_pitch + oc] = d;
@@ -629,4 +841,64 @@ extern "C" int shg_line_profile_finish(const float* raw, int64_t raw_plane_strid
     SHG_PROF("line_profile_finish", st);
     return shg::launch(k_map_finish<kPlanes>, dim3((unsigned)((a.nw + 255) / 256), (unsigned)out_h), dim3(256), 0, st, a,
                        "k_map_finish<5>");
+}
+
+extern "C" int shg_line_bisector(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px,
+                                 int64_t frame_stride_px, const double* fit, int half_width, int shift, const double* levels, int n_levels,
+                                 int flip_x, float* planes, int64_t plane_stride, int64_t row_pitch, int64_t n_cols, int64_t k_offset,
+                                 shg_stream_t stream) {
+    if (const int e = check_map_args("shg_line_bisector", stack, fit, planes, n_frames, height, width, bytes_per_px, frame_stride_px,
+                                     half_width, row_pitch, n_cols, k_offset))
+        return e;
+    const int64_t ih = width > height ? width : height, iw = width > height ? height : width;
+    SHG_REQUIRE(plane_stride >= ih * row_pitch, SHG_E_ARG, "shg_line_bisector: plane stride < %lld x %lld", (long long)ih,
+                (long long)row_pitch);
+    SHG_REQUIRE(shift > 3 - iw - half_width && shift < iw - 3 + half_width, SHG_E_ARG,
+                "shg_line_bisector: shift %d puts every window outside columns [1, %lld]", shift, (long long)(iw - 2));
+    SHG_REQUIRE(levels && n_levels >= 1 && n_levels <= kMaxLevels, SHG_E_ARG, "shg_line_bisector: %d levels (1 to %d)", n_levels,
+                kMaxLevels);
+    for (int i = 0; i < n_levels; ++i)
+        SHG_REQUIRE(isfinite(levels[i]) && levels[i] > 0.0 && levels[i] < 1.0 && (i == 0 || levels[i] > levels[i - 1]), SHG_E_ARG,
+                    "shg_line_bisector: levels must be finite, strictly increasing and inside (0, 1) (level %d is %g)", i, levels[i]);
+    const int64_t fstride = frame_stride_px > 0 ? frame_stride_px : height * width;
+    BisectorArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, shift, planes, plane_stride, row_pitch, n_cols,
+                   k_offset, flip_x ? 1 : 0, n_levels, {}};
+    for (int i = 0; i < n_levels; ++i) a.f[i] = levels[i];
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("line_bisector", st);
+    return launch_map(
+        a, bytes_per_px, st, [](auto t, auto vec) { return k_line_bisector_rot<decltype(t), decltype(vec)::value>; },
+        [](auto t) { return k_line_bisector_plain<decltype(t)>; }, "k_line_bisector_rot", "k_line_bisector_plain");
+}
+
+namespace {
+template <int K>
+int launch_bisector_finish(int n_levels, const FinishArgs& a, hipStream_t st) {
+    if (n_levels != K) return launch_bisector_finish<K - 1>(n_levels, a, st);
+    return shg::launch(k_map_finish<2 * K, K>, dim3((unsigned)((a.nw + 255) / 256), (unsigned)a.out_h), dim3(256), 0, st, a,
+                       "k_map_finish<2K, K>");
+}
+
+template <>
+int launch_bisector_finish<0>(int, const FinishArgs&, hipStream_t) {
+    return SHG_E_ARG;
+}
+}  // namespace
+
+extern "C" int shg_line_bisector_finish(const float* raw, int64_t raw_plane_stride, int n_levels, int64_t h, int64_t w,
+                                        int64_t raw_pitch, double h00, double h01, double h02, int64_t out_h, int64_t out_w,
+                                        const double* circle3, const int64_t* crop4, float* maps, int64_t map_plane_stride,
+                                        int64_t map_pitch, uint16_t* png, int64_t png_plane_stride, int64_t png_pitch, int half_width,
+                                        double display_range, shg_stream_t stream) {
+    SHG_REQUIRE(n_levels >= 1 && n_levels <= kMaxLevels, SHG_E_ARG, "shg_line_bisector_finish: %d levels (1 to %d)", n_levels,
+                kMaxLevels);
+    FinishArgs a{raw, raw_plane_stride, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, maps,
+                 map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0};
+    if (const int e = finish_args("shg_line_bisector_finish", 2 * n_levels, circle3, crop4, display_range, a)) return e;
+    SHG_REQUIRE(!png || (half_width >= 1 && half_width <= kMaxHalfWidth), SHG_E_UNSUPPORTED,
+                "shg_line_bisector_finish: half-width %d outside [1, %d]", half_width, kMaxHalfWidth);
+    a.width_scale = png ? 65534.0 / (double)(2 * half_width + 1) : 0.0;
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("line_bisector_finish", st);
+    return launch_bisector_finish<kMaxLevels>(n_levels, a, st);
 }

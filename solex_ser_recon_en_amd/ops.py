@@ -874,3 +874,38 @@ def line_profile_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None
                                            0 if half_width is None else int(half_width),
                                            0.0 if display_range is None else float(display_range), _stream()), 'shg_line_profile_finish')
     return out, png
+
+
+def line_bisector(stack, fit, half_width, levels, shift=0, flip_x=False, n_cols=None, k_offset=0, out=None):
+    """shg_line_bisector: the bisector (pixels from fit[y, 3] + shift) and the chord (pixels) at each of K = len(levels) depths of
+    the line, for every slit row and frame, measured around the line shifted by `shift` pixels -> planes [2K, ih, n_cols], planes
+    0 .. K-1 the bisectors and K .. 2K-1 the chords (a view of a row-pitched buffer; columns of frames this call does not hold stay
+    NaN).  levels: fractions from the core (0) to the continuum (1), checked by the C call.  fit float64 [ih, 4]."""
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.float64).reshape(-1))
+    n, h, w, bpp, fit, n_cols, out = _line_map_setup(stack, fit, n_cols, k_offset, out, (2 * lv.size,))
+    _lib.check(lib.shg_line_bisector(stack.data_ptr(), n, h, w, bpp, frame_stride(stack), fit.data_ptr(), int(half_width), int(shift),
+                                     _host_ptr(lv) if lv.size else None, int(lv.size), int(bool(flip_x)), out.data_ptr(),
+                                     out.stride(0), out.stride(1), n_cols, int(k_offset), _stream()), 'shg_line_bisector')
+    return out
+
+
+def line_bisector_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None, half_width=None, display_range=None):
+    """shg_line_bisector_finish: the 2K raw planes float32 [2K, ih, N] of line_bisector through doppler_finish's geometry, all in one
+    launch -> (maps float32 [2K, out_h, nw], png uint16 [2K, out_h, nw] or None).  With half_width H and display_range R also the
+    display planes: 0 for NaN; the bisectors as the Dopplergram's shift, the chords clip(rint(1 + v * 65534 / (2H + 1)), 1, 65535)."""
+    _dev(raw, 'raw')
+    if raw.dim() != 3 or raw.shape[0] % 2 or raw.dtype != torch.float32 or raw.stride(2) != 1:
+        raise ValueError('raw must be a float32 [2K, h, w] view with unit column stride')
+    if (half_width is None) != (display_range is None):
+        raise ValueError('the display planes need both half_width and display_range')
+    planes, h, w = raw.shape
+    nw, c3, c4 = _finish_setup(out_w, circle, crop)
+    out = torch.empty((planes, int(out_h), nw), dtype=torch.float32, device=raw.device)
+    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=raw.device)
+    _lib.check(lib.shg_line_bisector_finish(raw.data_ptr(), raw.stride(0), planes // 2, h, w, raw.stride(1), float(h00), float(h01),
+                                            float(h02), int(out_h), int(out_w), _host_ptr(c3), _host_ptr(c4), out.data_ptr(),
+                                            out.stride(0), out.stride(1), None if png is None else png.data_ptr(), out.stride(0),
+                                            out.stride(1), 0 if half_width is None else int(half_width),
+                                            0.0 if display_range is None else float(display_range), _stream()),
+               'shg_line_bisector_finish')
+    return out, png
