@@ -18,13 +18,11 @@ interpolated as the width's; the bisector is their midpoint minus the mean image
 the Dopplergram's), the chord their distance (pixels; at f = 0.5 the line-profile maps' width).  Different depths of a line form at
 different heights, so the bisectors at several levels give the line-of-sight velocity against height and the line's asymmetry.
 """
-import json
 import math
-import os
 import sys
 
 from . import ops
-from .doppler import _cli, _cli_dispersion, _km_s, _line_maps, _parser, _write_pair, disk_stats
+from .linemaps import _by_plane, _cli, _cli_dispersion, _line_maps, _parser, _print_json, _write_planes
 
 DEFAULT_LEVELS = (0.2, 0.4, 0.6, 0.8)
 MAX_LEVELS = 8
@@ -62,88 +60,52 @@ def line_bisector_maps(file_or_reader, options=None, half_width=10, shift=0, lev
     dopplergram())."""
     levels = check_levels(levels)
     half_width, shift = int(half_width), int(shift)
-
-    def check_frame(iw):
-        if not 3 - iw - half_width < shift < iw - 3 + half_width:
-            raise ValueError('shift %d puts every window outside the frame (%d columns)' % (shift, iw))
-
     raw, maps, png, res, factor = _line_maps(
         file_or_reader, options, half_width, display_range, dispersion, wavelength,
         'the line-bisector maps of a frame-sharded scan are not supported',
         lambda stack, fit, flip: ops.line_bisector(stack, fit, half_width, levels, shift, flip_x=flip),
-        lambda raw, *geometry: ops.line_bisector_finish(raw, *geometry, half_width, display_range), check_frame)
+        lambda raw, *geometry: ops.line_bisector_finish(raw, *geometry, half_width, display_range), shift)
     keys = [('bisector', f) for f in levels] + [('chord', f) for f in levels]
-    units = {key: 'pixel' for key in keys}
-    out = {key: maps[q] for q, key in enumerate(keys)}
-    if factor is not None:
-        for f in levels:
-            out['bisector', f] = _km_s(out['bisector', f], factor)
-            units['bisector', f] = 'km/s'
-    res.update(raw={key: raw[q] for q, key in enumerate(keys)}, maps=out, png={key: png[q] for q, key in enumerate(keys)},
-               units=units, shift=shift, levels=levels)
-    return res
+    return _by_plane(res, keys, {key: 'pixel' for key in keys}, [('bisector', f) for f in levels], raw, maps, png, factor, shift=shift,
+                     levels=levels)
 
 
 # ---- command line ---------------------------------------------------------------------------------
 def _own_flags(p):
-    p.add_argument('--shift', type=int, help='pixel shift of the line to measure (the -w shift; default 0: the fitted line)')
-    p.add_argument('--line', type=float, help='A, the line to measure (with --atlas / --anchor: its shift from the analyser)')
     p.add_argument('--levels', default=','.join('%g' % f for f in DEFAULT_LEVELS),
                    help='comma-separated fractions from the core (0) to the continuum (1), 1 to 8, strictly increasing')
     p.add_argument('--widths', action='store_true', help='also write the chord (width) map of every level')
 
 
 def main(argv=None):
-    from . import spectral
     from .video_reader import video_reader
     p = _parser('python -m solex_ser_recon_en_amd.bisector',
                 '%(prog)s FILE [--half-width H] [--shift S | --line L] [--levels 0.2,0.4,0.6,0.8] [--widths] [--range R] '
                 '[--dispersion D --wavelength L | --atlas A --anchor L] [SHG_MAIN flags]',
                 'Line-bisector maps of a scan: the line shift at several depths of the line.', 10,
                 ('pixels either side of the line measured (1..32)', 'PNG display range of the bisector maps: +-R pixels to 1 .. 65535',
-                 'A / pixel (with --wavelength: the bisector maps in km/s)', 'A, the line measured'), _own_flags)
+                 'A / pixel (with --wavelength: the bisector maps in km/s)', 'A, the line measured'), True, _own_flags)
 
     def own_checks(args):
-        if args.shift is not None and args.line is not None:
-            p.error('--shift and --line exclude each other')
-        if args.line is not None and args.atlas is None:
-            p.error('--line needs --atlas and --anchor')
         try:
             args.levels = check_levels([v for v in args.levels.split(',')] if args.levels.strip() else [])
         except ValueError as e:
             p.error('--levels: %s' % e)
 
     args, opts, path, atlas = _cli(p, argv, 'the line-bisector maps are single-process: run them without torchrun',
-                                   '-w is not a line-bisector flag: give the line with --shift or --line', own_checks, ('line',))
+                                   '-w is not a line-bisector flag: give the line with --shift or --line', own_checks)
     try:
         rdr = video_reader(path)
-        dispersion, wavelength, a = _cli_dispersion(rdr, opts, args, atlas)
-        shift = args.shift or 0
-        if args.line is not None:
-            shift, _ = spectral.shift_for_wavelength(args.line, args.anchor, dispersion, a['fit'], int(rdr.iw))
-            wavelength = args.line
+        dispersion, wavelength, shift = _cli_dispersion(rdr, opts, args, atlas)
         res = line_bisector_maps(rdr, opts, args.half_width, shift, args.levels, args.range, dispersion, wavelength)
     except ValueError as e:
         print('error: %s' % e, file=sys.stderr)
         return 1
-    base = os.path.splitext(path)[0]
-    out = {'shape': None, 'shift': res['shift'], 'half_width': res['half_width'], 'display_range': res['display_range'],
-           'dispersion': dispersion, 'wavelength': wavelength, 'levels': list(res['levels']), 'fits': {}, 'png': {}, 'units': {},
-           'median': {}, 'valid_fraction': {}}
     kinds = ('bisector', 'chord') if args.widths else ('bisector',)
-    for f in res['levels']:
-        for kind in kinds:
-            name = 'bisector_%s' % level_tag(f) + ('_chord' if kind == 'chord' else '')
-            key = (kind, f)
-            fits_path, png_path, out['shape'] = _write_pair('%s_shift=%d_%s' % (base, res['shift'], name), opts, rdr, res['maps'][key],
-                                                            res['png'][key], res['units'][key], res['half_width'], dispersion,
-                                                            wavelength, LEVEL=float(f), SHIFT=res['shift'])
-            stats = disk_stats({'map': res['maps'][key], 'circle_out': res['circle_out']})
-            out['fits'][name], out['png'][name], out['units'][name] = fits_path, png_path, res['units'][key]
-            out['median'][name], out['valid_fraction'][name] = stats['median'], stats['valid_fraction']
-    out.update(circle=list(res['circle']), ratio=res['ratio'], phi=res['phi'], crop=None if res['crop'] is None else list(res['crop']))
-    print(json.dumps(out), flush=True)
-    return 0
+    names = [('bisector_%s' % level_tag(f) + ('_chord' if kind == 'chord' else ''), (kind, f)) for f in res['levels'] for kind in kinds]
+    out = _write_planes(path, opts, rdr, res, dispersion, wavelength, [(name, name, key, {'LEVEL': float(key[1])}) for name, key in names],
+                        levels=list(res['levels']))
+    return _print_json(out, res)
 
 
 if __name__ == '__main__':

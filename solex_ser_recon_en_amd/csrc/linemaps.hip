@@ -1,8 +1,11 @@
-// Line maps: where the line core sits (the Dopplergram, shg_line_core_shift) and five planes of the line's profile (shg_line_profile:
-// the core's position, its intensity, the line's width (FWHM), its centre of gravity and its equivalent width within the window) in
-// every (slit row, frame) of a scan, and those raw maps taken to the products' geometry (shg_doppler_finish, shg_line_profile_finish).
-// Not a reference stage: the arithmetic is the one include/shg_hip.h states and tests/doppler_ref.py / tests/lineprofile_ref.py
-// restate in NumPy, bit for bit.
+// Line maps: where the line core sits (the Dopplergram, shg_line_core_shift), five planes of the line's profile (shg_line_profile:
+// the core's position, its intensity, the line's width (FWHM), its centre of gravity and its equivalent width within the window) and
+// the line's bisector and chord at K levels (shg_line_bisector) in every (slit row, frame) of a scan, and those raw maps taken to the
+// products' geometry (shg_doppler_finish, shg_line_profile_finish, shg_line_bisector_finish).  Not a reference stage: the arithmetic
+// is the one include/shg_hip.h states and tests/doppler_ref.py / lineprofile_ref.py / bisector_ref.py restate in NumPy, bit for bit.
+// The three maps share one core: the window, walk 1 and the vertex (core_d_of, level_of, thr_of), one walk-2 crossing state and
+// interpolation (Cross, crossings: the profile's width is the chord at half), one argument struct (MapArgs), the band walk, the
+// write-out of an LDS phase tile (write_tile), the plain kernels' prologue (plain_row), one launch and one set of checks.
 //
 // Rotated files (the usual layout): the samples of one wavelength column are one contiguous raw row across the slit, so a lane owns
 // eight consecutive raw columns (eight slit rows), loads them as ONE 16-byte piece (8 bytes for 8-bit files) per raw row, and a
@@ -22,12 +25,12 @@
 // the same L2.  No atomics.
 // k_line_core_plain, k_line_profile_plain (un-rotated files): a wave is one slit row of 64 frames, the window wave-uniform, each lane
 // walks its window (twice for the profile), the stores coalesced.
-// k_line_bisector_rot (shg_line_bisector, K <= 8 levels): the profile's shape, walk 1 carrying only the vertex state and C2.  Walk 2
+// k_line_bisector_rot (shg_line_bisector, K <= 8 levels): the profile's shape and walk 1, of which it reads the vertex and C2.  Walk 2
 // for K levels at once would hold 8 rows x K levels x (jl, jr, two packed sample pairs, the level's threshold) = 40 K registers, and
 // an output tile [2K][8][512] floats is 256 KiB at K = 8.  So the levels go in passes of kLevelsPerPass = 2: each pass walks the band
 // again (served on-die, as the profile's walk 2) for two levels, with 8 rows x 2 levels x 5 = 80 registers of crossing state (the
 // sample pairs packed as the profile's, the crossings interpolated once, after the walk), and leaves through a [4][8][512] tile
-// (64 KiB).  A level's decisions stay its own: its planes do not depend on the other levels requested.  The kernel keeps 252 VGPRs
+// (64 KiB).  A level's decisions stay its own: its planes do not depend on the other levels requested.  The kernel keeps 252-255 VGPRs
 // without spills (two waves per SIMD, one workgroup per CU, as the profile's 190); four waves per SIMD would spill about 400
 // registers, and passes of four levels would not fit 256.  k_line_bisector_plain: the profile's plain kernel, one walk of the
 // lane's window per level.
@@ -52,18 +55,8 @@ constexpr int kInFlight = 8;                   // raw rows a lane has loads in f
 constexpr int kMaxLevels = 8;                  // bisector levels of one call
 constexpr int kLevelsPerPass = 2;              // bisector levels of one walk 2 (see the top of the file)
 
-struct LineCoreArgs {
-    const void* stack;
-    int n;
-    int64_t height, width, fstride;            // file layout
-    const double* fit;                         // [ih][4]
-    int hw;
-    float* map;
-    int64_t pitch, n_cols, k_offset;
-    int flip_x;
-};
-
-struct ProfileArgs {
+// The map kernels' one argument: the Dopplergram passes shift 0 and its one plane; nl and f are the bisectors' alone.
+struct MapArgs {
     const void* stack;
     int n;
     int64_t height, width, fstride;            // file layout
@@ -72,18 +65,7 @@ struct ProfileArgs {
     float* planes;
     int64_t plane_stride, pitch, n_cols, k_offset;
     int flip_x;
-};
-
-struct BisectorArgs {
-    const void* stack;
-    int n;
-    int64_t height, width, fstride;            // file layout
-    const double* fit;                         // [ih][4]
-    int hw, shift;
-    float* planes;
-    int64_t plane_stride, pitch, n_cols, k_offset;
-    int flip_x;
-    int nl;                                    // K: planes 0 .. K-1 bisectors, K .. 2K-1 chords
+    int nl;                                    // bisectors: K, planes 0 .. K-1 bisectors, K .. 2K-1 chords
     double f[kMaxLevels];                      // the levels' fractions
 };
 
@@ -133,7 +115,8 @@ __device__ __forceinline__ float core_shift(const Core& s, int lo, int hi, doubl
     return (float)(((double)s.jb + delta) - ref);
 }
 
-// Walk 1 of the profile: the line core's state, Σp, Σ(j - lo) p and p(lo) + p(hi).  Σ(j - lo) p <= 64 * 65 / 2 * 65535 < 2^31.
+// Walk 1: the line core's state, Σp, Σ(j - lo) p and p(lo) + p(hi).  Σ(j - lo) p <= 64 * 65 / 2 * 65535 < 2^31.  (The bisectors read
+// only the core's state and C2: the compiler drops the two sums there.)
 struct Walk1 {
     Core c;
     int sp, st, c2;
@@ -152,30 +135,18 @@ __device__ __forceinline__ void walk1_step(Walk1& s, int j, int p, int lo, int h
     });
 }
 
-// Walk 2 of one slit row: jl = the largest j in [lo, j*) with p(j) >= half, jr = the smallest j in (j*, hi] with p(j) >= half
-// (p(j) >= half <=> p(j) >= thr = ceil(half) for integer p; thr = INT_MAX when the row has no width).  The sample pairs either
-// side of a crossing are kept as p | p' << 16 (samples < 2^16).
-struct Walk2 {
-    int jl, jr, prev;
-    uint32_t l, r;
-};
-
-__device__ __forceinline__ void walk2_init(Walk2& s) {
-    s.jl = s.jr = -1;
-    s.l = s.r = s.prev = 0;
+// core_d of a row with a vertex (lo < j* < hi): the parabola's value at its vertex.  den > 0: a > b (first minimum), e >= b.
+__device__ __forceinline__ double core_d_of(const Core& c) {
+    const int den = c.a + c.e - 2 * c.best;
+    const int64_t d = c.a - c.e;
+    return (double)c.best - (double)(d * d) / (8.0 * (double)den);
 }
 
-__device__ __forceinline__ void walk2_step(Walk2& s, int j, int p, int lo, int hi, int jb, int thr) {
-    if (j > lo && j <= jb && s.prev >= thr) {
-        s.jl = j - 1;
-        s.l = (uint32_t)s.prev | ((uint32_t)p << 16);    // p(jl), p(jl + 1)
-    }
-    if (j > jb && j <= hi && s.jr < 0 && p >= thr) {
-        s.jr = j;
-        s.r = (uint32_t)p | ((uint32_t)s.prev << 16);    // p(jr), p(jr - 1)
-    }
-    s.prev = p;
-}
+// level = ((1 - f) core_d) + (f (0.5 C2)), one IEEE operation a step (f = 0.5: the profile's half, bit for bit).
+__device__ __forceinline__ double level_of(double f, double core_d, int c2) { return ((1.0 - f) * core_d) + (f * (0.5 * (double)c2)); }
+
+// The crossing threshold ceil(level) of a row with a vertex, INT_MAX when p(j*) >= level (|level| < 2^30: core_d > -2^30, C2 < 2^17).
+__device__ __forceinline__ int thr_of(double level, int best) { return (double)best < level ? (int)ceil(level) : INT_MAX; }
 
 // The planes walk 1 decides (shift, core, cog, ew), and the half level of the width: see include/shg_hip.h.
 struct Vertex {
@@ -196,21 +167,53 @@ __device__ __forceinline__ Vertex vertex_of(const Walk1& s, int lo, int hi, doub
     if (c2 != 0) v.ew = (float)((double)s0 / (double)c2);
     if (!(s.c.jb > lo && s.c.jb < hi)) return v;
     v.shift = core_shift(s.c, lo, hi, ref);
-    const int den = s.c.a + s.c.e - 2 * s.c.best;                        // > 0: a > b (first minimum), e >= b
-    const int64_t d = s.c.a - s.c.e;
-    const double core = (double)s.c.best - (double)(d * d) / (8.0 * (double)den);
+    const double core = core_d_of(s.c);
     v.core = (float)core;
-    v.half = 0.5 * (0.5 * (double)c2 + core);
-    if ((double)s.c.best < v.half) v.thr = (int)ceil(v.half);           // |half| < 2^17
+    v.half = level_of(0.5, core, s.c2);
+    v.thr = thr_of(v.half, s.c.best);
     return v;
 }
 
-__device__ __forceinline__ float width_of(const Walk2& s, double half, int thr) {
-    if (thr == INT_MAX || s.jl < 0 || s.jr < 0) return __builtin_nanf("");
+// Walk 2's crossing state of one (slit row, level): jl = the largest j in [lo, j*) with p(j) >= level, jr = the smallest j in
+// (j*, hi] with p(j) >= level (p(j) >= level <=> p(j) >= thr = ceil(level) for integer p; thr = INT_MAX when the row has no
+// crossings).  The sample pairs either side of a crossing are kept as p | p' << 16 (samples < 2^16).  The previous sample is the
+// caller's, kept beside the state (one for all of a row's levels).
+struct Cross {
+    int jl, jr;
+    uint32_t l, r;
+};
+
+__device__ __forceinline__ void cross_init(Cross& s) {
+    s.jl = s.jr = -1;
+    s.l = s.r = 0;
+}
+
+__device__ __forceinline__ void cross_step(Cross& s, int j, int p, int prev, int lo, int hi, int jb, int thr) {
+    if (j > lo && j <= jb && prev >= thr) {
+        s.jl = j - 1;
+        s.l = (uint32_t)prev | ((uint32_t)p << 16);      // p(jl), p(jl + 1)
+    }
+    if (j > jb && j <= hi && s.jr < 0 && p >= thr) {
+        s.jr = j;
+        s.r = (uint32_t)p | ((uint32_t)prev << 16);      // p(jr), p(jr - 1)
+    }
+}
+
+// The crossings xl, xr of walk 2's state at `level`, each interpolated linearly with its inner neighbour: bis = their midpoint
+// - ref and len = the chord xr - xl (at half: the profile's width); both NaN when the row has no crossing pair.
+struct Chord {
+    float bis, len;
+};
+
+__device__ __forceinline__ Chord crossings(const Cross& s, double level, int thr, double ref) {
+    Chord c{__builtin_nanf(""), __builtin_nanf("")};
+    if (thr == INT_MAX || s.jl < 0 || s.jr < 0) return c;
     const int pl = (int)(s.l & 0xffffu), pl1 = (int)(s.l >> 16), pr = (int)(s.r & 0xffffu), pr1 = (int)(s.r >> 16);
-    const double xl = (double)s.jl + ((double)pl - half) / (double)(pl - pl1);
-    const double xr = (double)s.jr - ((double)pr - half) / (double)(pr - pr1);
-    return (float)(xr - xl);
+    const double xl = (double)s.jl + ((double)pl - level) / (double)(pl - pl1);
+    const double xr = (double)s.jr - ((double)pr - level) / (double)(pr - pr1);
+    c.bis = (float)((0.5 * (xl + xr)) - ref);
+    c.len = (float)(xr - xl);
+    return c;
 }
 
 // eight samples of one raw row, as four dwords of u16 pairs (sample r in the (r & 1) half of dword r >> 1)
@@ -309,7 +312,7 @@ __device__ __forceinline__ void walk_band(const char* frame, const Band& b, Step
 }
 
 template <typename T, bool VEC>
-__global__ __launch_bounds__(64 * kWaves) void k_line_core_rot(const LineCoreArgs a) {
+__global__ __launch_bounds__(64 * kWaves) void k_line_core_rot(const MapArgs a) {
     __shared__ float tile[kTileRows][kTileFrames + 1];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -337,7 +340,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_core_rot(const LineCoreArg
         const int64_t x = (int64_t)blockIdx.x * kTileRows + rl, k = kb + f;
         if (x < b.width && k < a.n) {
             const int64_t c = a.k_offset + k;
-            a.map[(b.width - 1 - x) * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c)] = tile[rl][f];
+            a.planes[(b.width - 1 - x) * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c)] = tile[rl][f];
         }
     }
 }
@@ -346,8 +349,23 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_core_rot(const LineCoreArg
 // hits 32 banks and a lane's four consecutive rows stay one aligned float4.
 __device__ __forceinline__ int tile_at(int q, int f, int row) { return (q * kWaves + f) * kTileRows + (row ^ (f << 2)); }
 
+// A phase's Q-plane tile to the planes, from frame kb on: 8 threads write 8 consecutive columns of one map row of one plane.  Tile
+// plane qt goes to plane plane_of(qt), nowhere when that is < 0.
+template <int Q, typename PlaneOf>
+__device__ __forceinline__ void write_tile(const MapArgs& a, const float* tile, int64_t kb, PlaneOf&& plane_of) {
+    for (int idx = threadIdx.x; idx < Q * kTileRows * kWaves; idx += 64 * kWaves) {
+        const int qt = idx / (kTileRows * kWaves), rl = (idx / kWaves) % kTileRows, f = idx % kWaves;
+        const int64_t q = plane_of(qt);
+        const int64_t x = (int64_t)blockIdx.x * kTileRows + rl, kf = kb + f;
+        if (q >= 0 && x < a.width && kf < a.n) {
+            const int64_t c = a.k_offset + kf;
+            a.planes[q * a.plane_stride + (a.width - 1 - x) * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c)] = tile[tile_at(qt, f, rl)];
+        }
+    }
+}
+
 template <typename T, bool VEC>
-__global__ __launch_bounds__(64 * kWaves) void k_line_profile_rot(const ProfileArgs a) {
+__global__ __launch_bounds__(64 * kWaves) void k_line_profile_rot(const MapArgs a) {
     __shared__ float tile[kPlanes * kWaves * kTileRows];            // 80 KiB: two workgroups per CU
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -381,138 +399,94 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_profile_rot(const ProfileA
                 *reinterpret_cast<float4*>(&tile[tile_at(3, wave, row)]) = make_float4(v[0].cog, v[1].cog, v[2].cog, v[3].cog);
                 *reinterpret_cast<float4*>(&tile[tile_at(4, wave, row)]) = make_float4(v[0].ew, v[1].ew, v[2].ew, v[3].ew);
             }
-            Walk2 t[kRowsPerLane];
+            Cross t[kRowsPerLane];
+            int prev[kRowsPerLane];
 #pragma unroll
-            for (int r = 0; r < kRowsPerLane; ++r) walk2_init(t[r]);
-            walk_band<T, VEC>(frame, b, [&](int j, int r, int p) { walk2_step(t[r], j, p, b.lo[r], b.hi[r], jb[r], thr[r]); });
+            for (int r = 0; r < kRowsPerLane; ++r) {
+                cross_init(t[r]);
+                prev[r] = 0;
+            }
+            walk_band<T, VEC>(frame, b, [&](int j, int r, int p) {
+                cross_step(t[r], j, p, prev[r], b.lo[r], b.hi[r], jb[r], thr[r]);
+                prev[r] = p;
+            });
 #pragma unroll
             for (int h = 0; h < kRowsPerLane; h += 4)
                 *reinterpret_cast<float4*>(&tile[tile_at(2, wave, lane * kRowsPerLane + h)]) =
-                    make_float4(width_of(t[h], half[h], thr[h]), width_of(t[h + 1], half[h + 1], thr[h + 1]),
-                                width_of(t[h + 2], half[h + 2], thr[h + 2]), width_of(t[h + 3], half[h + 3], thr[h + 3]));
+                    make_float4(crossings(t[h], half[h], thr[h], 0.0).len, crossings(t[h + 1], half[h + 1], thr[h + 1], 0.0).len,
+                                crossings(t[h + 2], half[h + 2], thr[h + 2], 0.0).len, crossings(t[h + 3], half[h + 3], thr[h + 3], 0.0).len);
         }
         __syncthreads();
-        // 8 threads write 8 consecutive columns of one map row of one plane
-        for (int idx = threadIdx.x; idx < kPlanes * kTileRows * kWaves; idx += 64 * kWaves) {
-            const int q = idx / (kTileRows * kWaves), rl = (idx / kWaves) % kTileRows, f = idx % kWaves;
-            const int64_t x = (int64_t)blockIdx.x * kTileRows + rl, kf = kb + f;
-            if (x < b.width && kf < a.n) {
-                const int64_t c = a.k_offset + kf;
-                a.planes[q * a.plane_stride + (b.width - 1 - x) * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c)] = tile[tile_at(q, f, rl)];
-            }
-        }
+        write_tile<kPlanes>(a, tile, kb, [](int qt) { return (int64_t)qt; });
         __syncthreads();
     }
 }
 
+// A plain kernel's thread (a wave: one slit row y of 64 frames k): the window around fit[y][0] + S, the row's samples p(j) and the
+// output (plane 0) of (y, k).  plain_row() is false outside the map.
 template <typename T>
-__global__ __launch_bounds__(64 * kWaves) void k_line_core_plain(const LineCoreArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t y = (int64_t)blockIdx.y * kWaves + (threadIdx.x >> 6);
-    const int64_t k = (int64_t)blockIdx.x * 64 + lane;
-    const int64_t ih = a.height;
-    if (y >= ih || k >= a.n) return;
-    constexpr int scale = sizeof(T) == 1 ? 256 : 1;
+struct PlainRow {
+    int64_t y;
     int lo, hi;
-    window_of(a.fit[y * 4], 0, a.hw, (int)a.width, lo, hi);
-    const T* row = static_cast<const T*>(a.stack) + k * a.fstride + y * a.width;
-    Core s;
-    core_init(s);
-    for (int j = lo; j <= hi; ++j) core_step(s, j, (int)row[j] * scale, lo, hi);
-    const int64_t c = a.k_offset + k;
-    a.map[y * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c)] = core_shift(s, lo, hi, a.fit[y * 4 + 3]);
-}
-
-template <typename T>
-__global__ __launch_bounds__(64 * kWaves) void k_line_profile_plain(const ProfileArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t y = (int64_t)blockIdx.y * kWaves + (threadIdx.x >> 6);
-    const int64_t k = (int64_t)blockIdx.x * 64 + lane;
-    const int64_t ih = a.height;
-    if (y >= ih || k >= a.n) return;
-    constexpr int scale = sizeof(T) == 1 ? 256 : 1;
-    int lo, hi;
-    window_of(a.fit[y * 4], a.shift, a.hw, (int)a.width, lo, hi);
-    const T* row = static_cast<const T*>(a.stack) + k * a.fstride + y * a.width;
-    Walk1 s;
-    walk1_init(s);
-    for (int j = lo; j <= hi; ++j) walk1_step(s, j, (int)row[j] * scale, lo, hi);
-    const Vertex v = vertex_of(s, lo, hi, a.fit[y * 4 + 3] + (double)a.shift);
-    Walk2 t;
-    walk2_init(t);
-    for (int j = lo; j <= hi; ++j) walk2_step(t, j, (int)row[j] * scale, lo, hi, s.c.jb, v.thr);
-    const int64_t c = a.k_offset + k;
-    float* out = a.planes + y * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c);
-    out[0] = v.shift;
-    out[a.plane_stride] = v.core;
-    out[2 * a.plane_stride] = width_of(t, v.half, v.thr);
-    out[3 * a.plane_stride] = v.cog;
-    out[4 * a.plane_stride] = v.ew;
-}
-
-// ---- line bisectors (shg_line_bisector) ----
-// Walk 1 of the bisectors: the vertex state and C2 = p(lo) + p(hi).
-struct Walk1B {
-    Core c;
-    int c2;
+    const T* row;
+    float* out;
+    __device__ int p(int j) const { return (int)row[j] * (sizeof(T) == 1 ? 256 : 1); }   // video_reader.py:121-122
 };
 
-__device__ __forceinline__ void walk1b_step(Walk1B& s, int j, int p, int lo, int hi) {
-    core_step(s.c, j, p, lo, hi, [&] {
-        if (j == lo || j == hi) s.c2 += p;
-    });
-}
-
-// core_d of a row with a vertex (lo < j* < hi), as vertex_of computes it.
-__device__ __forceinline__ double core_d_of(const Core& c) {
-    const int den = c.a + c.e - 2 * c.best;
-    const int64_t d = c.a - c.e;
-    return (double)c.best - (double)(d * d) / (8.0 * (double)den);
-}
-
-// level = ((1 - f) core_d) + (f (0.5 C2)), one IEEE operation a step (f = 0.5: the profile's half, bit for bit).
-__device__ __forceinline__ double level_of(double f, double core_d, int c2) { return ((1.0 - f) * core_d) + (f * (0.5 * (double)c2)); }
-
-// The crossing threshold ceil(level) of a row with a vertex, INT_MAX when p(j*) >= level (|level| < 2^30: core_d > -2^30, C2 < 2^17).
-__device__ __forceinline__ int thr_of(double level, int best) { return (double)best < level ? (int)ceil(level) : INT_MAX; }
-
-// The crossings of walk 2's state at `level` (width_of's xl and xr); false when the row has no crossing pair.
-__device__ __forceinline__ bool crossings(int jl, int jr, uint32_t l, uint32_t r, double level, int thr, double& xl, double& xr) {
-    if (thr == INT_MAX || jl < 0 || jr < 0) return false;
-    const int pl = (int)(l & 0xffffu), pl1 = (int)(l >> 16), pr = (int)(r & 0xffffu), pr1 = (int)(r >> 16);
-    xl = (double)jl + ((double)pl - level) / (double)(pl - pl1);
-    xr = (double)jr - ((double)pr - level) / (double)(pr - pr1);
+template <typename T>
+__device__ __forceinline__ bool plain_row(const MapArgs& a, PlainRow<T>& t) {
+    t.y = (int64_t)blockIdx.y * kWaves + (threadIdx.x >> 6);
+    const int64_t k = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    if (t.y >= a.height || k >= a.n) return false;
+    window_of(a.fit[t.y * 4], a.shift, a.hw, (int)a.width, t.lo, t.hi);
+    t.row = static_cast<const T*>(a.stack) + k * a.fstride + t.y * a.width;
+    const int64_t c = a.k_offset + k;
+    t.out = a.planes + t.y * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c);
     return true;
 }
 
-__device__ __forceinline__ void bisector_of(int jl, int jr, uint32_t l, uint32_t r, double level, int thr, double ref, float& bis,
-                                            float& chord) {
-    double xl, xr;
-    bis = chord = __builtin_nanf("");
-    if (!crossings(jl, jr, l, r, level, thr, xl, xr)) return;
-    bis = (float)((0.5 * (xl + xr)) - ref);
-    chord = (float)(xr - xl);
+// Walk 2 of a plain kernel's row at one level (none when thr = INT_MAX: no crossing can be found).
+template <typename T>
+__device__ __forceinline__ Cross cross_row(const PlainRow<T>& t, int jb, int thr) {
+    Cross s;
+    cross_init(s);
+    if (thr == INT_MAX) return s;
+    for (int j = t.lo, prev = 0; j <= t.hi; ++j) {
+        const int p = t.p(j);
+        cross_step(s, j, p, prev, t.lo, t.hi, jb, thr);
+        prev = p;
+    }
+    return s;
 }
 
-// Walk 2's crossing state of one (row, level): walk2_step's, the previous sample shared by a row's levels.
-struct Cross {
-    int jl, jr;
-    uint32_t l, r;
-};
-
-__device__ __forceinline__ void cross_step(Cross& s, int j, int p, int prev, int lo, int hi, int jb, int thr) {
-    if (j > lo && j <= jb && prev >= thr) {
-        s.jl = j - 1;
-        s.l = (uint32_t)prev | ((uint32_t)p << 16);      // p(jl), p(jl + 1)
-    }
-    if (j > jb && j <= hi && s.jr < 0 && p >= thr) {
-        s.jr = j;
-        s.r = (uint32_t)p | ((uint32_t)prev << 16);      // p(jr), p(jr - 1)
-    }
+template <typename T>
+__global__ __launch_bounds__(64 * kWaves) void k_line_core_plain(const MapArgs a) {
+    PlainRow<T> t;
+    if (!plain_row(a, t)) return;
+    Core s;
+    core_init(s);
+    for (int j = t.lo; j <= t.hi; ++j) core_step(s, j, t.p(j), t.lo, t.hi);
+    t.out[0] = core_shift(s, t.lo, t.hi, a.fit[t.y * 4 + 3]);
 }
 
+template <typename T>
+__global__ __launch_bounds__(64 * kWaves) void k_line_profile_plain(const MapArgs a) {
+    PlainRow<T> t;
+    if (!plain_row(a, t)) return;
+    Walk1 s;
+    walk1_init(s);
+    for (int j = t.lo; j <= t.hi; ++j) walk1_step(s, j, t.p(j), t.lo, t.hi);
+    const Vertex v = vertex_of(s, t.lo, t.hi, a.fit[t.y * 4 + 3] + (double)a.shift);
+    t.out[0] = v.shift;
+    t.out[a.plane_stride] = v.core;
+    t.out[2 * a.plane_stride] = crossings(cross_row(t, s.c.jb, v.thr), v.half, v.thr, 0.0).len;
+    t.out[3 * a.plane_stride] = v.cog;
+    t.out[4 * a.plane_stride] = v.ew;
+}
+
+// ---- line bisectors (shg_line_bisector) ----
 template <typename T, bool VEC>
-__global__ __launch_bounds__(64 * kWaves) void k_line_bisector_rot(const BisectorArgs a) {
+__global__ __launch_bounds__(64 * kWaves) void k_line_bisector_rot(const MapArgs a) {
     constexpr int L = kLevelsPerPass;
     __shared__ float tile[2 * L * kWaves * kTileRows];              // 64 KiB: two workgroups per CU
     const int lane = threadIdx.x & 63;
@@ -526,13 +500,10 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_bisector_rot(const Bisecto
         double core[kRowsPerLane];
         int c2[kRowsPerLane], best[kRowsPerLane], jb[kRowsPerLane];
         if (k < a.n) {
-            Walk1B s[kRowsPerLane];
+            Walk1 s[kRowsPerLane];
 #pragma unroll
-            for (int r = 0; r < kRowsPerLane; ++r) {
-                core_init(s[r].c);
-                s[r].c2 = 0;
-            }
-            walk_band<T, VEC>(frame, b, [&](int j, int r, int p) { walk1b_step(s[r], j, p, b.lo[r], b.hi[r]); });
+            for (int r = 0; r < kRowsPerLane; ++r) walk1_init(s[r]);
+            walk_band<T, VEC>(frame, b, [&](int j, int r, int p) { walk1_step(s[r], j, p, b.lo[r], b.hi[r]); });
 #pragma unroll
             for (int r = 0; r < kRowsPerLane; ++r) {
                 const bool vertex = s[r].c.jb > b.lo[r] && s[r].c.jb < b.hi[r];     // (false without a window: lo > hi)
@@ -553,8 +524,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_bisector_rot(const Bisecto
 #pragma unroll
                     for (int l = 0; l < L; ++l) {
                         thr[r][l] = jb[r] >= 0 && l < nl ? thr_of(level_of(a.f[l0 + l], core[r], c2[r]), best[r]) : INT_MAX;
-                        t[r][l].jl = t[r][l].jr = -1;
-                        t[r][l].l = t[r][l].r = 0;
+                        cross_init(t[r][l]);
                     }
                 }
                 walk_band<T, VEC>(frame, b, [&](int j, int r, int p) {
@@ -567,71 +537,46 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_bisector_rot(const Bisecto
                 for (int h = 0; h < kRowsPerLane; h += 4) {
 #pragma unroll
                     for (int l = 0; l < L; ++l) {
-                        float bis[4], chord[4];
+                        Chord c[4];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int64_t x = b.x0 + h + r;
                             const double ref = x < b.width ? a.fit[(b.width - 1 - x) * 4 + 3] + (double)a.shift : 0.0;
-                            const Cross& c = t[h + r][l];
-                            bisector_of(c.jl, c.jr, c.l, c.r, l < nl ? level_of(a.f[l0 + l], core[h + r], c2[h + r]) : 0.0,
-                                        thr[h + r][l], ref, bis[r], chord[r]);
+                            c[r] = crossings(t[h + r][l], l < nl ? level_of(a.f[l0 + l], core[h + r], c2[h + r]) : 0.0, thr[h + r][l], ref);
                         }
                         const int row = lane * kRowsPerLane + h;
-                        *reinterpret_cast<float4*>(&tile[tile_at(l, wave, row)]) = make_float4(bis[0], bis[1], bis[2], bis[3]);
-                        *reinterpret_cast<float4*>(&tile[tile_at(L + l, wave, row)]) =
-                            make_float4(chord[0], chord[1], chord[2], chord[3]);
+                        *reinterpret_cast<float4*>(&tile[tile_at(l, wave, row)]) = make_float4(c[0].bis, c[1].bis, c[2].bis, c[3].bis);
+                        *reinterpret_cast<float4*>(&tile[tile_at(L + l, wave, row)]) = make_float4(c[0].len, c[1].len, c[2].len, c[3].len);
                     }
                 }
             }
             __syncthreads();
-            // 8 threads write 8 consecutive columns of one map row of one plane: tile plane qt < L is level l0 + qt's bisector, L + i
-            // its chord
-            for (int idx = threadIdx.x; idx < 2 * L * kTileRows * kWaves; idx += 64 * kWaves) {
-                const int qt = idx / (kTileRows * kWaves), rl = (idx / kWaves) % kTileRows, f = idx % kWaves;
+            // tile plane qt < L is level l0 + qt's bisector, L + i its chord
+            write_tile<2 * L>(a, tile, kb, [&](int qt) {
                 const int li = qt % L;
-                const int64_t x = (int64_t)blockIdx.x * kTileRows + rl, kf = kb + f;
-                if (li < nl && x < b.width && kf < a.n) {
-                    const int64_t q = (qt < L ? 0 : a.nl) + l0 + li;
-                    const int64_t c = a.k_offset + kf;
-                    a.planes[q * a.plane_stride + (b.width - 1 - x) * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c)] = tile[tile_at(qt, f, rl)];
-                }
-            }
+                return li < nl ? (int64_t)((qt < L ? 0 : a.nl) + l0 + li) : (int64_t)-1;
+            });
             __syncthreads();
         }
     }
 }
 
 template <typename T>
-__global__ __launch_bounds__(64 * kWaves) void k_line_bisector_plain(const BisectorArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t y = (int64_t)blockIdx.y * kWaves + (threadIdx.x >> 6);
-    const int64_t k = (int64_t)blockIdx.x * 64 + lane;
-    const int64_t ih = a.height;
-    if (y >= ih || k >= a.n) return;
-    constexpr int scale = sizeof(T) == 1 ? 256 : 1;
-    int lo, hi;
-    window_of(a.fit[y * 4], a.shift, a.hw, (int)a.width, lo, hi);
-    const T* row = static_cast<const T*>(a.stack) + k * a.fstride + y * a.width;
-    Walk1B s;
-    core_init(s.c);
-    s.c2 = 0;
-    for (int j = lo; j <= hi; ++j) walk1b_step(s, j, (int)row[j] * scale, lo, hi);
-    const bool vertex = s.c.jb > lo && s.c.jb < hi;
+__global__ __launch_bounds__(64 * kWaves) void k_line_bisector_plain(const MapArgs a) {
+    PlainRow<T> t;
+    if (!plain_row(a, t)) return;
+    Walk1 s;
+    walk1_init(s);
+    for (int j = t.lo; j <= t.hi; ++j) walk1_step(s, j, t.p(j), t.lo, t.hi);
+    const bool vertex = s.c.jb > t.lo && s.c.jb < t.hi;
     const double core = vertex ? core_d_of(s.c) : 0.0;
-    const double ref = a.fit[y * 4 + 3] + (double)a.shift;
-    const int64_t c = a.k_offset + k;
-    float* out = a.planes + y * a.pitch + (a.flip_x ? a.n_cols - 1 - c : c);
+    const double ref = a.fit[t.y * 4 + 3] + (double)a.shift;
     for (int i = 0; i < a.nl; ++i) {
         const double level = level_of(a.f[i], core, s.c2);
         const int thr = vertex ? thr_of(level, s.c.best) : INT_MAX;
-        Walk2 t;
-        walk2_init(t);
-        if (thr != INT_MAX)
-            for (int j = lo; j <= hi; ++j) walk2_step(t, j, (int)row[j] * scale, lo, hi, s.c.jb, thr);
-        float bis, chord;
-        bisector_of(t.jl, t.jr, t.l, t.r, level, thr, ref, bis, chord);
-        out[i * a.plane_stride] = bis;
-        out[(a.nl + i) * a.plane_stride] = chord;
+        const Chord c = crossings(cross_row(t, s.c.jb, thr), level, thr, ref);
+        t.out[i * a.plane_stride] = c.bis;
+        t.out[(a.nl + i) * a.plane_stride] = c.len;
     }
 }
 
@@ -698,11 +643,11 @@ __global__ __launch_bounds__(256) void k_map_finish(const FinishArgs a) {
     }
 }
 
-
-// The checks shg_line_core_shift and shg_line_profile share; `fn` names the entry point in the messages.
+// The checks the three maps share; `fn` names the entry point in the messages.  Beyond the Dopplergram's one plane (planes = 1,
+// measured at the fitted line) also the plane stride and the shift.
 int check_map_args(const char* fn, const void* stack, const double* fit, const float* out, int64_t n_frames, int64_t height,
-                   int64_t width, int bytes_per_px, int64_t frame_stride_px, int half_width, int64_t row_pitch, int64_t n_cols,
-                   int64_t k_offset) {
+                   int64_t width, int bytes_per_px, int64_t frame_stride_px, int half_width, int shift, int planes, int64_t plane_stride,
+                   int64_t row_pitch, int64_t n_cols, int64_t k_offset) {
     SHG_REQUIRE(stack && fit && out, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(n_frames > 0 && height > 0 && width > 0, SHG_E_ARG, "%s: empty input", fn);
     SHG_REQUIRE(bytes_per_px == 1 || bytes_per_px == 2, SHG_E_ARG, "%s: bytes_per_px must be 1 or 2", fn);
@@ -718,14 +663,21 @@ int check_map_args(const char* fn, const void* stack, const double* fit, const f
     // (the rotated kernels address a sample as `frame base + 32-bit byte offset`, their spectral rows as int)
     SHG_REQUIRE(height * width * bytes_per_px < (1ll << 32) && height < (1ll << 31) && width < (1ll << 31), SHG_E_UNSUPPORTED,
                 "%s: a frame of %lld x %lld samples is larger than 4 GiB", fn, (long long)height, (long long)width);
+    if (planes != 1) {
+        const int64_t ih = width > height ? width : height, iw = width > height ? height : width;
+        SHG_REQUIRE(plane_stride >= ih * row_pitch, SHG_E_ARG, "%s: plane stride < %lld x %lld", fn, (long long)ih, (long long)row_pitch);
+        // a line at a column in [0, iw) shifted by S has a window of three samples within [1, iw - 2] only when 3 - iw - H < S < iw - 3 + H
+        SHG_REQUIRE(shift > 3 - iw - half_width && shift < iw - 3 + half_width, SHG_E_ARG,
+                    "%s: shift %d puts every window outside columns [1, %lld]", fn, shift, (long long)(iw - 2));
+    }
     return 0;
 }
 
-// The launch the two maps share: on rotated files (width > height) the rotated kernel, 512 slit rows x 16 frames a workgroup, with
+// The launch the three maps share: on rotated files (width > height) the rotated kernel, 512 slit rows x 16 frames a workgroup, with
 // 16-byte pieces (8 for 8-bit samples) when every row of every frame starts on that boundary; else the plain kernel, 64 frames x 8
 // slit rows a workgroup.  rot(T(), std::bool_constant<VEC>()) and plain(T()) name the kernels' instances.
-template <typename Args, typename Rot, typename Plain>
-int launch_map(const Args& a, int bytes_per_px, hipStream_t st, Rot rot, Plain plain, const char* rot_name, const char* plain_name) {
+template <typename Rot, typename Plain>
+int launch_map(const MapArgs& a, int bytes_per_px, hipStream_t st, Rot rot, Plain plain, const char* rot_name, const char* plain_name) {
     const int64_t ih = a.width > a.height ? a.width : a.height;
     if (a.width > a.height) {
         const int64_t piece = kRowsPerLane * bytes_per_px;
@@ -741,9 +693,11 @@ int launch_map(const Args& a, int bytes_per_px, hipStream_t st, Rot rot, Plain p
     return shg::launch(bytes_per_px == 2 ? plain(uint16_t()) : plain(uint8_t()), grid, dim3(64 * kWaves), 0, st, a, plain_name);
 }
 
-// The checks the two finish calls share, and the crop (crop_plan's (nw, lo, dx0, n); none when crop4 is NULL), the mask and the
-// shift display scale resolved into `a`, which holds the caller's planes, strides and warp.  planes = 1: the Dopplergram's one plane.
-int finish_args(const char* fn, int planes, const double* circle3, const int64_t* crop4, double display_range, FinishArgs& a) {
+// The checks the finish calls share, and the crop (crop_plan's (nw, lo, dx0, n); none when crop4 is NULL), the mask and the display
+// scales resolved into `a`, which holds the caller's planes, strides and warp.  planes = 1: the Dopplergram's one plane, which has
+// no width plane (half_width is not read).
+int finish_args(const char* fn, int planes, const double* circle3, const int64_t* crop4, int half_width, double display_range,
+                FinishArgs& a) {
     SHG_REQUIRE(a.raw && a.map, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(a.h > 0 && a.w > 0 && a.raw_pitch >= a.w && (planes == 1 || a.raw_plane >= a.h * a.raw_pitch) && a.out_h > 0 &&
                     a.out_w > 0,
@@ -774,6 +728,11 @@ int finish_args(const char* fn, int planes, const double* circle3, const int64_t
     a.cy = a.masked ? circle3[1] : 0.0;
     a.rad = a.masked ? circle3[2] : 0.0;
     a.shift_scale = a.png ? 32767.0 / display_range : 0.0;
+    if (planes != 1) {
+        SHG_REQUIRE(!a.png || (half_width >= 1 && half_width <= kMaxHalfWidth), SHG_E_UNSUPPORTED, "%s: half-width %d outside [1, %d]",
+                    fn, half_width, kMaxHalfWidth);
+        a.width_scale = a.png ? 65534.0 / (double)(2 * half_width + 1) : 0.0;
+    }
     return 0;
 }
 
@@ -783,10 +742,10 @@ extern "C" int shg_line_core_shift(const void* stack, int64_t n_frames, int64_t 
                                    int64_t frame_stride_px, const double* fit, int half_width, int flip_x, float* map,
                                    int64_t row_pitch, int64_t n_cols, int64_t k_offset, shg_stream_t stream) {
     if (const int e = check_map_args("shg_line_core_shift", stack, fit, map, n_frames, height, width, bytes_per_px, frame_stride_px,
-                                     half_width, row_pitch, n_cols, k_offset))
+                                     half_width, 0, 1, 0, row_pitch, n_cols, k_offset))
         return e;
     const int64_t fstride = frame_stride_px > 0 ? frame_stride_px : height * width;
-    LineCoreArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, map, row_pitch, n_cols, k_offset, flip_x ? 1 : 0};
+    MapArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, 0, map, 0, row_pitch, n_cols, k_offset, flip_x ? 1 : 0, 0, {}};
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("line_core_shift", st);
     return launch_map(
@@ -799,7 +758,7 @@ extern "C" int shg_doppler_finish(const float* raw, int64_t h, int64_t w, int64_
                                   int64_t map_pitch, uint16_t* png, int64_t png_pitch, double display_range, shg_stream_t stream) {
     FinishArgs a{raw, 0, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, map, 0, map_pitch, png, 0, png_pitch,
                  0.0, 0.0};
-    if (const int e = finish_args("shg_doppler_finish", 1, circle3, crop4, display_range, a)) return e;
+    if (const int e = finish_args("shg_doppler_finish", 1, circle3, crop4, 0, display_range, a)) return e;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("doppler_finish", st);
     return shg::launch(k_map_finish<1>, dim3((unsigned)((a.nw + 255) / 256), (unsigned)out_h), dim3(256), 0, st, a, "k_map_finish<1>");
@@ -809,17 +768,11 @@ extern "C" int shg_line_profile(const void* stack, int64_t n_frames, int64_t hei
                                 int64_t frame_stride_px, const double* fit, int half_width, int shift, int flip_x, float* planes,
                                 int64_t plane_stride, int64_t row_pitch, int64_t n_cols, int64_t k_offset, shg_stream_t stream) {
     if (const int e = check_map_args("shg_line_profile", stack, fit, planes, n_frames, height, width, bytes_per_px, frame_stride_px,
-                                     half_width, row_pitch, n_cols, k_offset))
+                                     half_width, shift, kPlanes, plane_stride, row_pitch, n_cols, k_offset))
         return e;
-    const int64_t ih = width > height ? width : height, iw = width > height ? height : width;
-    SHG_REQUIRE(plane_stride >= ih * row_pitch, SHG_E_ARG, "shg_line_profile: plane stride < %lld x %lld", (long long)ih,
-                (long long)row_pitch);
-    // a line at a column in [0, iw) shifted by S has a window of three samples within [1, iw - 2] only when 3 - iw - H < S < iw - 3 + H
-    SHG_REQUIRE(shift > 3 - iw - half_width && shift < iw - 3 + half_width, SHG_E_ARG,
-                "shg_line_profile: shift %d puts every window outside columns [1, %lld]", shift, (long long)(iw - 2));
     const int64_t fstride = frame_stride_px > 0 ? frame_stride_px : height * width;
-    ProfileArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, shift, planes, plane_stride, row_pitch, n_cols,
-                  k_offset, flip_x ? 1 : 0};
+    MapArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, shift, planes, plane_stride, row_pitch, n_cols, k_offset,
+              flip_x ? 1 : 0, 0, {}};
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("line_profile", st);
     return launch_map(
@@ -833,10 +786,7 @@ extern "C" int shg_line_profile_finish(const float* raw, int64_t raw_plane_strid
                                        int64_t png_pitch, int half_width, double display_range, shg_stream_t stream) {
     FinishArgs a{raw, raw_plane_stride, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, maps,
                  map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0};
-    if (const int e = finish_args("shg_line_profile_finish", kPlanes, circle3, crop4, display_range, a)) return e;
-    SHG_REQUIRE(!png || (half_width >= 1 && half_width <= kMaxHalfWidth), SHG_E_UNSUPPORTED,
-                "shg_line_profile_finish: half-width %d outside [1, %d]", half_width, kMaxHalfWidth);
-    a.width_scale = png ? 65534.0 / (double)(2 * half_width + 1) : 0.0;
+    if (const int e = finish_args("shg_line_profile_finish", kPlanes, circle3, crop4, half_width, display_range, a)) return e;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("line_profile_finish", st);
     return shg::launch(k_map_finish<kPlanes>, dim3((unsigned)((a.nw + 255) / 256), (unsigned)out_h), dim3(256), 0, st, a,
@@ -848,21 +798,16 @@ extern "C" int shg_line_bisector(const void* stack, int64_t n_frames, int64_t he
                                  int flip_x, float* planes, int64_t plane_stride, int64_t row_pitch, int64_t n_cols, int64_t k_offset,
                                  shg_stream_t stream) {
     if (const int e = check_map_args("shg_line_bisector", stack, fit, planes, n_frames, height, width, bytes_per_px, frame_stride_px,
-                                     half_width, row_pitch, n_cols, k_offset))
+                                     half_width, shift, 2 * n_levels, plane_stride, row_pitch, n_cols, k_offset))
         return e;
-    const int64_t ih = width > height ? width : height, iw = width > height ? height : width;
-    SHG_REQUIRE(plane_stride >= ih * row_pitch, SHG_E_ARG, "shg_line_bisector: plane stride < %lld x %lld", (long long)ih,
-                (long long)row_pitch);
-    SHG_REQUIRE(shift > 3 - iw - half_width && shift < iw - 3 + half_width, SHG_E_ARG,
-                "shg_line_bisector: shift %d puts every window outside columns [1, %lld]", shift, (long long)(iw - 2));
     SHG_REQUIRE(levels && n_levels >= 1 && n_levels <= kMaxLevels, SHG_E_ARG, "shg_line_bisector: %d levels (1 to %d)", n_levels,
                 kMaxLevels);
     for (int i = 0; i < n_levels; ++i)
         SHG_REQUIRE(isfinite(levels[i]) && levels[i] > 0.0 && levels[i] < 1.0 && (i == 0 || levels[i] > levels[i - 1]), SHG_E_ARG,
                     "shg_line_bisector: levels must be finite, strictly increasing and inside (0, 1) (level %d is %g)", i, levels[i]);
     const int64_t fstride = frame_stride_px > 0 ? frame_stride_px : height * width;
-    BisectorArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, shift, planes, plane_stride, row_pitch, n_cols,
-                   k_offset, flip_x ? 1 : 0, n_levels, {}};
+    MapArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, shift, planes, plane_stride, row_pitch, n_cols, k_offset,
+              flip_x ? 1 : 0, n_levels, {}};
     for (int i = 0; i < n_levels; ++i) a.f[i] = levels[i];
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("line_bisector", st);
@@ -894,10 +839,7 @@ extern "C" int shg_line_bisector_finish(const float* raw, int64_t raw_plane_stri
                 kMaxLevels);
     FinishArgs a{raw, raw_plane_stride, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, maps,
                  map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0};
-    if (const int e = finish_args("shg_line_bisector_finish", 2 * n_levels, circle3, crop4, display_range, a)) return e;
-    SHG_REQUIRE(!png || (half_width >= 1 && half_width <= kMaxHalfWidth), SHG_E_UNSUPPORTED,
-                "shg_line_bisector_finish: half-width %d outside [1, %d]", half_width, kMaxHalfWidth);
-    a.width_scale = png ? 65534.0 / (double)(2 * half_width + 1) : 0.0;
+    if (const int e = finish_args("shg_line_bisector_finish", 2 * n_levels, circle3, crop4, half_width, display_range, a)) return e;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("line_bisector_finish", st);
     return launch_bisector_finish<kMaxLevels>(n_levels, a, st);

@@ -854,26 +854,34 @@ def line_profile(stack, fit, half_width, shift=0, flip_x=False, n_cols=None, k_o
     return out
 
 
+def _planes_finish(fn, planes, dims, raw, h00, h01, h02, out_h, out_w, circle, crop, half_width, display_range, *levels):
+    """What line_profile_finish and line_bisector_finish share: raw float32 [planes, h, w] (`dims` names the count in the message)
+    through the C call `fn` (`levels`: its arguments after the raw plane stride) -> (maps float32 [planes, out_h, nw], png uint16
+    [planes, out_h, nw] or None)."""
+    _dev(raw, 'raw')
+    if raw.dim() != 3 or raw.shape[0] != planes or raw.dtype != torch.float32 or raw.stride(2) != 1:
+        raise ValueError('raw must be a float32 [%s, h, w] view with unit column stride' % dims)
+    if (half_width is None) != (display_range is None):
+        raise ValueError('the display planes need both half_width and display_range')
+    _, h, w = raw.shape
+    nw, c3, c4 = _finish_setup(out_w, circle, crop)
+    out = torch.empty((planes, int(out_h), nw), dtype=torch.float32, device=raw.device)
+    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=raw.device)
+    _lib.check(getattr(lib, fn)(raw.data_ptr(), raw.stride(0), *levels, h, w, raw.stride(1), float(h00), float(h01), float(h02),
+                                int(out_h), int(out_w), _host_ptr(c3), _host_ptr(c4), out.data_ptr(), out.stride(0), out.stride(1),
+                                None if png is None else png.data_ptr(), out.stride(0), out.stride(1),
+                                0 if half_width is None else int(half_width), 0.0 if display_range is None else float(display_range),
+                                _stream()), fn)
+    return out, png
+
+
 def line_profile_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=None, half_width=None, display_range=None):
     """shg_line_profile_finish: the five raw planes float32 [5, ih, N] through doppler_finish's geometry, all in one launch ->
     (maps float32 [5, out_h, nw], png uint16 [5, out_h, nw] or None).  With half_width H and display_range R also the display
     planes: 0 for NaN; shift and cog as the Dopplergram's, core clip(rint(v), 1, 65535), width and ew
     clip(rint(1 + v * 65534 / (2H + 1)), 1, 65535)."""
-    _dev(raw, 'raw')
-    if raw.dim() != 3 or raw.shape[0] != len(LINE_PROFILE_PLANES) or raw.dtype != torch.float32 or raw.stride(2) != 1:
-        raise ValueError('raw must be a float32 [5, h, w] view with unit column stride')
-    if (half_width is None) != (display_range is None):
-        raise ValueError('the display planes need both half_width and display_range')
-    _, h, w = raw.shape
-    nw, c3, c4 = _finish_setup(out_w, circle, crop)
-    out = torch.empty((len(LINE_PROFILE_PLANES), int(out_h), nw), dtype=torch.float32, device=raw.device)
-    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=raw.device)
-    _lib.check(lib.shg_line_profile_finish(raw.data_ptr(), raw.stride(0), h, w, raw.stride(1), float(h00), float(h01), float(h02),
-                                           int(out_h), int(out_w), _host_ptr(c3), _host_ptr(c4), out.data_ptr(), out.stride(0),
-                                           out.stride(1), None if png is None else png.data_ptr(), out.stride(0), out.stride(1),
-                                           0 if half_width is None else int(half_width),
-                                           0.0 if display_range is None else float(display_range), _stream()), 'shg_line_profile_finish')
-    return out, png
+    return _planes_finish('shg_line_profile_finish', len(LINE_PROFILE_PLANES), '5', raw, h00, h01, h02, out_h, out_w, circle, crop,
+                          half_width, display_range)
 
 
 def line_bisector(stack, fit, half_width, levels, shift=0, flip_x=False, n_cols=None, k_offset=0, out=None):
@@ -893,19 +901,6 @@ def line_bisector_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=Non
     """shg_line_bisector_finish: the 2K raw planes float32 [2K, ih, N] of line_bisector through doppler_finish's geometry, all in one
     launch -> (maps float32 [2K, out_h, nw], png uint16 [2K, out_h, nw] or None).  With half_width H and display_range R also the
     display planes: 0 for NaN; the bisectors as the Dopplergram's shift, the chords clip(rint(1 + v * 65534 / (2H + 1)), 1, 65535)."""
-    _dev(raw, 'raw')
-    if raw.dim() != 3 or raw.shape[0] % 2 or raw.dtype != torch.float32 or raw.stride(2) != 1:
-        raise ValueError('raw must be a float32 [2K, h, w] view with unit column stride')
-    if (half_width is None) != (display_range is None):
-        raise ValueError('the display planes need both half_width and display_range')
-    planes, h, w = raw.shape
-    nw, c3, c4 = _finish_setup(out_w, circle, crop)
-    out = torch.empty((planes, int(out_h), nw), dtype=torch.float32, device=raw.device)
-    png = None if display_range is None else torch.empty(out.shape, dtype=torch.uint16, device=raw.device)
-    _lib.check(lib.shg_line_bisector_finish(raw.data_ptr(), raw.stride(0), planes // 2, h, w, raw.stride(1), float(h00), float(h01),
-                                            float(h02), int(out_h), int(out_w), _host_ptr(c3), _host_ptr(c4), out.data_ptr(),
-                                            out.stride(0), out.stride(1), None if png is None else png.data_ptr(), out.stride(0),
-                                            out.stride(1), 0 if half_width is None else int(half_width),
-                                            0.0 if display_range is None else float(display_range), _stream()),
-               'shg_line_bisector_finish')
-    return out, png
+    planes = raw.shape[0] if isinstance(raw, torch.Tensor) and raw.dim() == 3 and raw.shape[0] % 2 == 0 else -1
+    return _planes_finish('shg_line_bisector_finish', planes, '2K', raw, h00, h01, h02, out_h, out_w, circle, crop, half_width,
+                          display_range, planes // 2)
