@@ -160,7 +160,7 @@ int shg_atlas_correlate(const uint8_t* atlas_y, int64_t n_atlas, double first, d
                         const double* scales, int64_t n_guesses, double* corr, int32_t* run, const int32_t* row_of_guess,
                         int64_t n_rows, double* rows, shg_stream_t stream);
 
-/* ---- the Dopplergram (not a reference stage; tests/doppler_ref.py restates both calls in NumPy, bit for bit)
+/* ---- the Dopplergram (not a reference stage; tests/linemaps_ref.py restates both calls in NumPy, bit for bit)
  * shg_line_core_shift: the line-core position of every (slit row y, frame k) of a frame stack in file layout (n_frames, height,
  * width, bytes_per_px, frame_stride_px as shg_extract_columns takes them).  p(j) = sample (y, j) of frame k after a1's rotation
  * (out[i, j] = raw[j, W - 1 - i] when width > height), 8-bit samples x 256.  fit[ih][4] float64 (device); c = int(fit[y][0])
@@ -184,7 +184,7 @@ int shg_doppler_finish(const float* raw, int64_t h, int64_t w, int64_t raw_pitch
                        int64_t out_h, int64_t out_w, const double* circle3, const int64_t* crop4, float* map, int64_t map_pitch,
                        uint16_t* png, int64_t png_pitch, double display_range, shg_stream_t stream);
 
-/* ---- line-profile maps (not a reference stage; tests/lineprofile_ref.py restates both calls in NumPy, bit for bit)
+/* ---- line-profile maps (not a reference stage; tests/linemaps_ref.py restates both calls in NumPy, bit for bit)
  * shg_line_profile: five planes of every (slit row y, frame k) of a frame stack in shg_line_core_shift's layout and with its p(j),
  * measured around the line shifted by the integer S (`shift`, the -w shift; 0 = the fitted line).  c = (int64)(fit[y][0] + (double)S)
  * (truncated), lo = max(c - H, 1), hi = min(c + H, iw - 2); every plane NaN when fit[y][0] is not finite or hi - lo < 2.
@@ -215,7 +215,7 @@ int shg_line_profile_finish(const float* raw, int64_t raw_plane_stride, int64_t 
                             float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
                             int64_t png_pitch, int half_width, double display_range, shg_stream_t stream);
 
-/* ---- line-bisector maps (not a reference stage; tests/bisector_ref.py restates both calls in NumPy, bit for bit)
+/* ---- line-bisector maps (not a reference stage; tests/linemaps_ref.py restates both calls in NumPy, bit for bit)
  * shg_line_bisector: the line's bisector and chord at K = n_levels depths of every (slit row y, frame k), in shg_line_profile's layout,
  * with its p(j), window [lo, hi] (and SHG_E_ARG for S), ref = fit[y][3] + (double)S, j*, a, b, e, den, core_d and C2.  levels: a host
  * array of K fractions f_i, 1 <= K <= 8, finite, strictly increasing, 0 < f_1 and f_K < 1 (else SHG_E_ARG, nothing written);

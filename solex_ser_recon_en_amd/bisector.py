@@ -1,7 +1,7 @@
 """Line-bisector maps: the line shift at several depths of the line, at every point of the disk, for the fitted line or any line at
 an integer pixel shift, in the geometry of the scan's products (the maps overlay `<base>_shift=<S>_clahe.png` pixel for pixel).  Not
 a reference feature: the arithmetic is the one include/shg_hip.h states for shg_line_bisector and shg_line_bisector_finish
-(tests/bisector_ref.py restates it in NumPy).
+(tests/linemaps_ref.py restates it in NumPy).
 
     python -m solex_ser_recon_en_amd.bisector FILE [--half-width H] [--shift S | --line L] [--levels 0.2,0.4,0.6,0.8] [--widths]
         [--range R] [--dispersion D --wavelength L | --atlas A --anchor L] [SHG_MAIN flags: -x -s -r W -m ...]

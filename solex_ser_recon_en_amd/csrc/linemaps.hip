@@ -2,7 +2,7 @@
 // the core's position, its intensity, the line's width (FWHM), its centre of gravity and its equivalent width within the window) and
 // the line's bisector and chord at K levels (shg_line_bisector) in every (slit row, frame) of a scan, and those raw maps taken to the
 // products' geometry (shg_doppler_finish, shg_line_profile_finish, shg_line_bisector_finish).  Not a reference stage: the arithmetic
-// is the one include/shg_hip.h states and tests/doppler_ref.py / lineprofile_ref.py / bisector_ref.py restate in NumPy, bit for bit.
+// is the one include/shg_hip.h states and tests/linemaps_ref.py restates in NumPy, bit for bit.
 // The three maps share one core: the window, walk 1 and the vertex (core_d_of, level_of, thr_of), one walk-2 crossing state and
 // interpolation (Cross, crossings: the profile's width is the chord at half), one argument struct (MapArgs), the band walk, the
 // write-out of an LDS phase tile (write_tile), the plain kernels' prologue (plain_row), one launch and one set of checks.

@@ -1,6 +1,6 @@
 """The Dopplergram: where the line core sits at every point of the disk, i.e. a line-of-sight velocity map, in the geometry of
 the scan's products (it overlays `_clahe.png` pixel for pixel).  Not a reference feature: the arithmetic is the one
-include/shg_hip.h states for shg_line_core_shift and shg_doppler_finish (tests/doppler_ref.py restates it in NumPy).
+include/shg_hip.h states for shg_line_core_shift and shg_doppler_finish (tests/linemaps_ref.py restates it in NumPy).
 
     python -m solex_ser_recon_en_amd.doppler FILE [--half-width H] [--range R]
         [--dispersion D --wavelength L | --atlas A --anchor L] [SHG_MAIN flags: -x -s -r W -m ...]

@@ -1,7 +1,7 @@
 """Line-profile maps: the line's core intensity, width (FWHM), centre of gravity and equivalent width at every point of the disk,
 for the fitted line or any line at an integer pixel shift, in the geometry of the scan's products (the maps overlay
 `<base>_shift=<S>_clahe.png` pixel for pixel).  Not a reference feature: the arithmetic is the one include/shg_hip.h states for
-shg_line_profile and shg_line_profile_finish (tests/lineprofile_ref.py restates it in NumPy).
+shg_line_profile and shg_line_profile_finish (tests/linemaps_ref.py restates it in NumPy).
 
     python -m solex_ser_recon_en_amd.lineprofile FILE [--half-width H] [--shift S | --line L] [--range R]
         [--dispersion D --wavelength L | --atlas A --anchor L] [SHG_MAIN flags: -x -s -r W -m ...]

@@ -1,5 +1,5 @@
 """Exact restatement of shg_doppler_finish and shg_line_profile_finish (include/shg_hip.h), one output pixel at a time, written from
-the header's comments, not from the kernel nor from doppler_ref.py / lineprofile_ref.py.
+the header's comments, not from the kernel nor from linemaps_ref.py.
 
 The float64 steps the header defines stay IEEE float64 steps (Python floats: no fused operations): x = (h00 c + h01 r) + h02,
 t = x - floor(x), the blend (1 - t) L + t R, the mask's (c - cx)^2 + (r - cy)^2 > rad^2 and the display expression e.  Every

@@ -1,12 +1,16 @@
-"""Seeded adversarial line profiles for shg_line_core_shift / shg_line_profile: P[k, y, j] in the rotated frame's coordinates
-(sample scale: 8-bit samples are multiples of 256), one class per slit row, windows placed by a fit whose rows also cover the
-window's own edge cases.  to_file() gives the raw file layout; occurrences() counts, on profile_exact's records, which of the
-decisions each class exists for were actually reached."""
+"""Seeded adversarial line profiles for the line maps (shg_line_core_shift, shg_line_profile, shg_line_bisector): P[k, y, j] in the
+rotated frame's coordinates (sample scale: 8-bit samples are multiples of 256), one class per slit row, windows placed by a fit
+whose rows also cover the window's own edge cases.  to_file() gives the raw file layout; occurrences() counts, on linemaps_exact's
+records, which of the decisions each class exists for were actually reached.
+
+level_profiles() adds rows for the bisector's level decisions on top of these (which already hold unbracketed minima, C2 = 0,
+emission lines with C2 / 2 <= core, ties and window edges): a sample at ceil(level) or ceil(level) - 1 beside the core, integral
+levels, p(j*) equal to the level, and crossings on the window's edges."""
 import math
 
 import numpy as np
 
-from tests import profile_exact as ex
+from tests import linemaps_exact as ex
 
 CLASSES = ('noise', 'plateau', 'monotone', 'constant', 'halfhit', 'nowidth', 'emission', 'maxsum', 'nearedge')
 # the window's edge cases, taken in turn by the fit rows of every other cycle of classes
@@ -155,7 +159,7 @@ def to_file(P, bits, rotate):
 
 
 def occurrences(records, cls, fit, bits, shift=0):
-    """How often each decision was reached, counted on profile_exact's records (and fit kinds on the fit)."""
+    """How often each decision was reached, counted on linemaps_exact's records (and fit kinds on the fit)."""
     top, one = (65535, 1) if bits == 16 else (255 * 256, 256)       # the largest sample, and one raw step on the sample scale
     c = {}
 
@@ -216,3 +220,79 @@ def occurrences(records, cls, fit, bits, shift=0):
 REQUIRED = ('noise_0', 'noise_max', 'plateau_lo', 'plateau_lo1', 'plateau_inside', 'plateau_hi', 'mono_up', 'mono_down',
             'const_0', 'const_max', 'emission', 'near_lo1', 'near_hi1', 'core_neg', 'best_ge_half', 'best_eq_half', 'one_side',
             'half_left', 'half_right', 'half_minus1', 'fit_nan', 'fit_inf', 'fit_clamp', 'fit_integer', 'fit_trunc')
+
+
+# ---- rows for the bisector's levels ----
+# the level sets the tests run: one level, the usual four, dyadic levels (integral levels need them), and eight reaching near 0 and 1
+LEVEL_SETS = ((0.5,), (0.2, 0.4, 0.6, 0.8), (0.25, 0.5, 0.75), (1e-6, 0.1, 0.3, 0.45, 0.55, 0.7, 0.9, 1.0 - 1e-6))
+LEVEL_KINDS = ('hit_left', 'hit_right', 'integral', 'best_eq', 'edges')
+
+
+def _level_row(kind, k, rng, Q, iw, lo, hi, levels):
+    """One profile (raw ints 0..Q) of a level class for frame k, or None when the window is too narrow.  Levels scale with the
+    samples (x 256 for 8-bit files is exact), so the classes are built in raw units."""
+    if hi - lo < 6:
+        return None
+    p = rng.integers(0, Q + 1, iw)
+    js = int(rng.integers(lo + 3, hi - 2))
+    if kind == 'best_eq':                  # p(lo) = b + 1, a = b + 4, e = p(hi) = b: at f = 0.5 the level is b itself
+        b = int(rng.integers(0, Q - 8))
+        p[lo:hi + 1] = rng.integers(b + 1, Q + 1, hi - lo + 1)
+        p[js + 1:hi + 1] = rng.integers(b, Q + 1, hi - js)
+        p[lo], p[js - 1], p[js], p[js + 1], p[hi] = b + 1, b + 4, b, b, b
+        return p
+    if kind == 'integral':                 # a = e: core = b; b and C2 / 2 multiples of 4: the levels at f = k / 4 are integers
+        b = 4 * int(rng.integers(0, Q // 16))
+        alpha = eps = int(rng.integers(1, 4))
+        c2h = 4 * int(rng.integers((b + Q // 4) // 4, Q // 4))
+        plo = min(Q, c2h + int(rng.integers(0, 4)))
+        phi = 2 * c2h - plo
+    else:
+        b = int(rng.integers(0, Q // 4))
+        alpha, eps = (int(v) for v in rng.integers(1, max(Q // 16, 2), 2))
+        plo, phi = (int(v) for v in rng.integers(b + Q // 2, Q + 1, 2))
+    core = b - (alpha - eps) ** 2 / (8.0 * (alpha + eps))
+    for t in range(len(levels)):           # the frame's level, else the next one with room between the core and the continuum
+        c = math.ceil(ex.level64(levels[(k + t) % len(levels)], core, plo + phi))
+        if b + max(alpha, eps) < c - 1 and c <= Q:
+            break
+    else:
+        return None
+    # every interior sample above b and below the level, then one sample at ceil(level) or ceil(level) - 1
+    p[lo:hi + 1] = rng.integers(b + max(alpha, eps) + 1, c, hi - lo + 1)
+    p[lo], p[hi] = plo, phi
+    p[js - 1], p[js], p[js + 1] = b + alpha, b, b + eps
+    hit = c if (k // len(levels)) % 2 == 0 else c - 1
+    if kind == 'hit_left':
+        p[int(rng.integers(lo + 1, js - 1))] = hit
+    elif kind == 'hit_right':
+        p[int(rng.integers(js + 2, hi))] = hit
+    elif kind == 'integral':
+        p[int(rng.integers(lo + 1, js - 1))] = hit
+        p[int(rng.integers(js + 2, hi))] = c if hit == c - 1 else c - 1
+    elif kind == 'edges':                  # the crossings on the window's edges, or a side that never reaches the level
+        if k % 3 == 1:
+            p[lo] = c - 1
+        elif k % 3 == 2:
+            p[hi] = c - 1
+    return p
+
+
+def level_profiles(n, ih, iw, bits, half_width, levels, shift=0, seed=0):
+    """(P int64 [n, ih, iw] on the sample scale, fit [ih, 4], classes [ih]): profiles()' rows, every third slit row (with a
+    window wide enough) replaced by a level class."""
+    P, fit, cls = profiles(n, ih, iw, bits, half_width, shift, seed)
+    rng = np.random.default_rng([seed, n, ih, iw, bits, half_width, shift + 1000, len(levels), 7])
+    Q, scale = (65535, 1) if bits == 16 else (255, 256)
+    cls = list(cls)
+    for y in range(2, ih, 3):
+        win = ex.window(fit[y, 0], shift, half_width, iw)
+        if win is None:
+            continue
+        kind = LEVEL_KINDS[(y // 3) % len(LEVEL_KINDS)]
+        rows = [_level_row(kind, k, rng, Q, iw, *win, levels) for k in range(n)]
+        if any(r is None for r in rows):
+            continue
+        P[:, y] = np.stack(rows) * scale
+        cls[y] = kind
+    return P, fit, cls

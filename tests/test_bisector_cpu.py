@@ -1,5 +1,5 @@
-"""The line-bisector maps without a GPU: the NumPy restatement (tests/bisector_ref.py) against the exact reference
-(tests/bisector_exact.py) on seeded adversarial profiles, its f = 0.5 chord against the line-profile width, symmetric lines, its
+"""The line-bisector maps without a GPU: the NumPy restatement (tests/linemaps_ref.py) against the exact reference
+(tests/linemaps_exact.py) on seeded adversarial profiles, its f = 0.5 chord against the line-profile width, symmetric lines, its
 accuracy on the two synthetic scans (the tolerance the GPU tests hold line_bisector_maps() to), the display planes, and the
 library's and the CLI's argument errors."""
 import math
@@ -7,11 +7,10 @@ import math
 import numpy as np
 import pytest
 
-from tests import bisector_exact as bx
-from tests import bisector_ref as ref
-from tests import lineprofile_ref
+from tests import linemaps_exact as ex
+from tests import linemaps_ref as ref
 from tests import profile_adversarial as adv
-from tests.test_doppler_cpu import fit_at, one_row_scan
+from tests.linemaps_util import fit_at, one_row_scan
 
 LAYOUTS = [  # (name, n, ih, iw, bits, half_width, shift, rotated file)
     ('rot_u16', 12, 304, 48, 16, 7, 0, True),
@@ -22,29 +21,29 @@ LAYOUTS = [  # (name, n, ih, iw, bits, half_width, shift, rotated file)
 
 
 def check(name, n, ih, iw, bits, hw, shift, rot, levels):
-    P, fit, cls = bx.profiles(n, ih, iw, bits, hw, levels, shift, seed=5)
+    P, fit, cls = adv.level_profiles(n, ih, iw, bits, hw, levels, shift, seed=5)
     raw = adv.to_file(P, bits, rot)
-    recs = bx.records(P, fit, hw, levels, shift)
+    recs = ex.records(P, fit, hw, shift, levels)
     mism, n_dec = set(), 0
     for y, row in enumerate(recs):
         for k, r in enumerate(row or ()):
-            for exact, f64, thr, _ in bx.level_decisions(r):
+            for exact, f64, thr, _ in ex.level_decisions(r):
                 n_dec += 1
                 assert f64 == thr                      # p >= level <=> p >= ceil(level) for integer p
                 if exact != f64:
                     mism.add((y, k))
     planes = ref.line_bisector(raw, fit, hw, levels, shift)
     kk = len(levels)
-    worst = max([bx.within(planes[i], recs, i, 'bis', shift, mism) for i in range(kk)] +
-                [bx.within(planes[kk + i], recs, i, 'chord', shift, mism) for i in range(kk)])
+    worst = max([ex.within(planes[i], recs, *ex.level(i, 'bis'), mism) for i in range(kk)] +
+                [ex.within(planes[kk + i], recs, *ex.level(i, 'chord'), mism) for i in range(kk)])
     assert np.isfinite(planes).any() and np.isnan(planes).any()
     return len(mism), n_dec, worst, cls
 
 
-@pytest.mark.parametrize('levels', bx.LEVEL_SETS, ids=['K%d' % len(s) for s in bx.LEVEL_SETS])
+@pytest.mark.parametrize('levels', adv.LEVEL_SETS, ids=['K%d' % len(s) for s in adv.LEVEL_SETS])
 @pytest.mark.parametrize('layout', LAYOUTS, ids=[c[0] for c in LAYOUTS])
 def test_restatement_agrees_with_the_exact_reference(layout, levels):
-    """NaN where the exact value is NaN, within profile_exact-style bounds elsewhere.  Cases whose float64 level decides otherwise
+    """NaN where the exact value is NaN, within linemaps_exact's bounds elsewhere.  Cases whose float64 level decides otherwise
     than the exact level (b < level, or p >= level for some sample) are counted and left out: non-dyadic fractions round in 1 - f
     and in the products, and the adversarial rows put samples at ceil(level) and ceil(level) - 1 on purpose.  Dyadic levels
     (0.25, 0.5, 0.75) must have none; the others hold the count under 2 % of the decisions (measured: 0.3 to 1.1 %)."""
@@ -55,26 +54,25 @@ def test_restatement_agrees_with_the_exact_reference(layout, levels):
         assert n_mism == 0
     assert n_mism <= 0.02 * n_dec
     if layout[5] >= 5:
-        assert all(cls.count(kind) for kind in bx.KINDS), 'level classes missing'
+        assert all(cls.count(kind) for kind in adv.LEVEL_KINDS), 'level classes missing'
 
 
 def test_integral_levels_and_hits_are_reached():
     """The adversarial rows reach: a sample at ceil(level) and at ceil(level) - 1, an integral level, p(j*) = level, crossings on
     the window's edges, an unbracketed minimum, C2 = 0 and C2 / 2 <= core."""
     levels = (0.25, 0.5, 0.75)
-    P, fit, _ = bx.profiles(12, 304, 48, 16, 7, levels, 0, seed=5)
+    P, fit, _ = adv.level_profiles(12, 304, 48, 16, 7, levels, 0, seed=5)
     seen = dict.fromkeys(('ceil', 'ceil_minus1', 'integral', 'best_eq', 'edge_lo', 'edge_hi', 'unbracketed', 'c2_zero',
                           'continuum_below_core'), 0)
-    for row in bx.records(P, fit, 7, levels):
-        for r in row or ():
-            v = r['vertex']
+    for row in ex.records(P, fit, 7, 0, levels):
+        for v in row or ():
             # (C2 / 2 at or below the core leaves no vertex: p(lo) > b for a first minimum inside forces p(hi) < b)
             seen['c2_zero'] += v['C2'] == 0
             seen['continuum_below_core'] += v['C2'] <= 2 * min(v['p'][v['lo']:v['hi'] + 1])
             if v['core'] is None:
                 seen['unbracketed'] += 1
                 continue
-            for L in r['levels']:
+            for L in v['levels']:
                 lv = L['level']
                 seen['integral'] += lv.denominator == 1
                 seen['best_eq'] += v['b'] == lv
@@ -95,7 +93,7 @@ def test_chord_at_half_is_the_profile_width():
     fit = fit_at(centre)
     for hw, s in ((1, 0), (5, 0), (12, 2)):
         got = ref.line_bisector(frames, fit, hw, (0.3, 0.5), s)[3]
-        want = lineprofile_ref.line_profile(frames, fit, hw, s)[2]
+        want = ref.line_profile(frames, fit, hw, s)[2]
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
         assert np.isfinite(got).any()
         # a level's planes do not depend on the others requested
@@ -115,16 +113,16 @@ def test_symmetric_lines_give_the_shift_at_every_level():
         assert np.all(got[:5, 0, 0] == np.float32(20.5 - fit0)), got[:5, 0, 0]
 
 
-@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE))
+@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE['bisector']))
 @pytest.mark.parametrize('kind', ('symmetric', 'asymmetric'))
 def test_restatement_recovers_the_bisectors(kind, noise):
     ih, n, iw = 400, 300, 48
-    frames, centre, on, truth = ref.scan(kind, ih, n, iw, noise)
-    rms_tol, max_tol = ref.TOLERANCE[noise][kind]
+    frames, centre, on, truth = ref.bisector_scan(kind, ih, n, iw, noise)
+    rms_tol, max_tol = ref.TOLERANCE['bisector'][noise][kind]
     kk = len(ref.LEVELS)
     for d in ref.FIT_OFFSETS:
         fit = fit_at(centre + d)
-        got = ref.errors(ref.line_bisector(frames, fit, 10, ref.LEVELS)[:kk], truth(fit, 10, ref.LEVELS), on)
+        got = ref.bisector_errors(ref.line_bisector(frames, fit, 10, ref.LEVELS)[:kk], truth(fit, 10, ref.LEVELS), on)
         print('%s noise %g, fit %+g px: %s' % (kind, noise, d, got))
         for i, (rms, mx, nans) in got.items():
             assert nans == 0 and rms <= rms_tol and mx <= max_tol, (ref.LEVELS[i], rms, mx, nans)
@@ -132,7 +130,7 @@ def test_restatement_recovers_the_bisectors(kind, noise):
 
 def test_asymmetric_line_has_a_c_shaped_bisector():
     # the broad component lies 1.2 px to the red of the narrow one: the bisector moves redward from the core to the continuum
-    frames, centre, on, truth = ref.scan('asymmetric', 200, 150, 48, 0.0)
+    frames, centre, on, truth = ref.bisector_scan('asymmetric', 200, 150, 48, 0.0)
     fit = fit_at(centre)
     b = ref.line_bisector(frames, fit, 10, (0.2, 0.5, 0.8))[:3]
     med = [float(np.median(b[i][on])) for i in range(3)]
@@ -148,7 +146,7 @@ def test_display_planes():
     maps, png = ref.line_bisector_finish(raw, 1.0, 0.0, 0.0, 3, 4, half_width=5, display_range=2.0)
     assert np.array_equal(maps, raw)
     for q in range(4):
-        assert np.array_equal(png[q], lineprofile_ref.display(maps[q], 'shift' if q < 2 else 'width', 5, 2.0))
+        assert np.array_equal(png[q], ref.display(maps[q], 'shift' if q < 2 else 'width', 5, 2.0))
 
 
 # ---- the library's and the CLI's argument errors (no GPU: they are refused before the scan is read) ----

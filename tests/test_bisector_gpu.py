@@ -1,19 +1,18 @@
 """The line-bisector maps on the GPU: shg_line_bisector and shg_line_bisector_finish bit for bit against the NumPy restatement
-(tests/bisector_ref.py), against the line-profile kernels where they overlap, and against the exact reference on adversarial
-rows; refused arguments writing nothing; line_bisector_maps() recovering the bisectors of both synthetic scans within what the
-restatement achieves (bisector_ref.TOLERANCE); the CLI end to end, its maps overlaying the products."""
-import json
+(tests/linemaps_ref.py), against the line-profile kernels where they overlap, and against the exact reference (tests/linemaps_exact.py)
+on adversarial rows; refused arguments writing nothing; line_bisector_maps() recovering the bisectors of both synthetic scans within
+what the restatement achieves (linemaps_ref.TOLERANCE['bisector']); the CLI end to end, its maps overlaying the products."""
 import os
 import shutil
 
 import numpy as np
 import pytest
 
-from tests import bisector_exact as bx
-from tests import bisector_ref as ref
+from tests import linemaps_exact as ex
+from tests import linemaps_ref as ref
 from tests import profile_adversarial as adv
-from tests.test_doppler_gpu import IH, IW, N, finish_cases, fit_for, same_bits, scan_reader
-from tests.test_lineprofile_gpu import SHIFT_CASES, stack_of
+from tests.linemaps_util import (IH, IW, N, SHIFT, SHIFT_CASES, finish_cases, fit_for, marked_scan, run_json, same_bits, same_region,
+                                 scan_reader, upload, write_scan)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
@@ -37,7 +36,7 @@ def test_line_bisector_bit_exact(mods, case, k):
     frames = synth.synth_frames_numpy(n, width, height, bits, seed=11, tilt=0.01, curv=2e-5)
     ih, iw = max(width, height), min(width, height)
     fit = fit_for(synth, ih, iw, seed=len(name))
-    stack = stack_of(ops, frames, bits, pitched)
+    stack = upload(ops, frames, bits, pitched)
     n_cols, k_offset = (n + 9, 4) if sharded else (n, 0)
     levels = LEVELS[k]
     got = ops.line_bisector(stack, fit, hw, levels, shift, flip_x=flip, n_cols=n_cols, k_offset=k_offset).cpu().numpy()
@@ -58,7 +57,7 @@ def test_a_level_does_not_depend_on_the_others(mods):
         frames = synth.synth_frames_numpy(20, width, height, bits, seed=5, tilt=0.01, curv=2e-5)
         ih, iw = max(width, height), min(width, height)
         fit = fit_for(synth, ih, iw, seed=3)
-        stack = stack_of(ops, frames, bits, False)
+        stack = upload(ops, frames, bits)
         many = ops.line_bisector(stack, fit, 12, LEVELS[8]).cpu().numpy()
         for i, f in enumerate(LEVELS[8]):
             alone = ops.line_bisector(stack, fit, 12, (f,)).cpu().numpy()
@@ -89,23 +88,22 @@ ADV_LAYOUTS = [  # (name, n, ih, iw, bits, half_width, shift, rotated file)
 ]
 
 
-@pytest.mark.parametrize('levels', bx.LEVEL_SETS, ids=['K%d' % len(s) for s in bx.LEVEL_SETS])
+@pytest.mark.parametrize('levels', adv.LEVEL_SETS, ids=['K%d' % len(s) for s in adv.LEVEL_SETS])
 @pytest.mark.parametrize('layout', ADV_LAYOUTS, ids=[c[0] for c in ADV_LAYOUTS])
 def test_adversarial_rows_against_the_exact_reference(mods, layout, levels):
     _, ops, _ = mods
     name, n, ih, iw, bits, hw, shift, rot = layout
-    P, fit, _ = bx.profiles(n, ih, iw, bits, hw, levels, shift, seed=5)
+    P, fit, _ = adv.level_profiles(n, ih, iw, bits, hw, levels, shift, seed=5)
     raw = adv.to_file(P, bits, rot)
-    t = torch.from_numpy(raw.view(np.int16) if bits == 16 else raw).cuda().view(torch.uint16 if bits == 16 else torch.uint8)
-    got = ops.line_bisector(t, fit, hw, levels, shift).cpu().numpy()
+    got = ops.line_bisector(upload(ops, raw, bits), fit, hw, levels, shift).cpu().numpy()
     same_bits(got, ref.line_bisector(raw, fit, hw, levels, shift))
-    recs = bx.records(P, fit, hw, levels, shift)
+    recs = ex.records(P, fit, hw, shift, levels)
     skip = {(y, k) for y, row in enumerate(recs) for k, r in enumerate(row or ())
-            if any(exact != f64 for exact, f64, _, _ in bx.level_decisions(r))}
+            if any(exact != f64 for exact, f64, _, _ in ex.level_decisions(r))}
     kk = len(levels)
     for i in range(kk):
-        bx.within(got[i], recs, i, 'bis', shift, skip)
-        bx.within(got[kk + i], recs, i, 'chord', shift, skip)
+        ex.within(got[i], recs, *ex.level(i, 'bis'), skip)
+        ex.within(got[kk + i], recs, *ex.level(i, 'chord'), skip)
 
 
 def test_refused_arguments_write_nothing(mods):
@@ -162,19 +160,19 @@ def test_finish_matches_doppler_finish_and_the_restatement(mods, phi, ratio, shi
 
 
 # ---- line_bisector_maps() on the synthetic scans ----
-@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE))
+@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE['bisector']))
 @pytest.mark.parametrize('kind', ('symmetric', 'asymmetric'))
 def test_maps_recover_the_bisectors(mods, kind, noise):
     bisector, _, _ = mods
-    frames, centre, on, truth = ref.scan(kind, IH, N, IW, noise)
+    frames, centre, on, truth = ref.bisector_scan(kind, IH, N, IW, noise)
     levels = ref.LEVELS
     res = bisector.line_bisector_maps(scan_reader(frames), levels=levels)
     kk = len(levels)
     raw = np.stack([res['raw']['bisector', f] for f in levels] + [res['raw']['chord', f] for f in levels])
     same_bits(raw, ref.line_bisector(frames, res['fit'], 10, levels))
-    got = ref.errors(raw[:kk], truth(res['fit'], 10, levels), on)
+    got = ref.bisector_errors(raw[:kk], truth(res['fit'], 10, levels), on)
     print('%s noise %g: %s' % (kind, noise, got))
-    rms_tol, max_tol = ref.TOLERANCE[noise][kind]
+    rms_tol, max_tol = ref.TOLERANCE['bisector'][noise][kind]
     for i, (rms, mx, nans) in got.items():
         assert nans == 0 and rms <= rms_tol and mx <= max_tol, (levels[i], rms, mx)
     from solex_ser_recon_en_amd.ellipse_to_circle import _warp_geometry
@@ -192,22 +190,11 @@ def test_maps_recover_the_bisectors(mods, kind, noise):
 
 
 # ---- the command line, and the overlay on the products ----
-def run_json(main, capsys, argv):
-    capsys.readouterr()
-    assert main(argv) == 0
-    out = capsys.readouterr().out.strip().splitlines()
-    return json.loads(out[-1])
-
-
 @pytest.fixture(scope='module')
 def scan_file(tmp_path_factory):
     if not torch.cuda.is_available():
         pytest.skip('no GPU')
-    from solex_ser_recon_en_amd import synth
-    frames, _, _, _, _ = ref.asym_scan(IH, N, IW, noise=0.004, seed=4)
-    path = tmp_path_factory.mktemp('bisector') / 'scan.ser'
-    synth.write_ser(str(path), frames)
-    return str(path)
+    return write_scan(tmp_path_factory, 'bisector', ref.bisector_scan('asymmetric', IH, N, IW, noise=0.004, seed=4)[0])
 
 
 def test_cli_end_to_end(mods, scan_file, capsys):
@@ -243,13 +230,12 @@ FLAGS = [('m', ['-m'], 0), ('s', ['-s'], 0), ('r', ['-r', '300'], 0), ('x', ['-x
 
 @pytest.mark.parametrize('flags, rotate', [f[1:] for f in FLAGS], ids=[f[0] for f in FLAGS])
 def test_bisector_maps_overlay_the_line_cog(mods, tmp_path, capsys, monkeypatch, flags, rotate):
-    """test_overlay_gpu's marked scan (a bright patch 2 px to the red): the patch lies on the same pixels of _bisector_50.fits and
+    """The overlay tests' marked scan (a bright patch 2 px to the red): the patch lies on the same pixels of _bisector_50.fits and
     _line_cog.fits, and the maps have the products' shape."""
     bisector, _, synth = mods
     from solex_ser_recon_en_amd import SHG_MAIN, lineprofile, outputs
     from solex_ser_recon_en_amd.fits_io import read_fits_f32
     from solex_ser_recon_en_amd.png_io import read_png_gray
-    from tests.test_overlay_gpu import SHIFT, marked_scan, same_region
     defaults = SHG_MAIN.default_options
     monkeypatch.setattr(SHG_MAIN, 'default_options', lambda: dict(defaults(), img_rotate=rotate))
     src = tmp_path / 'marked.ser'

@@ -1,42 +1,18 @@
-"""The Dopplergram without a GPU: the NumPy restatement (tests/doppler_ref.py) on hand-built profiles, its recovery of an injected
+"""The Dopplergram without a GPU: the NumPy restatement (tests/linemaps_ref.py) on hand-built profiles, its recovery of an injected
 velocity field (the tolerance the GPU tests hold dopplergram() to), the float32 FITS writer, and the CLI's argument errors."""
 import hashlib
 
 import numpy as np
 import pytest
 
-from tests import doppler_ref as ref
-
-
-def one_row_scan(profiles_yk, rotate=True):
-    """frames [n, H, W] (file layout) whose slit row y of frame k is profiles_yk[y, k] (uint16 [rows, n, iw]).  The slit axis is the
-    longer one (a1 rotates when W > H): rows beyond those given repeat the last one, up to iw + 1."""
-    rows, n, iw = profiles_yk.shape
-    ih = max(rows, iw + 1)
-    prof = np.concatenate([profiles_yk, np.repeat(profiles_yk[-1:], ih - rows, axis=0)])
-    img = np.transpose(prof, (1, 0, 2))                         # [n, ih, iw]
-    if rotate:
-        return np.ascontiguousarray(np.rot90(img, -1, axes=(1, 2)))   # img[y, x] = raw[x, W - 1 - y]
-    return np.ascontiguousarray(img)
-
-
-def fit_at(centre, ih=None):
-    """fit [ih, 4] of a line at centre[y] (the last value repeated up to ih rows)."""
-    centre = np.asarray(centre, dtype=np.float64)
-    if ih is not None and ih > centre.shape[0]:
-        centre = np.concatenate([centre, np.repeat(centre[-1:], ih - centre.shape[0])])
-    return np.stack([np.floor(centre), centre - np.floor(centre), np.arange(centre.shape[0], dtype=np.float64), centre], axis=1)
+from tests import linemaps_ref as ref
+from tests.linemaps_util import fit_at, one_row_scan, parabola
 
 
 def shifts(frames, centre, half_width=5, **kw):
     """the restatement on a one_row_scan, the rows given only"""
     ih = max(frames.shape[1:])
     return ref.line_core_shift(frames, fit_at(centre, ih), half_width, **kw)[:len(centre)]
-
-
-def parabola(iw, quad, lin, const):
-    j = np.arange(iw, dtype=np.int64)
-    return (quad * j * j + lin * j + const).astype(np.uint16)
 
 
 def test_rotation_and_samples():
@@ -75,12 +51,12 @@ def test_minimum_on_the_window_edge_is_nan():
 
 
 def test_windows_clip_at_columns_1_and_iw_minus_2():
-    assert ref.window(0.3, 5, 40) == (1, 5)
-    assert ref.window(37.9, 5, 40) == (32, 38)
-    assert ref.window(-0.5, 5, 40) == (1, 5)                    # truncation toward zero, as astype(int)
-    assert ref.window(-3.0, 5, 40) is None                      # hi - lo = 1
-    assert ref.window(43.0, 5, 40) is None
-    assert ref.window(20.0, 1, 40) == (19, 21)
+    assert ref.window(0.3, 0, 5, 40) == (1, 5)
+    assert ref.window(37.9, 0, 5, 40) == (32, 38)
+    assert ref.window(-0.5, 0, 5, 40) == (1, 5)                 # truncation toward zero, as astype(int)
+    assert ref.window(-3.0, 0, 5, 40) is None                   # hi - lo = 1
+    assert ref.window(43.0, 0, 5, 40) is None
+    assert ref.window(20.0, 0, 1, 40) == (19, 21)
     # a deeper minimum at column 0 is outside the window [1, 5]: the vertex at 3 is found
     p = parabola(40, 10, -60, 200)
     p[0] = 0
@@ -111,18 +87,18 @@ def test_flip_x_and_sharded_column_order():
     assert np.array_equal(shard[1:6], plain[::-1]) and np.isnan(shard[[0, 6, 7, 8]]).all()
 
 
-@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE))
+@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE['doppler']))
 def test_restatement_recovers_an_injected_field(noise):
     ih, n, iw = 400, 300, 48
-    rms_tol, max_tol = ref.TOLERANCE[noise]
+    rms_tol, max_tol = ref.TOLERANCE['doppler'][noise]
     field = ref.injected_field(ih, n)
-    frames, centre, on = ref.disk_scan(field, iw, noise=noise, seed=3)
+    frames, centre, on = ref.doppler_scan(field, iw, noise=noise, seed=3)
     got = ref.line_core_shift(frames, fit_at(centre), 5)
     err = (got.astype(np.float64) - field)[on]
     rms, mx = float(np.sqrt(np.mean(err * err))), float(np.abs(err).max())
     print('noise %g: RMS %.4f, max %.4f px over %d disk samples' % (noise, rms, mx, err.size))
     assert not np.isnan(err).any() and rms <= rms_tol and mx <= max_tol
-    frames0, _, _ = ref.disk_scan(np.zeros_like(field), iw, noise=noise, seed=3)
+    frames0, _, _ = ref.doppler_scan(np.zeros_like(field), iw, noise=noise, seed=3)
     assert abs(float(np.median(ref.line_core_shift(frames0, fit_at(centre), 5)[on]))) <= rms_tol
 
 

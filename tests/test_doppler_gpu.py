@@ -1,20 +1,15 @@
 """The Dopplergram on the GPU: shg_line_core_shift and shg_doppler_finish bit for bit against the NumPy restatement
-(tests/doppler_ref.py), dopplergram() recovering an injected velocity field within what the restatement achieves
-(doppler_ref.TOLERANCE), and the CLI end to end: FITS, PNG, geometry, the products' shape, --atlas."""
-import json
-import os
-
+(tests/linemaps_ref.py), dopplergram() recovering an injected velocity field within what the restatement achieves
+(linemaps_ref.TOLERANCE['doppler']), and the CLI end to end: FITS, PNG, geometry, the products' shape, --atlas."""
 import numpy as np
 import pytest
 
-from tests import doppler_ref as ref
-from tests.test_spectral_gpu import atlas_npz, atlas_scan, core_wavelength  # noqa: F401  -- the g17-style atlas scan and its fixtures
+from tests import linemaps_ref as ref
+from tests.linemaps_util import CASES, IH, IW, N, finish_cases, fit_for, run_json, same_bits, scan_reader, upload, write_scan
+from tests.spectral_util import ATLAS, atlas_npz, atlas_scan, core_wavelength  # noqa: F401  -- the g17-style atlas scan and its fixtures
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-ATLAS = os.path.join(GOLDEN, 'alps.npz')
 
 
 @pytest.fixture(scope='module')
@@ -25,50 +20,6 @@ def mods():
     return doppler, ops, synth
 
 
-def same_bits(got, want):
-    got, want = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
-    assert got.shape == want.shape
-    assert np.array_equal(np.isnan(got), np.isnan(want)), 'NaN positions differ (%d vs %d)' % (np.isnan(got).sum(), np.isnan(want).sum())
-    g, w = got.view(np.uint32).copy(), want.view(np.uint32).copy()
-    g[np.isnan(got)] = w[np.isnan(want)] = 0          # (NaN payloads are not part of the contract)
-    bad = np.flatnonzero(g != w)
-    assert bad.size == 0, '%d values differ, first at %s: %r vs %r' % (bad.size, np.unravel_index(bad[0], got.shape),
-                                                                      got.flat[bad[0]], want.flat[bad[0]])
-
-
-def fit_for(synth, ih, iw, seed, jitter=3.0, edges=True, nans=True):
-    """A fit [ih, 4] around synth's line: per-row jitter (minima land on window edges too), rows whose line is within H of both
-    frame edges, and non-finite rows."""
-    rng = np.random.default_rng(seed)
-    centre = synth.curve_of_row(np.arange(ih, dtype=np.float64), ih, iw) + rng.uniform(-jitter, jitter, ih)
-    if edges:
-        centre[0:ih:11] = rng.uniform(-1.5, 4.0, centre[0:ih:11].shape)
-        centre[5:ih:13] = rng.uniform(iw - 5.0, iw + 1.5, centre[5:ih:13].shape)
-    fit = np.stack([np.floor(centre), centre - np.floor(centre), np.arange(ih, dtype=np.float64), centre], axis=1)
-    if nans:
-        fit[3, 0], fit[7, 0], fit[9, 3] = np.nan, np.inf, np.nan
-    return fit
-
-
-CASES = [  # (name, n, width, height, bits, half_width, flip_x, sharded, pitched)
-    ('rot_u16', 37, 300, 40, 16, 5, False, False, False),
-    ('rot_u8', 37, 304, 40, 8, 5, False, False, False),
-    ('plain_u16', 37, 40, 300, 16, 5, False, False, False),
-    ('plain_u8', 37, 40, 300, 8, 5, False, False, False),
-    ('flip', 37, 304, 40, 16, 5, True, False, False),
-    ('sharded', 37, 304, 40, 16, 5, False, True, False),
-    ('sharded_flip', 37, 304, 40, 8, 5, True, True, False),
-    ('h1', 20, 304, 40, 16, 1, False, False, False),
-    ('h32', 20, 600, 80, 16, 32, False, False, False),
-    ('h32_plain', 20, 80, 600, 16, 32, True, False, False),
-    ('n1', 1, 304, 40, 16, 5, False, False, False),
-    ('odd_ih', 37, 301, 40, 16, 5, False, False, False),
-    ('odd_ih_u8', 37, 517, 40, 8, 7, True, False, False),
-    ('pitched', 37, 304, 40, 16, 5, False, False, True),
-    ('pitched_u8_odd', 37, 301, 41, 8, 5, False, False, True),
-]
-
-
 @pytest.mark.parametrize('case', CASES, ids=[c[0] for c in CASES])
 def test_line_core_shift_bit_exact(mods, case):
     _, ops, synth = mods
@@ -76,12 +27,7 @@ def test_line_core_shift_bit_exact(mods, case):
     frames = synth.synth_frames_numpy(n, width, height, bits, seed=11, tilt=0.01, curv=2e-5)
     ih, iw = max(width, height), min(width, height)
     fit = fit_for(synth, ih, iw, seed=len(name))
-    if pitched:
-        stack = ops.padded_stack(n, height, width, torch.uint8 if bits == 8 else torch.uint16, 'cuda')
-        stack.copy_(torch.from_numpy(frames.view(np.int16) if bits == 16 else frames).view(stack.dtype).cuda())
-        assert stack.stride(0) > height * width
-    else:
-        stack = torch.from_numpy(frames.view(np.int16) if bits == 16 else frames).cuda().view(torch.uint16 if bits == 16 else torch.uint8)
+    stack = upload(ops, frames, bits, pitched)
     n_cols, k_offset = (n + 9, 4) if sharded else (n, 0)
     got = ops.line_core_shift(stack, fit, hw, flip_x=flip, n_cols=n_cols, k_offset=k_offset)
     want = ref.line_core_shift(frames, fit, hw, flip_x=flip, n_cols=n_cols, k_offset=k_offset)
@@ -113,16 +59,6 @@ def test_unsupported_arguments(mods):
         ops.line_core_shift(stack, np.zeros((40, 4)), 5)
 
 
-def finish_cases():
-    from solex_ser_recon_en_amd import SHG_MAIN
-    base = SHG_MAIN.default_options()
-    return [('none', None, dict(base)), ('square', None, dict(base, crop_width_square=True)),
-            ('wide', None, dict(base, fixed_width=700)), ('narrow', None, dict(base, fixed_width=120)),
-            ('circle', (250.3, 199.6, 150.2), dict(base)), ('circle_square', (250.3, 199.6, 150.2), dict(base, crop_width_square=True)),
-            ('circle_wide', (250.3, 199.6, 150.2), dict(base, fixed_width=701)), ('circle_narrow', (250.3, 199.6, 150.2), dict(base, fixed_width=121)),
-            ('no_circle', (-1, -1, -1), dict(base, fixed_width=300))]
-
-
 @pytest.mark.parametrize('phi, ratio, shift', [(0.0, 1.0, 0.0), (0.12, 1.07, 0.0), (-0.3, 0.91, 0.0), (0.05, 1.2, 37.5), (0.0, 1.0, -90.25)])
 def test_doppler_finish_bit_exact(mods, phi, ratio, shift):
     _, ops, _ = mods
@@ -148,20 +84,12 @@ def test_doppler_finish_bit_exact(mods, phi, ratio, shift):
 
 
 # ---- dopplergram() on a scan with a known velocity field ----
-IH, N, IW = 400, 300, 48
-
-
-def scan_reader(frames):
-    from solex_ser_recon_en_amd.video_reader import array_reader
-    return array_reader(torch.from_numpy(frames.view(np.int16)).cuda().view(torch.uint16))
-
-
-@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE))
+@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE['doppler']))
 def test_dopplergram_recovers_an_injected_field(mods, noise):
     doppler, _, _ = mods
-    rms_tol, max_tol = ref.TOLERANCE[noise]
+    rms_tol, max_tol = ref.TOLERANCE['doppler'][noise]
     field = ref.injected_field(IH, N)
-    frames, centre, on = ref.disk_scan(field, IW, noise=noise, seed=3)
+    frames, centre, on = ref.doppler_scan(field, IW, noise=noise, seed=3)
     res = doppler.dopplergram(scan_reader(frames))
     same_bits(res['raw'], ref.line_core_shift(frames, res['fit'], 5))
     # the shift is relative to the scan's own fitted line: compare where the line core is
@@ -181,32 +109,20 @@ def test_dopplergram_recovers_an_injected_field(mods, noise):
     same_bits(kms['map'], (want.astype(np.float64) * ((0.05 / 6562.8) * ref.C_KM_S)).astype(np.float32))
 
 
-@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE))
+@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE['doppler']))
 def test_dopplergram_of_a_still_scan(mods, noise):
     doppler, _, _ = mods
-    frames, _, _ = ref.disk_scan(np.zeros((IH, N)), IW, noise=noise, seed=3)
+    frames, _, _ = ref.doppler_scan(np.zeros((IH, N)), IW, noise=noise, seed=3)
     res = doppler.dopplergram(scan_reader(frames))
     stats = doppler.disk_stats(res)
     print('noise %g: %s' % (noise, stats))
-    assert stats['valid_fraction'] > 0.95 and abs(stats['median']) <= ref.TOLERANCE[noise][0]
+    assert stats['valid_fraction'] > 0.95 and abs(stats['median']) <= ref.TOLERANCE['doppler'][noise][0]
 
 
 # ---- the command line ----
 @pytest.fixture(scope='module')
 def scan_file(tmp_path_factory):
-    from solex_ser_recon_en_amd import synth
-    frames, _, _ = ref.disk_scan(ref.injected_field(IH, N), IW, noise=0.004, seed=4)
-    path = tmp_path_factory.mktemp('doppler') / 'scan.ser'
-    synth.write_ser(str(path), frames)
-    return str(path)
-
-
-def run_cli(doppler, capsys, argv):
-    capsys.readouterr()
-    assert doppler.main(argv) == 0
-    out = capsys.readouterr().out.strip().splitlines()
-    assert len(out) == 1, out
-    return json.loads(out[0])
+    return write_scan(tmp_path_factory, 'doppler', ref.doppler_scan(ref.injected_field(IH, N), IW, noise=0.004, seed=4)[0])
 
 
 def test_cli_end_to_end(mods, scan_file, capsys):
@@ -219,7 +135,7 @@ def test_cli_end_to_end(mods, scan_file, capsys):
     from solex_ser_recon_en_amd.solex_util import compute_mean_return_fit, extract_disks
     from solex_ser_recon_en_amd.fits_io import make_header
     from solex_ser_recon_en_amd.video_reader import video_reader
-    got = run_cli(doppler, capsys, [scan_file, '--range', '1.5', '--half-width', '6'])
+    got = run_json(doppler.main, capsys, [scan_file, '--range', '1.5', '--half-width', '6'])
     res = doppler.dopplergram(scan_file, half_width=6, display_range=1.5)
     m, cards = read_fits_f32(got['fits'])
     same_bits(m, res['map'])
@@ -250,7 +166,7 @@ def test_cli_map_has_the_products_shape(mods, scan_file, capsys, tmp_path, flags
     b.mkdir()
     shutil.copy(scan_file, a / 'scan.ser')
     shutil.copy(scan_file, b / 'scan.ser')
-    got = run_cli(doppler, capsys, [str(a / 'scan.ser')] + flags)
+    got = run_json(doppler.main, capsys, [str(a / 'scan.ser')] + flags)
     assert SHG_MAIN.main(['-c'] + flags + [str(b / 'scan.ser')]) == 0
     outputs.flush()
     clahe = read_png_gray(str(b / 'scan_shift=0_clahe.png'))
@@ -263,7 +179,7 @@ def test_cli_atlas_gives_the_analysers_dispersion(mods, atlas_npz, atlas_scan, c
     doppler, _, _ = mods
     from solex_ser_recon_en_amd import spectral
     path, anchor = atlas_scan, core_wavelength(atlas_npz)
-    got = run_cli(doppler, capsys, [path, '--atlas', ATLAS, '--anchor', repr(anchor)])
+    got = run_json(doppler.main, capsys, [path, '--atlas', ATLAS, '--anchor', repr(anchor)])
     a = spectral.analyse(path)
     want = spectral.auto_dispersion(a['spectrum2'], a['anchor_x'], anchor, spectral.load_atlas(ATLAS))[0]
     assert got['dispersion'] == want and got['wavelength'] == anchor and got['units'] == 'km/s'

@@ -1,4 +1,4 @@
-"""The NumPy restatements of the finish (doppler_ref.doppler_finish, lineprofile_ref.line_profile_finish) held bit for bit to the
+"""The NumPy restatement of the finish (linemaps_ref.doppler_finish, linemaps_ref.line_profile_finish) held bit for bit to the
 exact reference written from the header (tests/finish_exact.py) on the adversarial geometries of tests/finish_adversarial.py, every
 decision class reached; and the number of pixels where the header's float64 circle test decides otherwise than the exact one."""
 from collections import Counter
@@ -6,9 +6,9 @@ from collections import Counter
 import numpy as np
 import pytest
 
-from tests import doppler_ref, lineprofile_ref
 from tests import finish_adversarial as adv
 from tests import finish_exact as ex
+from tests import linemaps_ref as ref
 
 # Pixels of the adversarial set (P = 1 and P = 5 alike: the mask does not depend on the planes) where the float64 compare
 # (c - cx)^2 + (r - cy)^2 > rad^2 keeps a pixel whose exact distance exceeds the exact radius, or the other way round.  The header
@@ -25,11 +25,11 @@ def run_exact(case):
 def restatement(case, P):
     h00, h01, h02, out_h, out_w = case['geometry']
     if P == 1:
-        m, png = doppler_ref.doppler_finish(case['raw'][0], h00, h01, h02, out_h, out_w, case['circle'], case['crop'],
-                                            case['display_range'])
+        m, png = ref.doppler_finish(case['raw'][0], h00, h01, h02, out_h, out_w, case['circle'], case['crop'],
+                                    case['display_range'])
         return m[None], png[None]
-    return lineprofile_ref.line_profile_finish(case['raw'], h00, h01, h02, out_h, out_w, case['circle'], case['crop'],
-                                               case['half_width'], case['display_range'])
+    return ref.line_profile_finish(case['raw'], h00, h01, h02, out_h, out_w, case['circle'], case['crop'],
+                                   case['half_width'], case['display_range'])
 
 
 @pytest.mark.parametrize('P', [1, 5])

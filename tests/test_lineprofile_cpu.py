@@ -1,11 +1,11 @@
-"""The line-profile maps without a GPU: the NumPy restatement (tests/lineprofile_ref.py) on hand-built profiles, one plane and one
+"""The line-profile maps without a GPU: the NumPy restatement (tests/linemaps_ref.py) on hand-built profiles, one plane and one
 NaN rule at a time, its accuracy on a scan with injected fields (the tolerance the GPU tests hold line_profile_maps() to), the
 display planes, and the CLI's argument errors."""
 import numpy as np
 import pytest
 
-from tests import lineprofile_ref as ref
-from tests.test_doppler_cpu import fit_at, one_row_scan, parabola
+from tests import linemaps_ref as ref
+from tests.linemaps_util import fit_at, one_row_scan, parabola
 
 IW = 40
 
@@ -134,28 +134,27 @@ def test_windows_with_a_shift_clip_at_the_edges(shift, window):
 
 
 def test_shift_plane_at_zero_is_the_dopplergram():
-    from tests import doppler_ref
     from solex_ser_recon_en_amd import synth
     frames = synth.synth_frames_numpy(9, 120, 30, 16, seed=3, tilt=0.01, curv=2e-5)
     centre = synth.curve_of_row(np.arange(120, dtype=np.float64), 120, 30) + np.random.default_rng(1).uniform(-3, 3, 120)
     fit = fit_at(centre)
     for hw in (1, 5, 12):
         got = ref.line_profile(frames, fit, hw)[0]
-        want = doppler_ref.line_core_shift(frames, fit, hw)
+        want = ref.line_core_shift(frames, fit, hw)
         assert np.array_equal(got.view(np.uint32)[~np.isnan(got)], want.view(np.uint32)[~np.isnan(want)])
         assert np.array_equal(np.isnan(got), np.isnan(want))
 
 
-@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE))
+@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE['profile']))
 def test_restatement_recovers_injected_fields(noise):
     ih, n, iw = 400, 300, 48
     shift, sigma, depth = ref.injected_fields(ih, n)
-    frames, centre, on, core = ref.disk_scan(shift, sigma, depth, iw, noise=noise, seed=3)
+    frames, centre, on, core = ref.profile_scan(shift, sigma, depth, iw, noise=noise, seed=3)
     for d in ref.FIT_OFFSETS:
         fit = fit_at(centre + d)
-        got = ref.errors(ref.line_profile(frames, fit, 10), fit, shift, sigma, depth, centre, core, on)
+        got = ref.profile_errors(ref.line_profile(frames, fit, 10), fit, shift, sigma, depth, centre, core, on)
         print('noise %g, fit %+g px: %s' % (noise, d, got))
-        for name, (rms_tol, max_tol) in ref.TOLERANCE[noise].items():
+        for name, (rms_tol, max_tol) in ref.TOLERANCE['profile'][noise].items():
             rms, mx, nans = got[name]
             assert nans == 0 and rms <= rms_tol and mx <= max_tol, name
 

@@ -1,21 +1,17 @@
 """The line-profile maps on the GPU: shg_line_profile and shg_line_profile_finish bit for bit against the NumPy restatement
-(tests/lineprofile_ref.py) and against the Dopplergram's kernels where they overlap, line_profile_maps() recovering injected line
-shift, width and depth within what the restatement achieves (lineprofile_ref.TOLERANCE), and the CLI end to end."""
-import json
+(tests/linemaps_ref.py) and against the Dopplergram's kernels where they overlap, line_profile_maps() recovering injected line
+shift, width and depth within what the restatement achieves (linemaps_ref.TOLERANCE['profile']), and the CLI end to end."""
 import os
 
 import numpy as np
 import pytest
 
-from tests import lineprofile_ref as ref
-from tests.test_doppler_gpu import CASES, IH, IW, N, fit_for, finish_cases, same_bits, scan_reader
-from tests.test_spectral_gpu import atlas_npz, atlas_scan, core_wavelength  # noqa: F401  -- the g17-style atlas scan and its fixtures
+from tests import linemaps_ref as ref
+from tests.linemaps_util import IH, IW, N, SHIFT_CASES, finish_cases, fit_for, run_json, same_bits, scan_reader, upload, write_scan
+from tests.spectral_util import ATLAS, atlas_npz, atlas_scan, core_wavelength  # noqa: F401  -- the g17-style atlas scan and its fixtures
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-ATLAS = os.path.join(GOLDEN, 'alps.npz')
 
 
 @pytest.fixture(scope='module')
@@ -26,24 +22,6 @@ def mods():
     return lineprofile, ops, synth
 
 
-def stack_of(ops, frames, bits, pitched):
-    if pitched:
-        stack = ops.padded_stack(*frames.shape, torch.uint8 if bits == 8 else torch.uint16, 'cuda')
-        stack.copy_(torch.from_numpy(frames.view(np.int16) if bits == 16 else frames).view(stack.dtype).cuda())
-        assert stack.stride(0) > frames.shape[1] * frames.shape[2]
-        return stack
-    return torch.from_numpy(frames.view(np.int16) if bits == 16 else frames).cuda().view(torch.uint16 if bits == 16 else torch.uint8)
-
-
-# the Dopplergram's cases at S = 0, plus shifts whose windows clip at either edge of the frame
-SHIFT_CASES = [c + (0,) for c in CASES] + [
-    ('s_minus', 37, 304, 40, 16, 5, False, False, False, -14),
-    ('s_plus', 37, 304, 40, 16, 5, True, False, False, 15),
-    ('s_plus_u8_plain', 37, 40, 300, 8, 7, False, False, False, 13),
-    ('s_minus_h32', 20, 600, 80, 16, 32, False, True, True, -30),
-]
-
-
 @pytest.mark.parametrize('case', SHIFT_CASES, ids=['%s_s%d' % (c[0], c[-1]) for c in SHIFT_CASES])
 def test_line_profile_bit_exact(mods, case):
     _, ops, synth = mods
@@ -51,7 +29,7 @@ def test_line_profile_bit_exact(mods, case):
     frames = synth.synth_frames_numpy(n, width, height, bits, seed=11, tilt=0.01, curv=2e-5)
     ih, iw = max(width, height), min(width, height)
     fit = fit_for(synth, ih, iw, seed=len(name))
-    stack = stack_of(ops, frames, bits, pitched)
+    stack = upload(ops, frames, bits, pitched)
     n_cols, k_offset = (n + 9, 4) if sharded else (n, 0)
     got = ops.line_profile(stack, fit, hw, shift, flip_x=flip, n_cols=n_cols, k_offset=k_offset).cpu().numpy()
     want = ref.line_profile(frames, fit, hw, shift, flip_x=flip, n_cols=n_cols, k_offset=k_offset)
@@ -123,20 +101,20 @@ def test_finish_matches_doppler_finish_and_the_restatement(mods, phi, ratio, shi
 
 
 # ---- line_profile_maps() on a scan with known fields ----
-@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE))
+@pytest.mark.parametrize('noise', sorted(ref.TOLERANCE['profile']))
 def test_maps_recover_injected_fields(mods, noise):
     lineprofile, _, _ = mods
     shift, sigma, depth = ref.injected_fields(IH, N)
-    frames, centre, on, core = ref.disk_scan(shift, sigma, depth, IW, noise=noise, seed=3)
+    frames, centre, on, core = ref.profile_scan(shift, sigma, depth, IW, noise=noise, seed=3)
     res = lineprofile.line_profile_maps(scan_reader(frames))
     raw = np.stack([res['raw'][p] for p in ref.PLANES])
     want = ref.line_profile(frames, res['fit'], 10)
     for q in range(5):
         same_bits(raw[q], want[q])
     # against the truth: the scan's own fitted line, not the exact centre, is the reference position
-    got = ref.errors(raw, res['fit'], shift, sigma, depth, centre, core, on)
+    got = ref.profile_errors(raw, res['fit'], shift, sigma, depth, centre, core, on)
     print('noise %g: %s; circle %s' % (noise, got, res['circle']))
-    for name, (rms_tol, max_tol) in ref.TOLERANCE[noise].items():
+    for name, (rms_tol, max_tol) in ref.TOLERANCE['profile'][noise].items():
         rms, mx, nans = got[name]
         assert nans == 0 and rms <= rms_tol and mx <= max_tol, name
     from solex_ser_recon_en_amd.ellipse_to_circle import _warp_geometry
@@ -155,7 +133,7 @@ def test_maps_recover_injected_fields(mods, noise):
 def test_maps_of_a_shifted_line_keep_the_geometry(mods):
     lineprofile, _, _ = mods
     shift, sigma, depth = ref.injected_fields(IH, N)
-    frames, _, _, _ = ref.disk_scan(shift, sigma, depth, IW, noise=0.004, seed=3)
+    frames, _, _, _ = ref.profile_scan(shift, sigma, depth, IW, noise=0.004, seed=3)
     base = lineprofile.line_profile_maps(scan_reader(frames), half_width=4)
     moved = lineprofile.line_profile_maps(scan_reader(frames), half_width=4, shift=-15)
     assert moved['circle'] == base['circle'] and moved['ratio'] == base['ratio'] and moved['shift'] == -15
@@ -169,26 +147,14 @@ def test_maps_of_a_shifted_line_keep_the_geometry(mods):
 # ---- the command line ----
 @pytest.fixture(scope='module')
 def scan_file(tmp_path_factory):
-    from solex_ser_recon_en_amd import synth
-    frames, _, _, _ = ref.disk_scan(*ref.injected_fields(IH, N), IW, noise=0.004, seed=4)
-    path = tmp_path_factory.mktemp('lineprofile') / 'scan.ser'
-    synth.write_ser(str(path), frames)
-    return str(path)
-
-
-def run_cli(lineprofile, capsys, argv):
-    capsys.readouterr()
-    assert lineprofile.main(argv) == 0
-    out = capsys.readouterr().out.strip().splitlines()
-    assert len(out) == 1, out
-    return json.loads(out[0])
+    return write_scan(tmp_path_factory, 'lineprofile', ref.profile_scan(*ref.injected_fields(IH, N), IW, noise=0.004, seed=4)[0])
 
 
 def test_cli_end_to_end(mods, scan_file, capsys):
     lineprofile, _, _ = mods
     from solex_ser_recon_en_amd.fits_io import read_fits_f32
     from solex_ser_recon_en_amd.png_io import read_png_gray
-    got = run_cli(lineprofile, capsys, [scan_file, '--half-width', '8', '--shift', '2', '--range', '1.5'])
+    got = run_json(lineprofile.main, capsys, [scan_file, '--half-width', '8', '--shift', '2', '--range', '1.5'])
     res = lineprofile.line_profile_maps(scan_file, half_width=8, shift=2, display_range=1.5)
     assert sorted(got['fits']) == sorted(lineprofile.WRITTEN) and got['shift'] == 2
     base = os.path.splitext(scan_file)[0]
@@ -214,7 +180,7 @@ def test_cli_maps_have_the_products_shape(mods, scan_file, capsys, tmp_path, fla
     b.mkdir()
     shutil.copy(scan_file, a / 'scan.ser')
     shutil.copy(scan_file, b / 'scan.ser')
-    got = run_cli(lineprofile, capsys, [str(a / 'scan.ser')] + flags)
+    got = run_json(lineprofile.main, capsys, [str(a / 'scan.ser')] + flags)
     assert SHG_MAIN.main(['-c'] + flags + [str(b / 'scan.ser')]) == 0
     outputs.flush()
     clahe = read_png_gray(str(b / 'scan_shift=0_clahe.png'))
@@ -231,6 +197,6 @@ def test_cli_line_takes_the_analysers_shift(mods, atlas_npz, atlas_scan, capsys)
     disp = spectral.auto_dispersion(a['spectrum2'], a['anchor_x'], anchor, spectral.load_atlas(ATLAS))[0]
     line = anchor + 9.0 * disp
     want, _ = spectral.shift_for_wavelength(line, anchor, disp, a['fit'], int(video_reader(path).iw))
-    got = run_cli(lineprofile, capsys, [path, '--atlas', ATLAS, '--anchor', repr(anchor), '--line', repr(line), '--half-width', '3'])
+    got = run_json(lineprofile.main, capsys, [path, '--atlas', ATLAS, '--anchor', repr(anchor), '--line', repr(line), '--half-width', '3'])
     assert got['shift'] == want != 0 and got['dispersion'] == disp and got['wavelength'] == line
     assert got['units']['cog'] == 'km/s' and got['fits']['ew'].endswith('_shift=%d_line_ew.fits' % want)

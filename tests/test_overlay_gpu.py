@@ -3,72 +3,22 @@ every flag that moves, mirrors, turns, crops or masks the image: a scan whose fr
 and carry the line 2 px to the red is run through SHG_MAIN and both command lines; that patch must sit on the same pixels of
 `_shift=0_uncontrasted.png`, `_doppler.fits` and `_shift=0_line_cog.fits` (up to a one-pixel border), the maps' NaN must be the
 products' circle (crop_plan's circle_out) and crop in the written orientation, and the maps' geometry the products'."""
-import json
 import shutil
 
 import numpy as np
 import pytest
 
+from tests.linemaps_util import IH, N, SHIFT, marked_scan, run_json, same_region, write_scan
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
-
-IH, N, IW = 400, 300, 48
-K0, K1, Y0, Y1 = 70, 100, 120, 200          # the marker: frames [K0, K1) x slit rows [Y0, Y1), off-centre both ways
-SHIFT, GAIN = 2.0, 1.25
-
-
-def marked_scan():
-    """doppler_ref.disk_scan's scene without noise, the marker's continuum GAIN times brighter and its line SHIFT px to the red."""
-    from solex_ser_recon_en_amd import synth
-    sp = synth.scene_params(N, IH, IW)
-    y = np.arange(IH, dtype=np.float64)
-    x = np.arange(IW, dtype=np.float64)
-    centre = synth.curve_of_row(y, IH, IW)
-    lit = ((y > sp['y_lo']) & (y < sp['y_hi'])).astype(np.float64)
-    mark = (y >= Y0) & (y < Y1)
-    frames = np.empty((N, IW, IH), dtype=np.uint16)
-    for k in range(N):
-        on = mark & (K0 <= k < K1)
-        r2 = ((k - sp['cx']) / sp['ax']) ** 2 + ((y - sp['cy']) / sp['ay']) ** 2
-        bright = np.where(r2 < 1.0, 0.35 + 0.65 * np.sqrt(np.clip(1.0 - r2, 0.0, 1.0)), sp['sky']) * lit * np.where(on, GAIN, 1.0)
-        line = 1.0 - sp['depth'] * np.exp(-0.5 * ((x[None, :] - (centre + np.where(on, SHIFT, 0.0))[:, None]) / sp['sigma']) ** 2)
-        img = np.clip(np.rint(sp['gain'] * bright[:, None] * line * 65535.0), 0, 65535).astype(np.uint16)
-        frames[k] = np.rot90(img, -1)
-    return frames
 
 
 @pytest.fixture(scope='module')
 def scan_file(tmp_path_factory):
     if not torch.cuda.is_available():
         pytest.skip('no GPU')
-    from solex_ser_recon_en_amd import synth
-    path = tmp_path_factory.mktemp('overlay') / 'scan.ser'
-    synth.write_ser(str(path), marked_scan())
-    return str(path)
-
-
-def grow(m):
-    """m dilated by one pixel (3 x 3)."""
-    p = np.pad(m, 1)
-    out = np.zeros_like(m)
-    for dy in (0, 1, 2):
-        for dx in (0, 1, 2):
-            out |= p[dy:dy + m.shape[0], dx:dx + m.shape[1]]
-    return out
-
-
-def same_region(a, b, what):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert a.sum() > 200 and b.sum() > 200, (what, int(a.sum()), int(b.sum()))
-    assert not (a & ~grow(b)).any() and not (b & ~grow(a)).any(), '%s: the marker lies on other pixels (%d vs %d px, %d apart)' % (
-        what, int(a.sum()), int(b.sum()), int((a & ~grow(b)).sum() + (b & ~grow(a)).sum()))
-
-
-def run_json(main, capsys, argv):
-    capsys.readouterr()
-    assert main(argv) == 0
-    out = capsys.readouterr().out.strip().splitlines()
-    return json.loads(out[-1])
+    return write_scan(tmp_path_factory, 'overlay', marked_scan())
 
 
 FLAGS = [('m', ['-m'], 0), ('s', ['-s'], 0), ('r_wide', ['-r', '500'], 0), ('r_narrow', ['-r', '200'], 0), ('x', ['-x'], 0),

@@ -1,14 +1,14 @@
 """shg_line_core_shift and shg_line_profile on seeded adversarial profiles (tests/profile_adversarial.py) in every layout the
-kernels branch on: bit for bit against the NumPy restatements, within the derived bound of the exact reference
-(tests/profile_exact.py), and line_profile's shift plane equal to line_core_shift's at S = 0.  The finish kernels' display
+kernels branch on: bit for bit against the NumPy restatement (tests/linemaps_ref.py), within the derived bound of the exact
+reference (tests/linemaps_exact.py), and line_profile's shift plane equal to line_core_shift's at S = 0.  The finish kernels' display
 rounding on exact ties and clips, and the library route (dopplergram(), line_profile_maps()) on 8-bit and un-rotated scans."""
 import numpy as np
 import pytest
 
-from tests import doppler_ref, lineprofile_ref
+from tests import linemaps_exact as ex
+from tests import linemaps_ref as ref
 from tests import profile_adversarial as adv
-from tests import profile_exact as ex
-from tests.test_doppler_gpu import same_bits
+from tests.linemaps_util import IH, IW, N, same_bits, scan_reader, upload
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
@@ -44,17 +44,6 @@ LAYOUTS = [  # (name, n, ih, iw, bits, half_width, shift, rotated file, pitched,
 ]
 
 
-def upload(ops, raw, bits, pitched):
-    dtype = torch.uint8 if bits == 8 else torch.uint16
-    host = torch.from_numpy(raw.view(np.int16) if bits == 16 else raw)
-    if pitched:
-        stack = ops.padded_stack(*raw.shape, dtype, 'cuda')
-        stack.copy_(host.view(dtype).cuda())
-        assert stack.stride(0) > raw.shape[1] * raw.shape[2]
-        return stack
-    return host.cuda().view(dtype)
-
-
 @pytest.mark.parametrize('layout', LAYOUTS, ids=[c[0] for c in LAYOUTS])
 def test_adversarial_profiles(ops, layout):
     name, n, ih, iw, bits, hw, shift, rot, pitched, flip, sharded = layout
@@ -66,7 +55,7 @@ def test_adversarial_profiles(ops, layout):
     cols = k_offset + np.arange(n)
     held = n_cols - 1 - cols if flip else cols                     # frame k's column
     kw = dict(flip_x=flip, n_cols=n_cols, k_offset=k_offset)
-    records = {s: ex.profile_records(P, fit, hw, s) for s in sorted({0, shift})}
+    records = {s: ex.records(P, fit, hw, s) for s in sorted({0, shift})}
     counts = adv.occurrences(records[shift], cls, fit, bits, shift)
     print('%s: %s' % (name, ', '.join('%s %d' % kv for kv in sorted(counts.items()))))
     if hw >= 5 and shift == 0:
@@ -76,15 +65,15 @@ def test_adversarial_profiles(ops, layout):
         assert counts.get('maxsum')
 
     core = ops.line_core_shift(stack, fit, hw, **kw).cpu().numpy()
-    same_bits(core, doppler_ref.line_core_shift(raw, fit, hw, **kw))
-    worst = {'line_core_shift': ex.within(core[:, held], records[0], 'shift')}
+    same_bits(core, ref.line_core_shift(raw, fit, hw, **kw))
+    worst = {'line_core_shift': ex.within(core[:, held], records[0], *ex.plane('shift'))}
     for s, rec in records.items():
         got = ops.line_profile(stack, fit, hw, s, **kw).cpu().numpy()
-        want = lineprofile_ref.line_profile(raw, fit, hw, s, **kw)
-        for q, plane in enumerate(ex.PLANES):
+        want = ref.line_profile(raw, fit, hw, s, **kw)
+        for q, plane in enumerate(ref.PLANES):
             same_bits(got[q], want[q])
             assert np.isfinite(got[q][:, held]).any(), plane
-            worst['%s S=%d' % (plane, s)] = ex.within(got[q][:, held], rec, plane, s)
+            worst['%s S=%d' % (plane, s)] = ex.within(got[q][:, held], rec, *ex.plane(plane, s))
         if s == 0:
             same_bits(got[0], core)
     print('%s: largest error / bound %s' % (name, ', '.join('%s %.3f' % kv for kv in worst.items())))
@@ -119,7 +108,7 @@ def test_finish_display_ties(ops):
     rt = torch.from_numpy(raw).cuda()
     maps, png = ops.line_profile_finish(rt, 1.0, 0.0, 0.0, 3, m, None, None, 3, 32767.0)
     maps, png = maps.cpu().numpy(), png.cpu().numpy()
-    want, want_png = lineprofile_ref.line_profile_finish(raw, 1.0, 0.0, 0.0, 3, m, None, None, 3, 32767.0)
+    want, want_png = ref.line_profile_finish(raw, 1.0, 0.0, 0.0, 3, m, None, None, 3, 32767.0)
     same_bits(maps, want)
     assert np.array_equal(png, want_png)
     # the map is the raw input (inf becomes NaN: t R = 0 x inf), and the hand-written display values
@@ -129,52 +118,42 @@ def test_finish_display_ties(ops):
     for q, pairs in ((0, SHIFT_TIES), (1, CORE_TIES), (2, WIDTH_CLIPS), (4, WIDTH_CLIPS)):
         expect = np.array([p[1] for p in pairs], dtype=np.uint16)
         for r in range(3):
-            assert np.array_equal(png[q, r, :len(pairs)], expect), (lineprofile_ref.PLANES[q], png[q, r, :len(pairs)], expect)
+            assert np.array_equal(png[q, r, :len(pairs)], expect), (ref.PLANES[q], png[q, r, :len(pairs)], expect)
     rev = np.array([p[1] for p in SHIFT_TIES], dtype=np.uint16)[::-1]
     assert np.array_equal(png[3, 0, m - len(SHIFT_TIES):], rev)
     # the Dopplergram's finish on the shift plane: the same display values
     one, dpng = ops.doppler_finish(rt[0], 1.0, 0.0, 0.0, 3, m, None, None, 32767.0)
     same_bits(one.cpu().numpy(), maps[0])
-    dwant, dwant_png = doppler_ref.doppler_finish(raw[0], 1.0, 0.0, 0.0, 3, m, None, None, 32767.0)
+    dwant, dwant_png = ref.doppler_finish(raw[0], 1.0, 0.0, 0.0, 3, m, None, None, 32767.0)
     assert np.array_equal(dpng.cpu().numpy(), dwant_png) and np.array_equal(dwant_png, png[0])
     assert np.array_equal(dpng.cpu().numpy()[:, :len(SHIFT_TIES)], np.tile(np.array([p[1] for p in SHIFT_TIES], dtype=np.uint16), (3, 1)))
 
 
 # ---- the library route on the file kinds the 16-bit rotated tests do not cover ----
-IH, N, IW = 400, 300, 48
-
-
-def scan_reader(frames):
-    from solex_ser_recon_en_amd.video_reader import array_reader
-    if frames.dtype == np.uint8:
-        return array_reader(torch.from_numpy(frames).cuda())
-    return array_reader(torch.from_numpy(frames.view(np.int16)).cuda().view(torch.uint16))
-
-
 @pytest.mark.parametrize('kind', ['u8_rotated', 'u16_plain'])
 def test_library_route_other_file_kinds(ops, kind):
     from solex_ser_recon_en_amd import doppler, lineprofile
     from solex_ser_recon_en_amd.ellipse_to_circle import _warp_geometry
-    shift, sigma, depth = lineprofile_ref.injected_fields(IH, N)
-    frames, _, _, _ = lineprofile_ref.disk_scan(shift, sigma, depth, IW, noise=0.004, seed=3, rotate=kind == 'u8_rotated')
+    shift, sigma, depth = ref.injected_fields(IH, N)
+    frames, _, _, _ = ref.profile_scan(shift, sigma, depth, IW, noise=0.004, seed=3, rotate=kind == 'u8_rotated')
     if kind == 'u8_rotated':
         frames = (frames >> 8).astype(np.uint8)
     assert (frames.shape[2] > frames.shape[1]) == (kind == 'u8_rotated')
     res = doppler.dopplergram(scan_reader(frames))
-    same_bits(res['raw'], doppler_ref.line_core_shift(frames, res['fit'], 5))
+    same_bits(res['raw'], ref.line_core_shift(frames, res['fit'], 5))
     assert np.isfinite(res['raw']).mean() > 0.3
     _, _, mat3, out_h, out_w, _, _ = _warp_geometry(res['phi'], res['ratio'], IH, N)
-    want, want_png = doppler_ref.doppler_finish(res['raw'], mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, res['circle'],
-                                                res['crop'], 2.0)
+    want, want_png = ref.doppler_finish(res['raw'], mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, res['circle'],
+                                        res['crop'], 2.0)
     same_bits(res['map'], want)
     assert np.array_equal(res['png'], want_png)
     lp = lineprofile.line_profile_maps(scan_reader(frames))
-    raw = np.stack([lp['raw'][p] for p in lineprofile_ref.PLANES])
-    for q, plane in enumerate(lineprofile_ref.PLANES):
-        same_bits(raw[q], lineprofile_ref.line_profile(frames, lp['fit'], 10)[q])
+    raw = np.stack([lp['raw'][p] for p in ref.PLANES])
+    for q, plane in enumerate(ref.PLANES):
+        same_bits(raw[q], ref.line_profile(frames, lp['fit'], 10)[q])
     _, _, mat3, out_h, out_w, _, _ = _warp_geometry(lp['phi'], lp['ratio'], IH, N)
-    maps, png = lineprofile_ref.line_profile_finish(raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, lp['circle'], lp['crop'],
-                                                    10, 2.0)
-    for q, plane in enumerate(lineprofile_ref.PLANES):
+    maps, png = ref.line_profile_finish(raw, mat3[0, 0], mat3[0, 1], mat3[0, 2], out_h, out_w, lp['circle'], lp['crop'],
+                                        10, 2.0)
+    for q, plane in enumerate(ref.PLANES):
         same_bits(lp['maps'][plane], maps[q])
         assert np.array_equal(lp['png'][plane], png[q]), plane

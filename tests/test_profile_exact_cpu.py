@@ -1,5 +1,5 @@
-"""The NumPy restatements of the line-core and line-profile kernels (tests/doppler_ref.py, tests/lineprofile_ref.py) against the
-exact reference (tests/profile_exact.py) on seeded adversarial profiles (tests/profile_adversarial.py) and on a synthetic scan:
+"""The NumPy restatement of the line-core and line-profile kernels (tests/linemaps_ref.py) against the exact reference
+(tests/linemaps_exact.py) on seeded adversarial profiles (tests/profile_adversarial.py) and on a synthetic scan:
 NaN where the exact value is NaN, and within the bound the header's operations allow everywhere else.  Also the argument that
 the float64 half level always takes the exact decision, checked case by case."""
 import math
@@ -8,9 +8,9 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from tests import doppler_ref, lineprofile_ref
+from tests import linemaps_exact as ex
+from tests import linemaps_ref as ref
 from tests import profile_adversarial as adv
-from tests import profile_exact as ex
 
 LAYOUTS = [  # (name, n, ih, iw, bits, half_width, shift, rotated file)
     ('rot_u16', 12, 304, 48, 16, 7, 0, True),
@@ -41,14 +41,14 @@ def test_restatements_agree_with_the_exact_reference(layout):
     P, fit, cls = adv.profiles(n, ih, iw, bits, hw, shift, seed=5)
     raw = adv.to_file(P, bits, rot)
     assert (raw.shape[2] > raw.shape[1]) == rot
-    assert np.array_equal(np.stack([doppler_ref.profiles(raw, y) for y in range(ih)], axis=1), P)   # the layout round trip
-    records = {s: ex.profile_records(P, fit, hw, s) for s in sorted({0, shift})}
+    assert np.array_equal(np.stack([ref.profiles(raw, y) for y in range(ih)], axis=1), P)   # the layout round trip
+    records = {s: ex.records(P, fit, hw, s) for s in sorted({0, shift})}
     check_coverage(name, adv.occurrences(records[shift], cls, fit, bits, shift), hw, shift)
-    worst = {'line_core_shift': ex.within(doppler_ref.line_core_shift(raw, fit, hw), records[0], 'shift')}
+    worst = {'line_core_shift': ex.within(ref.line_core_shift(raw, fit, hw), records[0], *ex.plane('shift'))}
     for s, rec in records.items():
-        planes = lineprofile_ref.line_profile(raw, fit, hw, s)
-        for q, plane in enumerate(ex.PLANES):
-            worst['%s S=%d' % (plane, s)] = ex.within(planes[q], rec, plane, s)
+        planes = ref.line_profile(raw, fit, hw, s)
+        for q, plane in enumerate(ref.PLANES):
+            worst['%s S=%d' % (plane, s)] = ex.within(planes[q], rec, *ex.plane(plane, s))
             assert np.isfinite(planes[q]).any() and np.isnan(planes[q]).any(), plane
     print('%s: largest error / bound %s' % (name, ', '.join('%s %.3f' % kv for kv in worst.items())))
 
@@ -64,15 +64,15 @@ def test_restatements_agree_on_a_synthetic_scan():
     centre[5:ih:13] = rng.uniform(iw - 5.0, iw + 1.5, centre[5:ih:13].shape)
     fit = np.stack([np.floor(centre), centre - np.floor(centre), np.arange(ih, dtype=np.float64), centre], axis=1)
     fit[3, 0], fit[7, 0], fit[9, 3] = np.nan, np.inf, np.nan
-    P = np.stack([doppler_ref.profiles(frames, y) for y in range(ih)], axis=1)
+    P = np.stack([ref.profiles(frames, y) for y in range(ih)], axis=1)
     for s in (0, 4):
-        rec = ex.profile_records(P, fit, hw, s)
-        planes = lineprofile_ref.line_profile(frames, fit, hw, s)
-        for q, plane in enumerate(ex.PLANES):
-            ex.within(planes[q], rec, plane, s)
+        rec = ex.records(P, fit, hw, s)
+        planes = ref.line_profile(frames, fit, hw, s)
+        for q, plane in enumerate(ref.PLANES):
+            ex.within(planes[q], rec, *ex.plane(plane, s))
             assert np.isfinite(planes[q]).any(), plane
         if s == 0:
-            ex.within(doppler_ref.line_core_shift(frames, fit, hw), rec, 'shift')
+            ex.within(ref.line_core_shift(frames, fit, hw), rec, *ex.plane('shift'))
             assert np.isfinite(planes[2]).mean() > 0.5
 
 
@@ -80,11 +80,11 @@ def test_float64_half_takes_the_exact_decision():
     """half = C2/4 + b/2 - d^2/(16 den) exactly.  When it is an integer, d^2/(8 den) is a multiple of 1/2, so every float64 step
     of the header (q = d^2/(8 den), b - q, 0.5 C2 + core, x 0.5) is exact and the float64 half is the exact one.  Otherwise the
     exact half, a fraction over 16 den, is at least 1/(16 den) from every integer, and the float64 half is closer to it than that
-    (profile_exact.bound's E_half): p >= half and b < half come out the same for every integer p, and so does p >= ceil(half)."""
+    (linemaps_exact.bound's E_half): p >= half and b < half come out the same for every integer p, and so does p >= ceil(half)."""
     n_int = n_frac = 0
     for name, n, ih, iw, bits, hw, shift, _ in LAYOUTS:
         P, fit, _ = adv.profiles(n, ih, iw, bits, hw, shift, seed=5)
-        for row in ex.profile_records(P, fit, hw, shift):
+        for row in ex.records(P, fit, hw, shift):
             for r in row or ():
                 if r['half'] is None:
                     continue
@@ -109,7 +109,7 @@ def test_float64_half_takes_the_exact_decision():
 
 
 def test_exact_reference_by_hand():
-    """A few values of profile_exact worked out on paper, so that the reference itself is pinned."""
+    """A few values of linemaps_exact worked out on paper, so that the reference itself is pinned."""
     # window: truncation toward zero (not floor), the 2^30 clamp, non-finite lines
     assert ex.window(-0.5, 0, 5, 40) == (1, 5) and ex.window(-1.5, 0, 5, 40) == (1, 4)
     assert ex.window(2.0 ** 31, 0, 5, 40) is None and ex.window(1e300, 0, 5, 40) is None and ex.window(math.nan, 0, 5, 40) is None
