@@ -16,8 +16,8 @@
  *    with respect to that stream and re-entrant (any number of threads, each with
  *    its own stream and buffers);
  *  - process-global state, all of it: (1) the per-thread error string; (2) the frame-pass lane of each device
- *    (shg_frame_pass_lane_set: one stream handle per device, set once) and a pair of events per (thread, device) that
- *    uses it; (3) the registry of passes launched ahead of their scans (shg_pass_a_prelaunch: workspace address ->
+ *    (shg_frame_pass_lane_set: one stream handle per device, set once) and an event per (thread, device) that
+ *    uses it from a stream with work pending; (3) the registry of passes launched ahead of their scans (shg_pass_a_prelaunch: workspace address ->
  *    launch plan + event, an entry lives from the prelaunch to the scan's first stage or shg_pass_a_forget); (4) every
  *    shg_pool: its threads, its queue and job map; (5) function-local
  *    one-time settings of kernel attributes (dynamic LDS sizes) and cached environment knobs (SHG_*); (6) the BLAS /
@@ -61,7 +61,9 @@ const char* shg_last_error_string(void);
 /* Optional per-kernel timing (bench.py roofline leg): HIP events recorded on the launch stream
  * directly around each kernel launch, keyed by kernel tag ("accumulate", "reduce_partials",
  * "extract", "warp", "rowpair_stats", "scale_rows", "clahe_hist", "clahe_lut", "clahe_interp",
- * "hist", "rescale", ...).  Off by default.  shg_profile_get waits for the events of `tag`. */
+ * "hist", "rescale", ...); the two frame passes ("accumulate", "extract") have theirs bound to the kernel's
+ * own dispatch as its start and stop events instead, which queues nothing between two kernels.
+ * Off by default.  shg_profile_get waits for the events of `tag`. */
 int shg_profile_enable(int on);
 int shg_profile_select(const char* tags_csv);   /* only time these tags (NULL or "" = all) */
 int shg_profile_reset(void);
@@ -704,6 +706,12 @@ int shg_scan_prelaunch(const shg_scan_request* req, shg_stream_t after, int* lau
 int shg_pass_a_prelaunch(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px,
                          int64_t frame_stride_px, void* workspace, size_t workspace_bytes, shg_stream_t after, int* launched);
 int shg_pass_a_forget(const void* workspace);
+/* Measurement aid (tools/lane_packets.py): `launches` passes A back to back on `stream`, all into `workspace`, with between two
+ * launches  mode 0: three event records (two timed, one not),  1: one,  2: nothing,  3: nothing, an event bound to every launch
+ * as the lane binds it (and, while the profiler is enabled for "accumulate", a sample per launch).  -> milliseconds per launch. */
+int shg_lane_packets_probe(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px,
+                           int64_t frame_stride_px, void* workspace, size_t workspace_bytes, int mode, int launches,
+                           shg_stream_t stream, double* ms_per_launch);
 int shg_pool_poll(shg_pool* pool, int64_t ticket);
 int shg_pool_wait(shg_pool* pool, int64_t ticket, int* scan_status, char* error_buf, size_t error_cap);
 int shg_pool_destroy(shg_pool* pool);

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <mutex>
 #include <unordered_map>
+#include <vector>
 #include <algorithm>
 #include "shg_common.h"
 
@@ -354,8 +355,9 @@ template <typename Src> __global__ __launch_bounds__(256) void k_finalize_rot(co
     }
 }
 
+// (the launch's events -- the profiler's pair, the `done` a scan waits for -- are bound to the dispatch itself: shg::launch_timed)
 template <int BPP, bool NT>
-void launch_vec(const Plan& p, const void* stack, int n, uint32_t* psum, uint16_t* pmax, hipStream_t st) {
+int launch_vec(const Plan& p, const void* stack, int n, uint32_t* psum, uint16_t* pmax, hipStream_t st, hipEvent_t* done) {
     const int64_t nblk = (p.vecs + 255) / 256;
     dim3 grid((unsigned)nblk, (unsigned)p.nsplit);
     int xcd_per = 0;
@@ -368,14 +370,15 @@ void launch_vec(const Plan& p, const void* stack, int n, uint32_t* psum, uint16_
     // shorter workgroups than the device can hold (a larger nsplit) the hardware then hands them out as earlier ones finish: CUs
     // that the other scans' kernels keep busy simply take fewer of them
     const size_t pad_lds = (size_t)std::min(std::max(tuning().lds_kib, 0), 160) * 1024;
-#define SHG_ACC_LAUNCH(U) { SHG_PROF("accumulate", st);                                                                                    \
+#define SHG_ACC_LAUNCH(U) {                                                                                                                \
         if (pad_lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_accumulate_vec<BPP, U, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds); \
-        k_accumulate_vec<BPP, U, NT><<<grid, 256, pad_lds, st>>>(s, p.vecs, p.stride_vecs, n, p.frames_per_split, psum, pmax, p.npix, p.nsplit, xcd_per, tuning().prio, tuning().interleave); }
+        return shg::launch_timed("accumulate", k_accumulate_vec<BPP, U, NT>, grid, dim3(256), pad_lds, st, done, "k_accumulate",          \
+                                 s, p.vecs, p.stride_vecs, n, p.frames_per_split, psum, pmax, p.npix, p.nsplit, xcd_per, tuning().prio, tuning().interleave); }
     switch (p.unroll) {
-        case 2: SHG_ACC_LAUNCH(2) break;
-        case 4: SHG_ACC_LAUNCH(4) break;
-        case 16: SHG_ACC_LAUNCH(16) break;
-        default: SHG_ACC_LAUNCH(8) break;
+        case 2: SHG_ACC_LAUNCH(2)
+        case 4: SHG_ACC_LAUNCH(4)
+        case 16: SHG_ACC_LAUNCH(16)
+        default: SHG_ACC_LAUNCH(8)
     }
 #undef SHG_ACC_LAUNCH
 }
@@ -395,7 +398,8 @@ extern "C" size_t shg_accumulate_workspace_bytes(int64_t n_frames, int64_t heigh
 namespace {
 // pass A into the per-slab partials at the head of `workspace`: psum u32 [nsplit][npix], pmax u16 [nsplit][npix]
 int accumulate_partials(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px, int64_t frame_stride_px,
-                        void* workspace, size_t workspace_bytes, shg_stream_t stream, Plan* plan_out, uint32_t** psum_out, uint16_t** pmax_out) {
+                        void* workspace, size_t workspace_bytes, shg_stream_t stream, Plan* plan_out, uint32_t** psum_out, uint16_t** pmax_out,
+                        hipEvent_t* done = nullptr) {
     SHG_REQUIRE(stack && workspace, SHG_E_ARG, "shg_accumulate_sum_max: null pointer");
     SHG_REQUIRE(n_frames > 0 && height > 0 && width > 0, SHG_E_ARG, "shg_accumulate_sum_max: empty stack (%lld x %lld x %lld)",
                 (long long)n_frames, (long long)height, (long long)width);
@@ -413,21 +417,24 @@ int accumulate_partials(const void* stack, int64_t n_frames, int64_t height, int
     uint32_t* psum = static_cast<uint32_t*>(workspace);
     uint16_t* pmax = reinterpret_cast<uint16_t*>(psum + (size_t)p.nsplit * p.npix);
     const int n = (int)n_frames;
+    int status;
     if (p.vector_path) {
         const bool nt = tuning().nt != 0;
-        if (bytes_per_px == 2) { if (nt) launch_vec<2, true>(p, stack, n, psum, pmax, st); else launch_vec<2, false>(p, stack, n, psum, pmax, st); }
-        else { if (nt) launch_vec<1, true>(p, stack, n, psum, pmax, st); else launch_vec<1, false>(p, stack, n, psum, pmax, st); }
+        if (bytes_per_px == 2) status = nt ? launch_vec<2, true>(p, stack, n, psum, pmax, st, done) : launch_vec<2, false>(p, stack, n, psum, pmax, st, done);
+        else status = nt ? launch_vec<1, true>(p, stack, n, psum, pmax, st, done) : launch_vec<1, false>(p, stack, n, psum, pmax, st, done);
     } else {
         dim3 grid((unsigned)((p.npix + 255) / 256), (unsigned)p.nsplit);
         if (bytes_per_px == 2)
-            { SHG_PROF("accumulate", st); k_accumulate_scalar<uint16_t><<<grid, 256, 0, st>>>(static_cast<const uint16_t*>(stack), p.npix, p.stride_px, n, p.frames_per_split, psum, pmax); }
+            status = shg::launch_timed("accumulate", k_accumulate_scalar<uint16_t>, grid, dim3(256), 0, st, done, "k_accumulate",
+                                       static_cast<const uint16_t*>(stack), p.npix, p.stride_px, n, p.frames_per_split, psum, pmax);
         else
-            { SHG_PROF("accumulate", st); k_accumulate_scalar<uint8_t><<<grid, 256, 0, st>>>(static_cast<const uint8_t*>(stack), p.npix, p.stride_px, n, p.frames_per_split, psum, pmax); }
+            status = shg::launch_timed("accumulate", k_accumulate_scalar<uint8_t>, grid, dim3(256), 0, st, done, "k_accumulate",
+                                       static_cast<const uint8_t*>(stack), p.npix, p.stride_px, n, p.frames_per_split, psum, pmax);
     }
     *plan_out = p;
     *psum_out = psum;
     *pmax_out = pmax;
-    return shg::check_launch("k_accumulate");
+    return status;
 }
 
 template <typename Src>
@@ -468,10 +475,10 @@ struct PassA {
     uint32_t* psum;
     uint16_t* pmax;
 };
-int launch_pass_a(hipStream_t st, void* arg) {
+int launch_pass_a(hipStream_t st, void* arg, hipEvent_t* done) {
     PassA* a = static_cast<PassA*>(arg);
     return accumulate_partials(a->stack, a->n_frames, a->height, a->width, a->bytes_per_px, a->frame_stride_px, a->workspace, a->workspace_bytes,
-                               reinterpret_cast<shg_stream_t>(st), &a->p, &a->psum, &a->pmax);
+                               reinterpret_cast<shg_stream_t>(st), &a->p, &a->psum, &a->pmax, done);
 }
 }  // namespace
 
@@ -479,7 +486,7 @@ int launch_pass_a(hipStream_t st, void* arg) {
 namespace {
 struct Ahead {
     PassA a;
-    hipEvent_t done;
+    hipEvent_t done;                      // bound to the pass's dispatch; with the profiler on it is also the sample's b (shg::event_release)
 };
 std::mutex g_ahead_mu;
 std::unordered_map<const void*, Ahead> g_ahead;
@@ -506,7 +513,7 @@ bool take_ahead(PassA* want, bool* same, int* status) {
         SHG_HOST_TIME("lane wait (queue + pass A)");
         e = hipEventSynchronize(got.done);
     }
-    (void)hipEventDestroy(got.done);
+    shg::event_release(got.done);
     *status = 0;
     if (e != hipSuccess) { shg::set_error("frame-pass lane: %s", hipGetErrorString(e)); *status = (int)e; }
     *same = same_pass(got.a, *want) && got.a.workspace_bytes <= want->workspace_bytes;
@@ -548,6 +555,51 @@ extern "C" int shg_pass_a_forget(const void* workspace) {
     int status = 0;
     (void)take_ahead(&a, &same, &status);
     return status;
+}
+
+// Measurement aid (tools/lane_packets.py): `launches` passes back to back on `stream`, all into the one workspace, with between
+// consecutive launches  mode 0: three hipEventRecord (the lane before its events were bound: the profiler's a and b, the scan's done),
+// 1: one (the same lane without the profiler), 2: nothing, 3: nothing, the launch's events bound to its dispatch as the lane does
+// now (a `done` per pass; with the profiler enabled for "accumulate" also a sample per pass, whose b is that `done`).
+// -> *ms_per_launch: from a record in front of the first launch to one behind the last, over `launches`.
+extern "C" int shg_lane_packets_probe(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px,
+                                      int64_t frame_stride_px, void* workspace, size_t workspace_bytes, int mode, int launches,
+                                      shg_stream_t stream, double* ms_per_launch) {
+    SHG_REQUIRE(ms_per_launch && mode >= 0 && mode <= 3 && launches > 0 && launches <= 4096, SHG_E_ARG, "shg_lane_packets_probe: bad argument");
+    hipStream_t st = shg::as_stream(stream);
+    PassA a{stack, n_frames, height, width, bytes_per_px, frame_stride_px, workspace, workspace_bytes, Plan{}, nullptr, nullptr};
+    hipEvent_t first = nullptr, last = nullptr, rec[3] = {};
+    std::vector<hipEvent_t> dones;
+    hipError_t e = hipEventCreate(&first);
+    if (e == hipSuccess) e = hipEventCreate(&last);
+    const int n_rec = mode == 0 ? 3 : mode == 1 ? 1 : 0;       // (the profiler's pair gives times, the scan's event does not)
+    for (int i = 0; i < n_rec && e == hipSuccess; ++i)
+        e = mode == 0 && i < 2 ? hipEventCreate(&rec[i]) : hipEventCreateWithFlags(&rec[i], hipEventDisableTiming);
+    int status = 0;
+    if (e == hipSuccess) e = hipEventRecord(first, st);
+    for (int i = 0; i < launches && e == hipSuccess && status == 0; ++i) {
+        if (mode == 0) e = hipEventRecord(rec[0], st);
+        hipEvent_t done = nullptr;
+        if (e == hipSuccess) status = launch_pass_a(st, &a, mode == 3 ? &done : nullptr);
+        if (done) dones.push_back(done);
+        if (mode == 0 && status == 0) e = hipEventRecord(rec[1], st);
+        if (mode <= 1 && status == 0 && e == hipSuccess) e = hipEventRecord(rec[mode == 0 ? 2 : 0], st);
+    }
+    if (e == hipSuccess && status == 0) e = hipEventRecord(last, st);
+    const hipError_t es = hipStreamSynchronize(st);            // (whatever went wrong: nothing of this is pending when the events go)
+    if (e == hipSuccess) e = es;
+    for (hipEvent_t d : dones) {                               // a bound event has completed with its kernel
+        if (e == hipSuccess && status == 0 && hipEventQuery(d) != hipSuccess) { (void)hipGetLastError(); e = hipErrorNotReady; }
+        shg::event_release(d);
+    }
+    float ms = 0.f;
+    if (e == hipSuccess && status == 0) e = hipEventElapsedTime(&ms, first, last);
+    for (hipEvent_t x : {first, last, rec[0], rec[1], rec[2]})
+        if (x) (void)hipEventDestroy(x);
+    if (status) return status;
+    if (e != hipSuccess) { (void)hipGetLastError(); shg::set_error("shg_lane_packets_probe: %s", hipGetErrorString(e)); return (int)e; }
+    *ms_per_launch = (double)ms / launches;
+    return 0;
 }
 
 // Pass A goes through the frame-pass lane when the process has one (streams.hip): the passes of all scans in flight run

@@ -608,7 +608,7 @@ int launch_band(const BandArgs& ba, int bytes_per_px, int64_t ih, hipStream_t st
         static const bool ok_ = lds <= 64 * 1024 || hipFuncSetAttribute(reinterpret_cast<const void*>(k_extract_band<T, GV, CONSEC>),    \
                                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; \
         if (!ok_) (void)hipGetLastError();                                                                                                \
-        status = shg::launch(k_extract_band<T, GV, CONSEC>, grid, dim3(64 * BAND_NW), lds, st, ba, "k_extract_band");                     \
+        status = shg::launch_timed("extract", k_extract_band<T, GV, CONSEC>, grid, dim3(64 * BAND_NW), lds, st, nullptr, "k_extract_band", ba); \
     }
     if constexpr (CONSEC) {
         SHG_BAND(uint16_t, 4) SHG_BAND(uint16_t, 5) SHG_BAND(uint16_t, 6) SHG_BAND(uint16_t, 7)
@@ -701,7 +701,7 @@ extern "C" int shg_extract_columns_minmax(const void* stack, int64_t n_frames, i
     const int n = (int)n_frames;
     const ExtractArgs xa{stack, n, height, width, fstride, ind_l, lw, rw, n_shifts, disks, row_pitch, plane_stride, n_cols, k_offset, flip_x, vec_store, minmax_slots};
     int launch_status = 0;
-#define EXT_LAUNCH_BS(T, ROT, B, SCV) launch_status = shg::launch(k_extract<T, ROT, B, SCV>, grid, dim3(256), 0, st, xa, "k_extract")
+#define EXT_LAUNCH_BS(T, ROT, B, SCV) launch_status = shg::launch_timed("extract", k_extract<T, ROT, B, SCV>, grid, dim3(256), 0, st, nullptr, "k_extract", xa)
 #define EXT_LAUNCH_B(T, ROT, B) do { if (sc == 2) EXT_LAUNCH_BS(T, ROT, B, 2); else EXT_LAUNCH_BS(T, ROT, B, 4); } while (0)
 #define EXT_LAUNCH(T, ROT)                                                 \
     switch (batch) {                                                       \
@@ -727,21 +727,15 @@ extern "C" int shg_extract_columns_minmax(const void* stack, int64_t n_frames, i
     if (rot && !general_only) {
         BandArgs ba{stack, n, height, width, fstride, ind_l, nullptr, lw, rw, n_shifts, disks, row_pitch, plane_stride, n_cols, k_offset, flip_x, vec_store,
                     minmax_slots, (int)((n_cols + TK - 1) / TK), {}};
-        {
-            SHG_PROF("extract", st);
-            launch_status = launch_band<false>(ba, bytes_per_px, ih, st);
-        }
+        launch_status = launch_band<false>(ba, bytes_per_px, ih, st);
         if (launch_status) return launch_status;
         if (minmax_slots) return launch_fold(minmax_slots, n_shifts, st);
         return 0;
     }
-    {
-        SHG_PROF("extract", st);
-        if (bytes_per_px == 2) {
-            if (rot) EXT_LAUNCH(uint16_t, true) else EXT_LAUNCH(uint16_t, false)
-        } else {
-            if (rot) EXT_LAUNCH(uint8_t, true) else EXT_LAUNCH(uint8_t, false)
-        }
+    if (bytes_per_px == 2) {
+        if (rot) EXT_LAUNCH(uint16_t, true) else EXT_LAUNCH(uint16_t, false)
+    } else {
+        if (rot) EXT_LAUNCH(uint8_t, true) else EXT_LAUNCH(uint8_t, false)
     }
 #undef EXT_LAUNCH_B
 #undef EXT_LAUNCH_BS
@@ -804,11 +798,7 @@ extern "C" int shg_extract_columns_dense(const void* stack, int64_t n_frames, in
         BandArgs ba{stack, n, height, width, fstride, ind_l, base_col, lw, rw, n_shifts, disks, row_pitch, plane_stride, n_cols, k_offset, flip_x, vec_store,
                     minmax_slots, (int)((n_cols + TK - 1) / TK), {}};
         for (int i = 0; i < n_shifts; ++i) ba.plane_of[host_shifts[i] - lo] = (uint8_t)i;
-        int launch_status;
-        {
-            SHG_PROF("extract", st);
-            launch_status = launch_band<true>(ba, bytes_per_px, ih, st);
-        }
+        const int launch_status = launch_band<true>(ba, bytes_per_px, ih, st);
         if (launch_status) return launch_status;
         if (minmax_slots) return launch_fold(minmax_slots, n_shifts, st);
         return 0;
@@ -822,8 +812,9 @@ extern "C" int shg_extract_columns_dense(const void* stack, int64_t n_frames, in
         if (!ok_) (void)hipGetLastError();                                                                                                          \
         const size_t lds = (size_t)n_shifts * TY * (DKV + 2) * sizeof(uint16_t);                                                                    \
         dim3 grid((unsigned)((n_cols + DKV - 1) / DKV), (unsigned)((ih + TY - 1) / TY));                                                            \
-        k_extract_dense<T, ROT, B, NW, DKV><<<grid, 64 * NW, lds, st>>>(static_cast<const T*>(stack), n, height, width, fstride, ind_l, base_col, lw, rw, \
-                                                                       n_shifts, po, disks, row_pitch, plane_stride, n_cols, k_offset, flip_x, vec_store, minmax_slots); \
+        launch_status = shg::launch_timed("extract", k_extract_dense<T, ROT, B, NW, DKV>, grid, dim3(64 * NW), lds, st, nullptr, "k_extract_dense",      \
+                                          static_cast<const T*>(stack), n, height, width, fstride, ind_l, base_col, lw, rw,                       \
+                                          n_shifts, po, disks, row_pitch, plane_stride, n_cols, k_offset, flip_x, vec_store, minmax_slots);       \
     } while (0)
 #define SHG_DENSE_S(T, ROT)                                                                  \
     do {                                                                                     \
@@ -837,14 +828,12 @@ extern "C" int shg_extract_columns_dense(const void* stack, int64_t n_frames, in
             default: SHG_DENSE(T, ROT, 4, 4, 16); break;                                     \
         }                                                                                    \
     } while (0)
-    {
-        SHG_PROF("extract", st);
-        if (bytes_per_px == 2) { if (rot) SHG_DENSE_S(uint16_t, true); else SHG_DENSE_S(uint16_t, false); }
-        else { if (rot) SHG_DENSE_S(uint8_t, true); else SHG_DENSE_S(uint8_t, false); }
-    }
+    int launch_status = 0;
+    if (bytes_per_px == 2) { if (rot) SHG_DENSE_S(uint16_t, true); else SHG_DENSE_S(uint16_t, false); }
+    else { if (rot) SHG_DENSE_S(uint8_t, true); else SHG_DENSE_S(uint8_t, false); }
 #undef SHG_DENSE_S
 #undef SHG_DENSE
-    if (int e = shg::check_launch("k_extract_dense")) return e;
+    if (launch_status) return launch_status;
     if (minmax_slots) return launch_fold(minmax_slots, n_shifts, st);
     return 0;
 }

@@ -1,6 +1,7 @@
 // Shared helpers for the libshg_hip.so translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <type_traits>
@@ -29,6 +30,39 @@ inline int launch(void (*k)(A), dim3 grid, dim3 block, size_t lds, hipStream_t s
     return check_launch(what);
 }
 
+// The same launch with its events bound to the kernel's own dispatch packet (hipExtLaunchKernel) instead of recorded around it:
+// an hipEventRecord is a barrier-and-signal packet of its own, handled after the previous kernel has retired and before the next
+// may start -- on the frame-pass lane, where the passes of all scans run back to back, three of them between two passes were the
+// lane's idle gap.  Two things may want events:
+//   * the profiler, when it is enabled for `tag`: the sample's a / b are created here and bound as start / stop of the launch;
+//     the sample is (tag, a, b) as with SHG_PROF, which stays the way to time everything that is not one launch;
+//   * the caller, with `done` != nullptr: *done is an event bound as the launch's stop event, to wait for (hipEventSynchronize,
+//     hipStreamWaitEvent) and then to hand to shg::event_release -- never to hipEventDestroy: when the profiler took a sample,
+//     *done IS the sample's b, and the two hold it by a reference count (the last of shg_profile_reset and event_release destroys it).
+// With neither this is shg::launch.  `a...` are the kernel's arguments, one for one.
+struct TimedEvents { hipEvent_t start = nullptr, stop = nullptr; bool sampled = false; };
+int timed_begin(const char* tag, bool want_done, TimedEvents* ev);
+void timed_end(const char* tag, hipStream_t st, const TimedEvents& ev, bool launched, hipEvent_t* done);
+void event_release(hipEvent_t e);
+template <typename... P>
+inline int launch_timed(const char* tag, void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, hipEvent_t* done, const char* what,
+                        typename same_type<P>::type... a) {
+    TimedEvents ev;
+    if (int e = timed_begin(tag, done != nullptr, &ev)) return e;
+    int r;
+    if (ev.start || ev.stop) {
+        void* args[] = {static_cast<void*>(&a)...};
+        const hipError_t le = hipExtLaunchKernel(reinterpret_cast<const void*>(k), grid, block, args, lds, st, ev.start, ev.stop, 0);
+        r = check_launch(what);
+        if (r == 0 && le != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(le)); r = (int)le; }
+    } else {
+        hipLaunchKernelGGL(k, grid, block, lds, st, a...);
+        r = check_launch(what);
+    }
+    timed_end(tag, st, ev, r == 0, done);
+    return r;
+}
+
 #define SHG_REQUIRE(cond, code, ...)            \
     do {                                        \
         if (!(cond)) {                          \
@@ -39,9 +73,11 @@ inline int launch(void (*k)(A), dim3 grid, dim3 block, size_t lds, hipStream_t s
 
 inline hipStream_t as_stream(shg_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-// The frame-pass lane (streams.hip): launch(stream, arg) runs on the current device's lane when one is set -- `st` then
-// waits for it through an event -- and on `st` itself otherwise.
-int on_frame_pass_lane(hipStream_t st, int (*launch)(hipStream_t, void*), void* arg);
+// The frame-pass lane (streams.hip): launch(stream, arg, done) runs on the current device's lane when one is set -- `st` then
+// waits for it through the event the launch bound to its kernel (*done, shg::launch_timed; done is null when nobody waits) --
+// and on `st` itself otherwise.
+typedef int (*lane_launch_fn)(hipStream_t st, void* arg, hipEvent_t* done);
+int on_frame_pass_lane(hipStream_t st, lane_launch_fn launch, void* arg);
 
 // Set by a stage that has already cleared the extrema's slots (stages.hip: in the launch that uploads the plan); the extraction entry point
 // this thread calls next then skips its memset, and resets the flag.
@@ -54,9 +90,9 @@ extern thread_local void* t_zero_with_fold;
 extern thread_local size_t t_zero_with_fold_words;
 extern thread_local void* t_prezeroed;
 size_t limb_prepare_zero_words(int64_t h, int64_t w);          // words shg_limb_prepare zeroes for an [h][w] disk (0: not the fused path's)
-// The same launch with nobody waiting: after what `after` holds so far, *done recorded behind it (the caller's to destroy).
-// -> 1 when the device has no lane (nothing launched), 0 when launched, another value on error.
-int prelaunch_on_lane(hipStream_t after, int (*launch)(hipStream_t, void*), void* arg, hipEvent_t* done);
+// The same launch with nobody waiting: after what `after` holds so far, *done = the event bound to it (the caller's to
+// shg::event_release).  -> 1 when the device has no lane (nothing launched), 0 when launched, another value on error.
+int prelaunch_on_lane(hipStream_t after, lane_launch_fn launch, void* arg, hipEvent_t* done);
 
 // Optional per-kernel timing with HIP events recorded on the launch stream, right around
 // the launch (bench.py's roofline leg).  Disabled by default: no events, no overhead.

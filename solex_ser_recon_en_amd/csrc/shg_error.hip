@@ -15,6 +15,7 @@ void set_error(const char* fmt, ...) {
 // ---- event profiler ---------------------------------------------------------------
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 namespace shg {
 namespace {
@@ -24,16 +25,76 @@ std::mutex g_mu;
 bool g_enabled = false;
 std::vector<Sample> g_samples;
 std::vector<std::string> g_only;      // empty = every tag
+// A sample's b that a caller of launch_timed also waits on (its `done`): the profiler and the waiter each hold one reference, and
+// whoever lets go last (shg_profile_reset, event_release) destroys the event.  Every other event has one owner and is not listed.
+std::unordered_map<hipEvent_t, int> g_shared;
+
+bool wanted(const char* tag) {            // under g_mu
+    if (!g_enabled) return false;
+    if (g_only.empty()) return true;
+    for (auto& t : g_only)
+        if (t == tag) return true;
+    return false;
+}
+void release_locked(hipEvent_t e) {       // under g_mu
+    auto it = g_shared.find(e);
+    if (it != g_shared.end()) {
+        if (--it->second > 0) return;
+        g_shared.erase(it);
+    }
+    (void)hipEventDestroy(e);
+}
 }  // namespace
+
+void event_release(hipEvent_t e) {
+    if (!e) return;
+    std::lock_guard<std::mutex> lk(g_mu);
+    release_locked(e);
+}
+
+// The events of one launch_timed: a timed pair when the profiler wants a sample of `tag`, else a stop event alone when the caller
+// waits for the launch (that one never gives a time: created without timing), else none.
+int timed_begin(const char* tag, bool want_done, TimedEvents* ev) {
+    *ev = TimedEvents{};
+    if (g_enabled) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        ev->sampled = wanted(tag);
+    }
+    if (ev->sampled && (hipEventCreate(&ev->start) != hipSuccess || hipEventCreate(&ev->stop) != hipSuccess)) {
+        (void)hipGetLastError();                               // the profiler's own trouble: no sample, as in ProfScope
+        if (ev->start) (void)hipEventDestroy(ev->start);
+        *ev = TimedEvents{};
+    }
+    if (!ev->stop && want_done) {
+        if (hipError_t e = hipEventCreateWithFlags(&ev->stop, hipEventDisableTiming)) {
+            (void)hipGetLastError();
+            set_error("launch event: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    return 0;
+}
+
+// The sample enters the list once its events are bound (a reader never meets an event no launch knows of), in whatever generation
+// is current then; a launch that failed leaves nothing behind.
+void timed_end(const char* tag, hipStream_t st, const TimedEvents& ev, bool launched, hipEvent_t* done) {
+    if (!launched) {
+        if (ev.start) (void)hipEventDestroy(ev.start);
+        if (ev.stop) (void)hipEventDestroy(ev.stop);
+        return;
+    }
+    if (ev.sampled) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        g_samples.push_back(Sample{tag, ev.start, ev.stop, st, g_generation});
+        if (done) g_shared[ev.stop] = 2;
+    }
+    if (done) *done = ev.stop;
+}
 
 ProfScope::ProfScope(const char* tag, hipStream_t st) : slot(-1), stream(st), generation(0) {
     if (!g_enabled) return;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_only.empty()) {
-        bool hit = false;
-        for (auto& t : g_only) hit = hit || t == tag;
-        if (!hit) return;
-    }
+    if (!wanted(tag)) return;
     Sample s;
     s.tag = tag;
     s.stream = st;
@@ -124,7 +185,7 @@ extern "C" int shg_profile_select(const char* tags_csv) {
 
 extern "C" int shg_profile_reset(void) {
     std::lock_guard<std::mutex> lk(shg::g_mu);
-    for (auto& s : shg::g_samples) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
+    for (auto& s : shg::g_samples) { (void)hipEventDestroy(s.a); shg::release_locked(s.b); }     // (a b some scan still waits on lives on with it)
     shg::g_samples.clear();
     ++shg::g_generation;
     return 0;

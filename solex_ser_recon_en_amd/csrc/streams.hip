@@ -9,6 +9,11 @@
 // asked, each alone with the small kernels of the other scans, and the chains run on the workers' own streams
 // (optionally confined to a subset of the CUs, hipExtStreamCreateWithCUMask).  A scan waits for its own pass A through
 // an event (on the host by default, see on_frame_pass_lane).
+//
+// Nothing but kernels goes onto the lane.  Between two passes every other packet -- an hipEventRecord is one: a barrier and a
+// signal the command processor handles by itself, after the previous kernel has retired and before the next may start -- is time
+// in which the one thing a batch is bound by does nothing.  So the event a scan waits for, and the profiler's pair when it is on,
+// are bound to the pass's own dispatch (shg::launch_timed, which the launch callback passes `done` on to), not recorded behind it.
 #include <stdlib.h>
 #include <mutex>
 #include <vector>
@@ -17,19 +22,16 @@
 namespace shg {
 namespace {
 constexpr int kMaxDevices = 64;
-std::mutex g_lane_mu;                         // guards g_lanes, and keeps one scan's (launch, record) pair together
+std::mutex g_lane_mu;                         // guards g_lanes, and keeps one scan's (wait for its producer, launch) pair together
 hipStream_t g_lanes[kMaxDevices] = {};
 struct LaneEvents {
-    hipEvent_t ev[kMaxDevices] = {};
     hipEvent_t before[kMaxDevices] = {};
     ~LaneEvents() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : before)
             if (e) (void)hipEventDestroy(e);
     }
 };
-thread_local LaneEvents t_events;             // a pair of events per (thread, device): a thread has one pass A pending at most
+thread_local LaneEvents t_events;             // an event per (thread, device) for a producer stream that is still busy
 }  // namespace
 
 hipStream_t frame_pass_lane(int device) {
@@ -37,42 +39,36 @@ hipStream_t frame_pass_lane(int device) {
     return g_lanes[device];                   // read without the lock: set once per process before the workers start
 }
 
-// Launch `launch(stream)` on the device's lane when there is one (and make `st` wait for it), else on `st`.
-int on_frame_pass_lane(hipStream_t st, int (*launch)(hipStream_t, void*), void* arg) {
+// Launch `launch(stream, arg, done)` on the device's lane when there is one (and make `st` wait for it), else on `st`.
+int on_frame_pass_lane(hipStream_t st, lane_launch_fn launch, void* arg) {
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) device = -1;
     hipStream_t lane = frame_pass_lane(device);
-    if (!lane || lane == st) return launch(st, arg);
-    hipEvent_t& ev = t_events.ev[device];
-    hipEvent_t& before = t_events.before[device];
-    if (!ev || !before) {
-        hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e == hipSuccess && !before) e = hipEventCreateWithFlags(&before, hipEventDisableTiming);
-        if (e != hipSuccess) { set_error("frame-pass lane: %s", hipGetErrorString(e)); return (int)e; }
-    }
+    if (!lane || lane == st) return launch(st, arg, nullptr);
+    hipEvent_t ev = nullptr;
     hipError_t e;
     {
         std::lock_guard<std::mutex> lk(g_lane_mu);
         // the pass reads what the caller's stream has produced so far (a stack a kernel has only just written, a workspace
         // the previous scan's last kernel still uses): the lane waits for that point of `st` -- in the scan pool, where a
-        // worker synchronises its stream after every scan, there is nothing to wait for
-        // (a stream with nothing pending -- the usual case -- needs no barrier on the lane: every packet between two passes
-        // there is a few microseconds in which the lane, the one thing the rate of a batch is bound by, does nothing)
+        // worker synchronises its stream after every scan, there is nothing to wait for, and a stream with nothing pending
+        // -- the usual case -- puts no barrier on the lane
         if (hipStreamQuery(st) != hipSuccess) {
             (void)hipGetLastError();
-            e = hipEventRecord(before, st);
+            hipEvent_t& before = t_events.before[device];
+            e = before ? hipSuccess : hipEventCreateWithFlags(&before, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventRecord(before, st);
             if (e == hipSuccess) e = hipStreamWaitEvent(lane, before, 0);
             if (e != hipSuccess) { set_error("frame-pass lane: %s", hipGetErrorString(e)); return (int)e; }
         }
-        if (int le = launch(lane, arg)) return le;
-        e = hipEventRecord(ev, lane);
+        if (int le = launch(lane, arg, &ev)) return le;
     }
     // How the scan's own stream learns that its pass has run.  A barrier in the stream (hipStreamWaitEvent) costs the host
     // nothing, but the runtime multiplexes streams onto a few hardware queues (4 by default) and a barrier that waits for
     // the lane holds up every stream that shares the queue -- with more scan workers than queues, whole chains of OTHER scans.
     // Waiting on the host keeps the queue free; the stage synchronises a few kernels later anyway.
     static const bool host_wait = [] { const char* v = getenv("SHG_LANE_WAIT"); return !(v && v[0] == 's'); }();
-    if (e == hipSuccess) {
+    {
         SHG_HOST_TIME("lane wait (queue + pass A)");
         if (host_wait) {
             e = hipEventSynchronize(ev);
@@ -80,46 +76,38 @@ int on_frame_pass_lane(hipStream_t st, int (*launch)(hipStream_t, void*), void* 
             e = hipStreamWaitEvent(st, ev, 0);
         }
     }
+    event_release(ev);                                       // (letting go of an event a stream waits on is fine: the wait has been queued)
     if (e != hipSuccess) { set_error("frame-pass lane: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
 }
 
 // Launch on the lane without anybody waiting for it here: the pass of a scan that is still queued (shg_pass_a_prelaunch).  The lane
-// first waits for what `after` has queued so far (the stack's producer, if it is still running); *done gets an event recorded
-// behind the launch (the caller owns it).  -> 1 when there is no lane (nothing launched), 0 launched, else an error.
-int prelaunch_on_lane(hipStream_t after, int (*launch)(hipStream_t, void*), void* arg, hipEvent_t* done) {
+// first waits for what `after` has queued so far (the stack's producer, if it is still running); *done gets the event bound to the
+// launch (the caller hands it to shg::event_release).  -> 1 when there is no lane (nothing launched), 0 launched, else an error.
+int prelaunch_on_lane(hipStream_t after, lane_launch_fn launch, void* arg, hipEvent_t* done) {
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return 1;
     hipStream_t lane = frame_pass_lane(device);
     if (!lane) return 1;
-    hipEvent_t before = nullptr, ev = nullptr;
+    hipEvent_t before = nullptr;
     const bool idle = hipStreamQuery(after) == hipSuccess;    // nothing pending there: no barrier on the lane (see on_frame_pass_lane)
     if (!idle) (void)hipGetLastError();
     hipError_t e = idle ? hipSuccess : hipEventCreateWithFlags(&before, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    int le = 0;
     if (e == hipSuccess) {
         std::lock_guard<std::mutex> lk(g_lane_mu);
         if (!idle) {
             e = hipEventRecord(before, after);
             if (e == hipSuccess) e = hipStreamWaitEvent(lane, before, 0);
         }
-        if (e == hipSuccess) {
-            if (int le = launch(lane, arg)) {
-                if (before) (void)hipEventDestroy(before);
-                (void)hipEventDestroy(ev);
-                return le;
-            }
-            e = hipEventRecord(ev, lane);
-        }
+        if (e == hipSuccess) le = launch(lane, arg, done);
     }
     if (before) (void)hipEventDestroy(before);               // (destroying a recorded event is fine: the wait has been queued)
     if (e != hipSuccess) {
-        if (ev) (void)hipEventDestroy(ev);
         set_error("frame-pass lane: %s", hipGetErrorString(e));
         return (int)e;
     }
-    *done = ev;
-    return 0;
+    return le;
 }
 }  // namespace shg
 
