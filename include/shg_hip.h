@@ -243,6 +243,34 @@ int shg_line_bisector_finish(const float* raw, int64_t raw_plane_stride, int n_l
                              float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
                              int64_t png_pitch, int half_width, double display_range, shg_stream_t stream);
 
+/* ---- removing a fitted plane from a finished line map (not a reference stage; tests/detrend_ref.py restates both calls in NumPy,
+ * bit for bit).  The plane z = a + b c + g r (c the column, r the row of the map as the finish wrote it) is fitted on the host from
+ * ten integer moments; the 3 x 3 normal equations are INTEGRATION.md's.
+ * shg_map_plane_moments: pixel (r, c) with v = map[r * pitch + c] is USED iff
+ *   v is finite and |v| < 64;
+ *   with a circle (circle3, host: cx, cy, rad; NULL or (-1, -1, -1): none), not (c - cx)^2 + (r - cy)^2 > rad^2 -- shg_doppler_finish's
+ *   float64 test step for step: dx = (double)c - cx, dy = (double)r - cy, dx * dx + dy * dy against rad * rad;
+ *   with prev4 (host: a, b, g, limit; NULL: none), |(double)v - ((a + b * (double)c) + g * (double)r)| <= limit, one IEEE operation a
+ *   step, no contraction, the <= inclusive (limit may be +inf).
+ * q = (int64)rint((double)v * 4096), ties to even (the product is exact).  Over the used pixels, all exact int64:
+ *   moments10 = { N, sum c, sum r, sum c^2, sum c r, sum r^2, sum q, sum q c, sum q r, sum q^2 }
+ * moments10 is device memory; the call overwrites it (it does not add to it).  Every accumulated quantity is an integer, so the result
+ * does not depend on the order of the additions.  1 <= h, w <= 8192, else SHG_E_UNSUPPORTED.  The bound: |v| < 64 gives |q| <= 2^18
+ * (the largest float32 below 64 rounds up to it), c, r < 2^13 and N <= 2^26, so the largest sums are sum q^2 <= 2^36 * 2^26 = 2^62 and
+ * |sum q c| < 2^18 * 2^13 * 2^26 = 2^57: every slot stays below 2^63.  SHG_E_ARG for a null map or moments10, pitch < w, a limit that
+ * is negative or NaN, or a previous plane that is not finite.  On any error nothing is written. */
+int shg_map_plane_moments(const float* map, int64_t h, int64_t w, int64_t pitch, const double* circle3, const double* prev4,
+                          int64_t* moments10, shg_stream_t stream);
+
+/* shg_map_detrend: out[r * out_pitch + c] = (float)((double)v - ((a + b * (double)c) + g * (double)r)), v = map[r * pitch + c],
+ * plane3 (host) = (a, b, g), one IEEE operation a step: a NaN v gives NaN, an infinite one stays infinite.  out may be map when the
+ * pitches are equal (in place).  png (may be NULL, row pitch png_pitch): shg_doppler_finish's display rule on the OUTPUT value o: 0
+ * where o is NaN, else clip(rint(32768 + (double)o * (32767 / display_range)), 1, 65535).  Elements between w and a pitch are never
+ * touched.  Limits and codes as shg_map_plane_moments; SHG_E_ARG also for a plane3 that is not finite, an output pitch < w, out == map
+ * with another pitch, and (with png) a display range that is not positive. */
+int shg_map_detrend(const float* map, int64_t h, int64_t w, int64_t pitch, const double* plane3, float* out, int64_t out_pitch,
+                    uint16_t* png, int64_t png_pitch, double display_range, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -105,6 +105,76 @@ def _by_plane(res, keys, units, velocity, raw, maps, png, factor, **more):
     return res
 
 
+# ---- removing the plane a global field (solar rotation) leaves in a shift map ------------------------------------------------
+Q_SCALE = 4096                                # shg_map_plane_moments sums q = rint(4096 v)
+MAX_CLIP_ITERATIONS = 16
+
+
+def plane_from_moments(m10):
+    """The least-squares plane z = a + b c + g r through the used pixels' z = q / 4096, from shg_map_plane_moments' ten integers {N,
+    sum c, sum r, sum c^2, sum c r, sum r^2, sum q, sum q c, sum q r, sum q^2} -> (a, b, g, sigma, n).  Exact rational arithmetic
+    (Cramer's rule on Python ints): a, b, g are the exact solution of the 3 x 3 normal equations, each rounded once to float64;
+    sigma = sqrt(float(RSS / (N - 3))) with the residual sum of squares exact.  ValueError when N < 4 or the determinant is 0 (the
+    used pixels lie on one line)."""
+    from fractions import Fraction
+    n, sc, sr, scc, scr, srr, sq, sqc, sqr, sqq = (int(v) for v in m10)
+    if n < 4:
+        raise ValueError('a plane fit needs at least 4 used pixels, got %d' % n)
+
+    def det3(m):
+        return (m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0])
+                + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]))
+
+    lhs = ((n, sc, sr), (sc, scc, scr), (sr, scr, srr))
+    rhs = (sq, sqc, sqr)
+    det = det3(lhs)
+    if det == 0:
+        raise ValueError('the used pixels lie on one line: no plane through them')
+    sol = [Fraction(det3([[rhs[i] if j == k else lhs[i][j] for j in range(3)] for i in range(3)]), det * Q_SCALE) for k in range(3)]
+    # at the solution RSS = sum z^2 - a sum z - b sum z c - g sum z r
+    rss = Fraction(sqq, Q_SCALE * Q_SCALE) - (sol[0] * sq + sol[1] * sqc + sol[2] * sqr) / Q_SCALE
+    return float(sol[0]), float(sol[1]), float(sol[2]), math.sqrt(float(rss / (n - 3))), n
+
+
+def detrend_plane(m, circle=None, clip=3.0, iterations=3, display_range=None):
+    """The map minus its sigma-clipped least-squares plane a + b * column + g * row.  m: a float32 [h, w] GPU tensor, or a NumPy
+    array (uploaded; the results then come back as NumPy arrays).  Pass 0 fits every usable pixel (finite, |v| < 64, inside
+    `circle` = (cx, cy, r) in the map's own columns and rows; None or (-1, -1, -1): no mask); each of up to `iterations` further
+    passes fits the pixels within clip * sigma of the previous plane, and the loop ends early when a pass used the same number of
+    pixels as the one before or sigma is 0.  A pass is one launch and an 80-byte readback; the solve is plane_from_moments.
+    -> (detrended, png (with display_range R: doppler_finish's display plane of the detrended map) or None, info: a, b, g, sigma,
+    n_used, n_valid (pass 0's N), passes, gradient = hypot(b, g), axis_angle_deg = degrees(atan2(g, b)), the direction of steepest
+    increase in the (column, row) frame, and with a circle limb_amplitude = gradient * r)."""
+    import torch
+    from . import ops
+    if not (math.isfinite(clip) and clip > 0):
+        raise ValueError('clip must be finite and positive')
+    if int(iterations) != iterations or not 0 <= iterations <= MAX_CLIP_ITERATIONS:
+        raise ValueError('iterations must lie in [0, %d]' % MAX_CLIP_ITERATIONS)
+    host = not isinstance(m, torch.Tensor)
+    dm = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).cuda() if host else m
+    masked = circle is not None and tuple(circle) != (-1, -1, -1)
+    slots = torch.empty(10, dtype=torch.int64, device=dm.device)
+    a, b, g, sigma, n = plane_from_moments(ops.map_plane_moments(dm, circle, None, slots).cpu().numpy())
+    n_valid, passes = n, 1
+    for _ in range(int(iterations)):
+        if sigma == 0.0:
+            break
+        before = n
+        a, b, g, sigma, n = plane_from_moments(ops.map_plane_moments(dm, circle, (a, b, g, clip * sigma), slots).cpu().numpy())
+        passes += 1
+        if n == before:
+            break
+    out, png = ops.map_detrend(dm, (a, b, g), display_range)
+    info = {'a': a, 'b': b, 'g': g, 'sigma': sigma, 'n_used': n, 'n_valid': n_valid, 'passes': passes, 'gradient': math.hypot(b, g),
+            'axis_angle_deg': math.degrees(math.atan2(g, b))}
+    if masked:
+        info['limb_amplitude'] = info['gradient'] * float(circle[2])
+    if host:
+        return out.cpu().numpy(), None if png is None else png.cpu().numpy(), info
+    return out, png, info
+
+
 def disk_stats(res):
     """valid fraction, median and 1st / 99th percentile of the map on the disk (the whole map without a circle)."""
     m = res['map']

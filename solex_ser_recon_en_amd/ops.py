@@ -904,3 +904,42 @@ def line_bisector_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=Non
     planes = raw.shape[0] if isinstance(raw, torch.Tensor) and raw.dim() == 3 and raw.shape[0] % 2 == 0 else -1
     return _planes_finish('shg_line_bisector_finish', planes, '2K', raw, h00, h01, h02, out_h, out_w, circle, crop, half_width,
                           display_range, planes // 2)
+
+
+# ---- removing a fitted plane from a finished map -----------------------------------------------------
+def map_plane_moments(m, circle=None, prev=None, out=None):
+    """shg_map_plane_moments: the ten integer moments {N, sum c, sum r, sum c^2, sum c r, sum r^2, sum q, sum q c, sum q r, sum q^2}
+    (q = rint(4096 v)) of the used pixels of the map float32 [h, w] -> int64 [10] on the map's device (`out`: the caller's,
+    overwritten).  Used: finite, |v| < 64, inside `circle` (cx, cy, r; None or (-1, -1, -1): no mask) and, with prev = (a, b, g,
+    limit), within limit of that plane."""
+    ptr, h, w, pitch = _img(m, 'map', torch.float32)
+    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    p4 = None if prev is None else np.ascontiguousarray([float(v) for v in prev], dtype=np.float64)
+    if (c3 is not None and c3.size != 3) or (p4 is not None and p4.size != 4):
+        raise ValueError('circle is (cx, cy, r) and prev is (a, b, g, limit)')
+    if out is None:
+        out = torch.empty(10, dtype=torch.int64, device=m.device)
+    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (10,) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int64 [10] tensor')
+    _lib.check(lib.shg_map_plane_moments(ptr, h, w, pitch, _host_ptr(c3), _host_ptr(p4), out.data_ptr(), _stream()),
+               'shg_map_plane_moments')
+    return out
+
+
+def map_detrend(m, plane, display_range=None, out=None):
+    """shg_map_detrend: the map float32 [h, w] minus the plane (a, b, g): a + b * column + g * row -> (out float32 [h, w], png uint16
+    [h, w] or None).  out: the caller's view (the map itself: in place), else a new one.  display_range R: also the 16-bit display
+    plane of the output, as doppler_finish's."""
+    ptr, h, w, pitch = _img(m, 'map', torch.float32)
+    p3 = np.ascontiguousarray([float(v) for v in plane], dtype=np.float64)
+    if p3.size != 3:
+        raise ValueError('plane is (a, b, g)')
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.float32, device=m.device)
+    optr, oh, ow, opitch = _img(out, 'out', torch.float32)
+    if (oh, ow) != (h, w):
+        raise ValueError('out must be a float32 [%d, %d] view' % (h, w))
+    png = None if display_range is None else torch.empty((h, w), dtype=torch.uint16, device=m.device)
+    _lib.check(lib.shg_map_detrend(ptr, h, w, pitch, _host_ptr(p3), optr, opitch, None if png is None else png.data_ptr(), w,
+                                   0.0 if display_range is None else float(display_range), _stream()), 'shg_map_detrend')
+    return out, png
