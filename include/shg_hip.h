@@ -243,6 +243,44 @@ int shg_line_bisector_finish(const float* raw, int64_t raw_plane_stride, int n_l
                              float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
                              int64_t png_pitch, int half_width, double display_range, shg_stream_t stream);
 
+/* ---- emission-line maps (not a reference stage; tests/emission_ref.py restates both calls in NumPy, bit for bit)
+ * shg_line_emission: five planes of every (slit row y, frame k) for a line seen in EMISSION (prominences off the limb, flares), in
+ * shg_line_profile's layout and with its p(j), c, window [lo, hi], ref = fit[y][3] + (double)S, col(k), limits on H and SHG_E_ARG
+ * range of S.  j* = the first j in [lo, hi] with MAXIMAL p(j); a, b, e = p(j* - 1), p(j*), p(j* + 1), den = a + e - 2b (at a bracketed
+ * first maximum a < b and e <= b: den < 0, never zero).  Every integer below is exact in float64, every step one IEEE operation:
+ *   B2 = p(lo) + p(hi) (integer, twice the background);
+ *   peak_d = (double)b - (double)((a - e)^2) / (8.0 (double)den), excess_d = peak_d - 0.5 (double)B2.
+ * The gate: all five planes are NaN unless lo < j* < hi and excess_d >= min_excess (min_excess finite and >= 0, else SHG_E_ARG and
+ * nothing written).  Scattered disk light off the limb carries the absorption line, whose maximum sits on the window's edge; min_excess
+ * rejects noise bumps.  Past the gate:
+ *   shift = (float)(((double)j* + (double)(a - e) / (double)(2 den)) - ref)
+ *   peak = (float)excess_d
+ *   half = 0.5 (0.5 (double)B2 + peak_d); width NaN unless p(j*) > half;
+ *   jl = the largest j in [lo, j*) with p(j) <= half, xl = (double)jl + (half - (double)p(jl)) / (double)(p(jl + 1) - p(jl));
+ *   jr = the smallest j in (j*, hi] with p(j) <= half, xr = (double)jr - (half - (double)p(jr)) / (double)(p(jr - 1) - p(jr));
+ *   width = (float)(xr - xl), NaN when jl or jr does not exist
+ *   n = hi - lo + 1, int64 S0 = 2 sum p - n B2, S1 = 2 sum j p - B2 sum j over [lo, hi];
+ *   cog = (float)((double)S1 / (double)S0 - ref), flux = (float)(0.5 (double)S0); both NaN when S0 <= 0.
+ * The bound: p < 2^16, n <= 65 and j < 2^16 (a frame holds < 2^32 samples and iw is its shorter side), so |S0| < 2^24 and |S1| < 2^40,
+ * (a - e)^2 < 2^32: every integer is far below 2^53.
+ * planes[q * plane_stride + y * row_pitch + col(k)], q = 0 shift, 1 peak, 2 width, 3 cog, 4 flux. */
+int shg_line_emission(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px, int64_t frame_stride_px,
+                      const double* fit, int half_width, int shift, double min_excess, int flip_x, float* planes, int64_t plane_stride,
+                      int64_t row_pitch, int64_t n_cols, int64_t k_offset, shg_stream_t stream);
+
+/* shg_line_emission_finish: shg_line_profile_finish with a ring in place of the circle.  Each plane of every output pixel is
+ * bit-identical to shg_doppler_finish on that plane with no circle; then, with ring4 (host: cx, cy, r_in, r_out; NULL: no mask),
+ * dx = (double)c - cx, dy = (double)r - cy, d2 = dx * dx + dy * dy (the circle test's float64 steps), v = NaN where
+ *   r_in >= 0 and d2 <= r_in * r_in   (the limb pixel itself is masked; a negative r_in: no inner mask, emission on the disk), or
+ *   d2 > r_out * r_out                (r_out = +inf keeps everything).
+ * SHG_E_ARG for a NaN in ring4, r_out < 0 or r_out < r_in.  crop4, pitches and limits as shg_line_profile_finish.
+ * png (may be NULL): 0 where v is NaN, else clip(rint(e), 1, 65535) with e = 32768 + (double)v * (32767 / display_range) for shift and
+ * cog, (double)v for peak, 1 + (double)v * (65534 / (2 H + 1)) for width, (double)v / (double)(2 H + 1) for flux. */
+int shg_line_emission_finish(const float* raw, int64_t raw_plane_stride, int64_t h, int64_t w, int64_t raw_pitch, double h00,
+                             double h01, double h02, int64_t out_h, int64_t out_w, const double* ring4, const int64_t* crop4,
+                             float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
+                             int64_t png_pitch, int half_width, double display_range, shg_stream_t stream);
+
 /* ---- removing a fitted plane from a finished line map (not a reference stage; tests/detrend_ref.py restates both calls in NumPy,
  * bit for bit).  The plane z = a + b c + g r (c the column, r the row of the map as the finish wrote it) is fitted on the host from
  * ten integer moments; the 3 x 3 normal equations are INTEGRATION.md's.

@@ -95,6 +95,10 @@ SIGNATURES = {
                                   c_int64, c_int64, P]),
     'shg_line_bisector_finish': (c_int, [P, c_int64, c_int, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_int64, c_int64,
                                          P, P, P, c_int64, c_int64, P, c_int64, c_int64, c_int, c_double, P]),
+    'shg_line_emission': (c_int, [P, c_int64, c_int64, c_int64, c_int, c_int64, P, c_int, c_int, c_double, c_int, P, c_int64, c_int64,
+                                  c_int64, c_int64, P]),
+    'shg_line_emission_finish': (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_int64, c_int64, P, P,
+                                         P, c_int64, c_int64, P, c_int64, c_int64, c_int, c_double, P]),
     'shg_map_plane_moments': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P]),
     'shg_map_detrend': (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, c_double, P]),
     'shg_blur_fits_fused': (c_int, [c_int64, c_int]),

@@ -37,6 +37,9 @@
 // k_map_finish<1> (the Dopplergram's), k_map_finish<5> (the profile's), k_map_finish<2K, K> (the bisectors'): the ellipse -> circle
 // resample of k_warp_rows with NaN for taps outside, the limb mask, the crop / pad of crop_plan, and the 16-bit display planes; one
 // thread per output pixel, all planes of it.
+// Emission maps (shg_line_emission, shg_line_emission_finish): the profile's kernels with the polarity EMIT (first maximum, the
+// crossings downward, the sums' sign, the gate on the peak's excess over the background), the same walks, state and tile;
+// k_map_finish<5, 0, RING> masks with a ring around the limb instead of the disk's circle.
 #include "shg_common.h"
 
 #include <limits.h>
@@ -67,6 +70,7 @@ struct MapArgs {
     int flip_x;
     int nl;                                    // bisectors: K, planes 0 .. K-1 bisectors, K .. 2K-1 chords
     double f[kMaxLevels];                      // the levels' fractions
+    double min_excess;                         // the emission maps' gate
 };
 
 // Window of a slit row around fit[y][0] + S: lo > hi when the row has none (then its shift, and every plane, is NaN).
@@ -81,23 +85,25 @@ __device__ __forceinline__ void window_of(double f0, int s, int hw, int iw, int&
     hi = h;
 }
 
-// The streaming arg-minimum of one slit row: the first minimum of p over [lo, hi] and the samples either side of it.
+// The streaming arg-minimum of one slit row: the first minimum of p over [lo, hi] and the samples either side of it.  EMIT (the
+// emission maps' polarity, here and below): the first maximum.
 struct Core {
     int best, jb, a, e, prev;
 };
 
+template <bool EMIT = false>
 __device__ __forceinline__ void core_init(Core& s) {
-    s.best = INT_MAX;
+    s.best = EMIT ? INT_MIN : INT_MAX;
     s.jb = -2;
     s.a = s.e = s.prev = 0;
 }
 
 // in_window() runs for the samples inside [lo, hi] (walk 1 of the profile adds its sums there).
-template <typename F = void (*)()>
+template <bool EMIT = false, typename F = void (*)()>
 __device__ __forceinline__ void core_step(Core& s, int j, int p, int lo, int hi, F&& in_window = [] {}) {
     if (j == s.jb + 1) s.e = p;
     if (j >= lo && j <= hi) {
-        if (p < s.best) {
+        if (EMIT ? p > s.best : p < s.best) {
             s.best = p;
             s.jb = j;
             s.a = s.prev;
@@ -108,7 +114,8 @@ __device__ __forceinline__ void core_step(Core& s, int j, int p, int lo, int hi,
 }
 
 // d = (float)(((double)j* + delta) - ref), NaN unless lo < j* < hi.  a > b strictly (first occurrence) and e >= b, so the
-// denominator is positive; every integer is exact in float64 and the quotient is one IEEE division.
+// denominator is positive (at a first maximum a < b and e <= b: negative); every integer is exact in float64 and the quotient is
+// one IEEE division.
 __device__ __forceinline__ float core_shift(const Core& s, int lo, int hi, double ref) {
     if (!(s.jb > lo && s.jb < hi)) return __builtin_nanf("");
     const double delta = (double)(s.a - s.e) / (double)(2 * (s.a + s.e - 2 * s.best));
@@ -122,20 +129,23 @@ struct Walk1 {
     int sp, st, c2;
 };
 
+template <bool EMIT = false>
 __device__ __forceinline__ void walk1_init(Walk1& s) {
-    core_init(s.c);
+    core_init<EMIT>(s.c);
     s.sp = s.st = s.c2 = 0;
 }
 
+template <bool EMIT = false>
 __device__ __forceinline__ void walk1_step(Walk1& s, int j, int p, int lo, int hi) {
-    core_step(s.c, j, p, lo, hi, [&] {
+    core_step<EMIT>(s.c, j, p, lo, hi, [&] {
         s.sp += p;
         s.st += (j - lo) * p;
         if (j == lo || j == hi) s.c2 += p;
     });
 }
 
-// core_d of a row with a vertex (lo < j* < hi): the parabola's value at its vertex.  den > 0: a > b (first minimum), e >= b.
+// core_d of a row with a vertex (lo < j* < hi): the parabola's value at its vertex.  den > 0: a > b (first minimum), e >= b (the
+// emission maps' peak_d: den < 0).
 __device__ __forceinline__ double core_d_of(const Core& c) {
     const int den = c.a + c.e - 2 * c.best;
     const int64_t d = c.a - c.e;
@@ -146,7 +156,15 @@ __device__ __forceinline__ double core_d_of(const Core& c) {
 __device__ __forceinline__ double level_of(double f, double core_d, int c2) { return ((1.0 - f) * core_d) + (f * (0.5 * (double)c2)); }
 
 // The crossing threshold ceil(level) of a row with a vertex, INT_MAX when p(j*) >= level (|level| < 2^30: core_d > -2^30, C2 < 2^17).
-__device__ __forceinline__ int thr_of(double level, int best) { return (double)best < level ? (int)ceil(level) : INT_MAX; }
+// EMIT: floor(level), INT_MIN when p(j*) <= level (the crossings are the samples <= level).  no_cross<EMIT>: that sentinel.
+template <bool EMIT = false>
+constexpr int no_cross = EMIT ? INT_MIN : INT_MAX;
+
+template <bool EMIT = false>
+__device__ __forceinline__ int thr_of(double level, int best) {
+    if constexpr (EMIT) return (double)best > level ? (int)floor(level) : INT_MIN;
+    return (double)best < level ? (int)ceil(level) : INT_MAX;
+}
 
 // The planes walk 1 decides (shift, core, cog, ew), and the half level of the width: see include/shg_hip.h.
 struct Vertex {
@@ -155,14 +173,32 @@ struct Vertex {
     int thr;                                   // INT_MAX: no width
 };
 
-__device__ __forceinline__ Vertex vertex_of(const Walk1& s, int lo, int hi, double ref) {
+// EMIT (shg_line_emission): shift, peak = the excess over the background C2 / 2, cog and flux of p - C2 / 2 (S0 and S1 with the other
+// sign), every plane NaN unless the first maximum is bracketed and its excess reaches min_excess.
+template <bool EMIT = false>
+__device__ __forceinline__ Vertex vertex_of(const Walk1& s, int lo, int hi, double ref, double min_excess = 0.0) {
     const float nan = __builtin_nanf("");
-    Vertex v{nan, nan, nan, nan, 0.0, INT_MAX};
+    Vertex v{nan, nan, nan, nan, 0.0, no_cross<EMIT>};
     if (lo > hi) return v;
     const int64_t n = hi - lo + 1, c2 = s.c2;
     const int64_t s0 = n * c2 - 2 * (int64_t)s.sp;
     const int64_t sj = n * (int64_t)(lo + hi) / 2;                       // Σj over [lo, hi] (n (lo + hi) is even)
     const int64_t s1 = c2 * sj - 2 * ((int64_t)lo * s.sp + (int64_t)s.st);
+    if constexpr (EMIT) {
+        if (!(s.c.jb > lo && s.c.jb < hi)) return v;
+        const double peak = core_d_of(s.c);
+        const double excess = peak - 0.5 * (double)s.c2;
+        if (!(excess >= min_excess)) return v;
+        v.shift = core_shift(s.c, lo, hi, ref);
+        v.core = (float)excess;
+        if (s0 < 0) {
+            v.cog = (float)((double)-s1 / (double)-s0 - ref);
+            v.ew = (float)(0.5 * (double)-s0);
+        }
+        v.half = level_of(0.5, peak, s.c2);
+        v.thr = thr_of<true>(v.half, s.c.best);
+        return v;
+    }
     if (s0 > 0) v.cog = (float)((double)s1 / (double)s0 - ref);
     if (c2 != 0) v.ew = (float)((double)s0 / (double)c2);
     if (!(s.c.jb > lo && s.c.jb < hi)) return v;
@@ -177,7 +213,7 @@ __device__ __forceinline__ Vertex vertex_of(const Walk1& s, int lo, int hi, doub
 // Walk 2's crossing state of one (slit row, level): jl = the largest j in [lo, j*) with p(j) >= level, jr = the smallest j in
 // (j*, hi] with p(j) >= level (p(j) >= level <=> p(j) >= thr = ceil(level) for integer p; thr = INT_MAX when the row has no
 // crossings).  The sample pairs either side of a crossing are kept as p | p' << 16 (samples < 2^16).  The previous sample is the
-// caller's, kept beside the state (one for all of a row's levels).
+// caller's, kept beside the state (one for all of a row's levels).  EMIT: p(j) <= level <=> p(j) <= thr = floor(level).
 struct Cross {
     int jl, jr;
     uint32_t l, r;
@@ -188,26 +224,29 @@ __device__ __forceinline__ void cross_init(Cross& s) {
     s.l = s.r = 0;
 }
 
+template <bool EMIT = false>
 __device__ __forceinline__ void cross_step(Cross& s, int j, int p, int prev, int lo, int hi, int jb, int thr) {
-    if (j > lo && j <= jb && prev >= thr) {
+    if (j > lo && j <= jb && (EMIT ? prev <= thr : prev >= thr)) {
         s.jl = j - 1;
         s.l = (uint32_t)prev | ((uint32_t)p << 16);      // p(jl), p(jl + 1)
     }
-    if (j > jb && j <= hi && s.jr < 0 && p >= thr) {
+    if (j > jb && j <= hi && s.jr < 0 && (EMIT ? p <= thr : p >= thr)) {
         s.jr = j;
         s.r = (uint32_t)p | ((uint32_t)prev << 16);      // p(jr), p(jr - 1)
     }
 }
 
 // The crossings xl, xr of walk 2's state at `level`, each interpolated linearly with its inner neighbour: bis = their midpoint
-// - ref and len = the chord xr - xl (at half: the profile's width); both NaN when the row has no crossing pair.
+// - ref and len = the chord xr - xl (at half: the profile's width); both NaN when the row has no crossing pair.  EMIT: the header
+// writes (level - p(jl)) / (p(jl + 1) - p(jl)), both operands of the quotient below negated, which is the same float64.
 struct Chord {
     float bis, len;
 };
 
+template <bool EMIT = false>
 __device__ __forceinline__ Chord crossings(const Cross& s, double level, int thr, double ref) {
     Chord c{__builtin_nanf(""), __builtin_nanf("")};
-    if (thr == INT_MAX || s.jl < 0 || s.jr < 0) return c;
+    if (thr == no_cross<EMIT> || s.jl < 0 || s.jr < 0) return c;
     const int pl = (int)(s.l & 0xffffu), pl1 = (int)(s.l >> 16), pr = (int)(s.r & 0xffffu), pr1 = (int)(s.r >> 16);
     const double xl = (double)s.jl + ((double)pl - level) / (double)(pl - pl1);
     const double xr = (double)s.jr - ((double)pr - level) / (double)(pr - pr1);
@@ -364,7 +403,7 @@ __device__ __forceinline__ void write_tile(const MapArgs& a, const float* tile, 
     }
 }
 
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool EMIT = false>
 __global__ __launch_bounds__(64 * kWaves) void k_line_profile_rot(const MapArgs a) {
     __shared__ float tile[kPlanes * kWaves * kTileRows];            // 80 KiB: two workgroups per CU
     const int lane = threadIdx.x & 63;
@@ -377,8 +416,8 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_profile_rot(const MapArgs 
             const char* frame = static_cast<const char*>(a.stack) + k * a.fstride * (int64_t)sizeof(T);
             Walk1 s[kRowsPerLane];
 #pragma unroll
-            for (int r = 0; r < kRowsPerLane; ++r) walk1_init(s[r]);
-            walk_band<T, VEC>(frame, b, [&](int j, int r, int p) { walk1_step(s[r], j, p, b.lo[r], b.hi[r]); });
+            for (int r = 0; r < kRowsPerLane; ++r) walk1_init<EMIT>(s[r]);
+            walk_band<T, VEC>(frame, b, [&](int j, int r, int p) { walk1_step<EMIT>(s[r], j, p, b.lo[r], b.hi[r]); });
             double half[kRowsPerLane];
             int thr[kRowsPerLane], jb[kRowsPerLane];
 #pragma unroll
@@ -388,7 +427,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_profile_rot(const MapArgs 
                 for (int r = 0; r < 4; ++r) {
                     const int64_t x = b.x0 + h + r;
                     const double ref = x < b.width ? a.fit[(b.width - 1 - x) * 4 + 3] + (double)a.shift : 0.0;
-                    v[r] = vertex_of(s[h + r], b.lo[h + r], b.hi[h + r], ref);
+                    v[r] = vertex_of<EMIT>(s[h + r], b.lo[h + r], b.hi[h + r], ref, a.min_excess);
                     half[h + r] = v[r].half;
                     thr[h + r] = v[r].thr;
                     jb[h + r] = s[h + r].c.jb;
@@ -407,14 +446,14 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_profile_rot(const MapArgs 
                 prev[r] = 0;
             }
             walk_band<T, VEC>(frame, b, [&](int j, int r, int p) {
-                cross_step(t[r], j, p, prev[r], b.lo[r], b.hi[r], jb[r], thr[r]);
+                cross_step<EMIT>(t[r], j, p, prev[r], b.lo[r], b.hi[r], jb[r], thr[r]);
                 prev[r] = p;
             });
 #pragma unroll
             for (int h = 0; h < kRowsPerLane; h += 4)
-                *reinterpret_cast<float4*>(&tile[tile_at(2, wave, lane * kRowsPerLane + h)]) =
-                    make_float4(crossings(t[h], half[h], thr[h], 0.0).len, crossings(t[h + 1], half[h + 1], thr[h + 1], 0.0).len,
-                                crossings(t[h + 2], half[h + 2], thr[h + 2], 0.0).len, crossings(t[h + 3], half[h + 3], thr[h + 3], 0.0).len);
+                *reinterpret_cast<float4*>(&tile[tile_at(2, wave, lane * kRowsPerLane + h)]) = make_float4(
+                    crossings<EMIT>(t[h], half[h], thr[h], 0.0).len, crossings<EMIT>(t[h + 1], half[h + 1], thr[h + 1], 0.0).len,
+                    crossings<EMIT>(t[h + 2], half[h + 2], thr[h + 2], 0.0).len, crossings<EMIT>(t[h + 3], half[h + 3], thr[h + 3], 0.0).len);
         }
         __syncthreads();
         write_tile<kPlanes>(a, tile, kb, [](int qt) { return (int64_t)qt; });
@@ -446,14 +485,14 @@ __device__ __forceinline__ bool plain_row(const MapArgs& a, PlainRow<T>& t) {
 }
 
 // Walk 2 of a plain kernel's row at one level (none when thr = INT_MAX: no crossing can be found).
-template <typename T>
+template <typename T, bool EMIT = false>
 __device__ __forceinline__ Cross cross_row(const PlainRow<T>& t, int jb, int thr) {
     Cross s;
     cross_init(s);
-    if (thr == INT_MAX) return s;
+    if (thr == no_cross<EMIT>) return s;
     for (int j = t.lo, prev = 0; j <= t.hi; ++j) {
         const int p = t.p(j);
-        cross_step(s, j, p, prev, t.lo, t.hi, jb, thr);
+        cross_step<EMIT>(s, j, p, prev, t.lo, t.hi, jb, thr);
         prev = p;
     }
     return s;
@@ -469,17 +508,17 @@ __global__ __launch_bounds__(64 * kWaves) void k_line_core_plain(const MapArgs a
     t.out[0] = core_shift(s, t.lo, t.hi, a.fit[t.y * 4 + 3]);
 }
 
-template <typename T>
+template <typename T, bool EMIT = false>
 __global__ __launch_bounds__(64 * kWaves) void k_line_profile_plain(const MapArgs a) {
     PlainRow<T> t;
     if (!plain_row(a, t)) return;
     Walk1 s;
-    walk1_init(s);
-    for (int j = t.lo; j <= t.hi; ++j) walk1_step(s, j, t.p(j), t.lo, t.hi);
-    const Vertex v = vertex_of(s, t.lo, t.hi, a.fit[t.y * 4 + 3] + (double)a.shift);
+    walk1_init<EMIT>(s);
+    for (int j = t.lo; j <= t.hi; ++j) walk1_step<EMIT>(s, j, t.p(j), t.lo, t.hi);
+    const Vertex v = vertex_of<EMIT>(s, t.lo, t.hi, a.fit[t.y * 4 + 3] + (double)a.shift, a.min_excess);
     t.out[0] = v.shift;
     t.out[a.plane_stride] = v.core;
-    t.out[2 * a.plane_stride] = crossings(cross_row(t, s.c.jb, v.thr), v.half, v.thr, 0.0).len;
+    t.out[2 * a.plane_stride] = crossings<EMIT>(cross_row<T, EMIT>(t, s.c.jb, v.thr), v.half, v.thr, 0.0).len;
     t.out[3 * a.plane_stride] = v.cog;
     t.out[4 * a.plane_stride] = v.ew;
 }
@@ -593,12 +632,14 @@ struct FinishArgs {
     uint16_t* png;
     int64_t png_plane, png_pitch;
     double shift_scale, width_scale;           // 32767 / R, 65534 / (2H + 1)
+    double rin, flux_div;                      // the emission maps': the ring's inner radius (rad: its outer one), 2H + 1
 };
 
 // One thread per output pixel, its P planes: P = 1 for the Dopplergram's shift map, kPlanes for the profile's, 2 KB for KB bisector
 // levels.  Display planes: shift and cog around 32768, core as it is, width and ew from 1 up; with KB > 0, planes q < KB (the
-// bisectors) around 32768 and the chords from 1 up.
-template <int P, int KB = 0>
+// bisectors) around 32768 and the chords from 1 up.  RING (the emission maps' mask policy): NaN on and inside the circle of radius
+// rin (none when rin < 0) and outside the one of radius rad, and the flux plane (4) divided by 2H + 1.
+template <int P, int KB = 0, bool RING = false>
 __global__ __launch_bounds__(256) void k_map_finish(const FinishArgs a) {
     const int64_t oc = (int64_t)blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
     if (oc >= a.nw) return;
@@ -616,7 +657,9 @@ __global__ __launch_bounds__(256) void k_map_finish(const FinishArgs a) {
         if (x1 >= 0.0 && x1 < w) i1 = (int64_t)x1;
         if (a.masked) {
             const double dx = (double)c - a.cx, dy = (double)r - a.cy;
-            off = dx * dx + dy * dy > a.rad * a.rad;
+            const double d2 = dx * dx + dy * dy;
+            off = d2 > a.rad * a.rad;
+            if (RING) off = off || (a.rin >= 0.0 && d2 <= a.rin * a.rin);
         }
     }
 #pragma unroll
@@ -635,6 +678,7 @@ __global__ __launch_bounds__(256) void k_map_finish(const FinishArgs a) {
                 const double e = KB > 0 ? (q < KB ? 32768.0 + (double)v * a.shift_scale : 1.0 + (double)v * a.width_scale)
                                  : q == 0 || q == 3 ? 32768.0 + (double)v * a.shift_scale
                                  : q == 1           ? (double)v
+                                 : RING && q == 4   ? (double)v / a.flux_div
                                                     : 1.0 + (double)v * a.width_scale;
                 d = (uint16_t)fmin(fmax(rint(e), 1.0), 65535.0);
             }
@@ -757,7 +801,7 @@ extern "C" int shg_doppler_finish(const float* raw, int64_t h, int64_t w, int64_
                                   int64_t out_h, int64_t out_w, const double* circle3, const int64_t* crop4, float* map,
                                   int64_t map_pitch, uint16_t* png, int64_t png_pitch, double display_range, shg_stream_t stream) {
     FinishArgs a{raw, 0, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, map, 0, map_pitch, png, 0, png_pitch,
-                 0.0, 0.0};
+                 0.0, 0.0, 0.0, 0.0};
     if (const int e = finish_args("shg_doppler_finish", 1, circle3, crop4, 0, display_range, a)) return e;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("doppler_finish", st);
@@ -785,12 +829,56 @@ extern "C" int shg_line_profile_finish(const float* raw, int64_t raw_plane_strid
                                        float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
                                        int64_t png_pitch, int half_width, double display_range, shg_stream_t stream) {
     FinishArgs a{raw, raw_plane_stride, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, maps,
-                 map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0};
+                 map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0, 0.0, 0.0};
     if (const int e = finish_args("shg_line_profile_finish", kPlanes, circle3, crop4, half_width, display_range, a)) return e;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("line_profile_finish", st);
     return shg::launch(k_map_finish<kPlanes>, dim3((unsigned)((a.nw + 255) / 256), (unsigned)out_h), dim3(256), 0, st, a,
                        "k_map_finish<5>");
+}
+
+extern "C" int shg_line_emission(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px,
+                                 int64_t frame_stride_px, const double* fit, int half_width, int shift, double min_excess, int flip_x,
+                                 float* planes, int64_t plane_stride, int64_t row_pitch, int64_t n_cols, int64_t k_offset,
+                                 shg_stream_t stream) {
+    if (const int e = check_map_args("shg_line_emission", stack, fit, planes, n_frames, height, width, bytes_per_px, frame_stride_px,
+                                     half_width, shift, kPlanes, plane_stride, row_pitch, n_cols, k_offset))
+        return e;
+    SHG_REQUIRE(isfinite(min_excess) && min_excess >= 0.0, SHG_E_ARG, "shg_line_emission: min_excess %g must be finite and >= 0",
+                min_excess);
+    const int64_t fstride = frame_stride_px > 0 ? frame_stride_px : height * width;
+    MapArgs a{stack, (int)n_frames, height, width, fstride, fit, half_width, shift, planes, plane_stride, row_pitch, n_cols, k_offset,
+              flip_x ? 1 : 0, 0, {}, min_excess};
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("line_emission", st);
+    return launch_map(
+        a, bytes_per_px, st, [](auto t, auto vec) { return k_line_profile_rot<decltype(t), decltype(vec)::value, true>; },
+        [](auto t) { return k_line_profile_plain<decltype(t), true>; }, "k_line_profile_rot<emission>", "k_line_profile_plain<emission>");
+}
+
+extern "C" int shg_line_emission_finish(const float* raw, int64_t raw_plane_stride, int64_t h, int64_t w, int64_t raw_pitch, double h00,
+                                        double h01, double h02, int64_t out_h, int64_t out_w, const double* ring4, const int64_t* crop4,
+                                        float* maps, int64_t map_plane_stride, int64_t map_pitch, uint16_t* png, int64_t png_plane_stride,
+                                        int64_t png_pitch, int half_width, double display_range, shg_stream_t stream) {
+    FinishArgs a{raw, raw_plane_stride, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, maps,
+                 map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0, 0.0, 0.0};
+    if (const int e = finish_args("shg_line_emission_finish", kPlanes, nullptr, crop4, half_width, display_range, a)) return e;
+    if (ring4) {
+        SHG_REQUIRE(!isnan(ring4[0]) && !isnan(ring4[1]) && !isnan(ring4[2]) && !isnan(ring4[3]) && ring4[3] >= 0.0 &&
+                        ring4[3] >= ring4[2],
+                    SHG_E_ARG, "shg_line_emission_finish: ring (%g, %g, %g, %g) needs numbers and 0 <= r_out >= r_in", ring4[0], ring4[1],
+                    ring4[2], ring4[3]);
+        a.masked = 1;
+        a.cx = ring4[0];
+        a.cy = ring4[1];
+        a.rin = ring4[2];
+        a.rad = ring4[3];
+    }
+    a.flux_div = (double)(2 * half_width + 1);
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("line_emission_finish", st);
+    return shg::launch(k_map_finish<kPlanes, 0, true>, dim3((unsigned)((a.nw + 255) / 256), (unsigned)out_h), dim3(256), 0, st, a,
+                       "k_map_finish<5, ring>");
 }
 
 extern "C" int shg_line_bisector(const void* stack, int64_t n_frames, int64_t height, int64_t width, int bytes_per_px,
@@ -838,7 +926,7 @@ extern "C" int shg_line_bisector_finish(const float* raw, int64_t raw_plane_stri
     SHG_REQUIRE(n_levels >= 1 && n_levels <= kMaxLevels, SHG_E_ARG, "shg_line_bisector_finish: %d levels (1 to %d)", n_levels,
                 kMaxLevels);
     FinishArgs a{raw, raw_plane_stride, h, w, raw_pitch, h00, h01, h02, out_h, out_w, 0, 0.0, 0.0, 0.0, 0, 0, 0, 0, maps,
-                 map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0};
+                 map_plane_stride, map_pitch, png, png_plane_stride, png_pitch, 0.0, 0.0, 0.0, 0.0};
     if (const int e = finish_args("shg_line_bisector_finish", 2 * n_levels, circle3, crop4, half_width, display_range, a)) return e;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("line_bisector_finish", st);

@@ -906,6 +906,34 @@ def line_bisector_finish(raw, h00, h01, h02, out_h, out_w, circle=None, crop=Non
                           display_range, planes // 2)
 
 
+# ---- the emission-line maps ---------------------------------------------------------------------------
+LINE_EMISSION_PLANES = ('shift', 'peak', 'width', 'cog', 'flux')
+
+
+def line_emission(stack, fit, half_width, shift=0, min_excess=0.0, flip_x=False, n_cols=None, k_offset=0, out=None):
+    """shg_line_emission: the five planes (LINE_EMISSION_PLANES, float32) of a line seen in emission, for every slit row and frame,
+    measured around the line shifted by `shift` pixels -> planes [5, ih, n_cols] as line_profile's.  Every plane is NaN unless the
+    window's first maximum is bracketed and rises min_excess (sample units, finite and >= 0) above the mean of the window's end
+    samples.  fit float64 [ih, 4] (host array or GPU tensor)."""
+    n, h, w, bpp, fit, n_cols, out = _line_map_setup(stack, fit, n_cols, k_offset, out, (len(LINE_EMISSION_PLANES),))
+    _lib.check(lib.shg_line_emission(stack.data_ptr(), n, h, w, bpp, frame_stride(stack), fit.data_ptr(), int(half_width), int(shift),
+                                     float(min_excess), int(bool(flip_x)), out.data_ptr(), out.stride(0), out.stride(1), n_cols,
+                                     int(k_offset), _stream()), 'shg_line_emission')
+    return out
+
+
+def line_emission_finish(raw, h00, h01, h02, out_h, out_w, ring=None, crop=None, half_width=None, display_range=None):
+    """shg_line_emission_finish: the five raw planes float32 [5, ih, N] of line_emission through doppler_finish's geometry, NaN on
+    and inside the circle of radius r_in and outside the one of radius r_out of `ring` (cx, cy, r_in, r_out; None: no mask; r_in < 0:
+    no inner mask; r_out may be inf) -> (maps float32 [5, out_h, nw], png uint16 [5, out_h, nw] or None).  Display planes with
+    half_width H and display_range R: 0 for NaN; shift and cog as the Dopplergram's, peak clip(rint(v), 1, 65535), width
+    clip(rint(1 + v * 65534 / (2H + 1)), 1, 65535), flux clip(rint(v / (2H + 1)), 1, 65535)."""
+    if ring is not None and len(ring) != 4:
+        raise ValueError('ring is (cx, cy, r_in, r_out)')
+    return _planes_finish('shg_line_emission_finish', len(LINE_EMISSION_PLANES), '5', raw, h00, h01, h02, out_h, out_w, ring, crop,
+                          half_width, display_range)
+
+
 # ---- removing a fitted plane from a finished map -----------------------------------------------------
 def map_plane_moments(m, circle=None, prev=None, out=None):
     """shg_map_plane_moments: the ten integer moments {N, sum c, sum r, sum c^2, sum c r, sum r^2, sum q, sum q c, sum q r, sum q^2}
