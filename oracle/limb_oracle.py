@@ -86,9 +86,9 @@ class LsqEllipse:
         return np.c_[x, y]
 
 
-def canny(image, sigma, low_threshold, high_threshold):
-    """skimage.feature.canny(image, sigma, low_threshold, high_threshold) for a float image
-    (dtype_max = 1, mask = all ones), scikit-image 0.18.3."""
+def canny_masks(image, sigma, low_threshold, high_threshold):
+    """skimage.feature.canny up to its hysteresis, for a float image (dtype_max = 1, mask = all ones),
+    scikit-image 0.18.3.  -> (low_mask, high_mask, magnitude, local_maxima)."""
     eps = np.finfo(float).eps
     mask = np.ones(image.shape, dtype=bool)
 
@@ -132,6 +132,11 @@ def canny(image, sigma, low_threshold, high_threshold):
 
     high_mask = local_maxima & (magnitude >= high_threshold)
     low_mask = local_maxima & (magnitude >= low_threshold)
+    return low_mask, high_mask, magnitude, local_maxima
+
+
+def hysteresis(low_mask, high_mask):
+    """canny's last step: the 8-connected components of low_mask that hold a pixel of high_mask."""
     labels, count = ndi.label(low_mask, np.ones((3, 3), bool))
     if count == 0:
         return low_mask
@@ -139,6 +144,13 @@ def canny(image, sigma, low_threshold, high_threshold):
     good_label = np.zeros((count + 1,), bool)
     good_label[1:] = sums > 0
     return good_label[labels]
+
+
+def canny(image, sigma, low_threshold, high_threshold):
+    """skimage.feature.canny(image, sigma, low_threshold, high_threshold) for a float image
+    (dtype_max = 1, mask = all ones), scikit-image 0.18.3."""
+    low_mask, high_mask, _, _ = canny_masks(image, sigma, low_threshold, high_threshold)
+    return hysteresis(low_mask, high_mask)
 
 
 def get_flood_image(image):                                         # ellipse_to_circle.py:148-228

@@ -651,10 +651,23 @@ def test_canny_masks_match_skimage_0_18_3(ops, orc, golden):
         np.testing.assert_array_equal(edges, g['canny%d' % i])
         idx, root = ops.edge_components(low_m, high_m)                 # the same on the GPU
         np.testing.assert_array_equal(idx, np.flatnonzero(edges))
-    # a noisy gray-level image (no flooding): thresholds that bite, real hysteresis
+    # every value of noisy * 65000 + 1 is above the flood threshold 0.5: the image floods to all ones, and canny sees the
+    # rounding noise of the bleed-over normalisation alone (the SciPy summation order), far below these thresholds
+    from oracle import limb_oracle
     noisy = g['noisy']
-    low_m, high_m = ops.canny_masks(dev(noisy * 65000.0 + 1.0), 0.5, 1.0, 0.05 * 65000, 0.12 * 65000)
+    blurred = noisy * 65000.0 + 1.0
+    assert blurred.min() >= 0.5
+    low_m, high_m = ops.canny_masks(dev(blurred), 0.5, 1.0, 0.05 * 65000, 0.12 * 65000)
     assert host(low_m).shape == noisy.shape
+    want_low, want_high, _, _ = limb_oracle.canny_masks(np.where(blurred < 0.5, 0.0, 65000.0), 1.0, 0.05 * 65000, 0.12 * 65000)
+    np.testing.assert_array_equal(host(low_m).astype(bool), want_low)
+    np.testing.assert_array_equal(host(high_m).astype(bool), want_high)
+    # (those masks are empty; with zero thresholds the local maxima of that noise are the masks)
+    low_m, high_m = ops.canny_masks(dev(blurred), 0.5, 1.0, 0.0, 0.0)
+    want_low, want_high, _, _ = limb_oracle.canny_masks(np.full(noisy.shape, 65000.0), 1.0, 0.0, 0.0)
+    assert want_low.any()
+    np.testing.assert_array_equal(host(low_m).astype(bool), want_low)
+    np.testing.assert_array_equal(host(high_m).astype(bool), want_high)
 
 
 def test_limb_points_stage_matches_oracle(ops, golden):
