@@ -1,14 +1,20 @@
-// CLAHE and image histograms.
+// CLAHE, image histograms and the exact order statistics that follow them.
 // Replaces cv2.createCLAHE(clipLimit, (t, t)).apply() (reference solex_util.py:532-533,
 // clahe_apply.py:247) and feeds np.percentile / np.max (solex_util.py:535-537).
 // Restated from OpenCV 4.x imgproc/clahe.cpp: per-tile histogram -> clip ->
 // redistribute -> cumulative LUT (float32 scale, round half even) -> per-pixel
 // bilinear blend of the four neighbouring tile LUTs in float32, unfused.
 //
-// The image is a few MB, so the stage is bound by the 65536-bin histogram scatter
-// and by launch latency, not by HBM streaming.  Histogram: every workgroup owns a
-// private 65536 x u16 LDS histogram (128 KiB) for a slice of <= 65535 pixels of one
-// tile and flushes only its non-zero bins with global atomics.
+// The image is a few MB, so the stage is bound by the 65536-bin histogram scatter and by launch latency, not by HBM streaming.
+// Three histogram routes (plan_clahe below decides):
+//   * slices, the default for 16-bit images: every workgroup counts a slice of one tile in a private 65536 x u16 LDS histogram
+//     (128 KiB) and stores it whole -- or, where the clip limit fits a byte and nobody needs the true counts, clamped to bytes or
+//     nibbles -- then one reduction adds a tile's slices up and 32 workgroups per tile build its LUT: no atomics, no memset, any
+//     number of disks per launch, and the frame's percentiles and the next select's first pass ride along;
+//   * 16-bit atomics, for a workspace without the slices' room or a clip out of the u16 range: the same LDS histogram, its non-zero
+//     bins flushed into a zeroed tile histogram with global atomics;
+//   * 8-bit atomics, for 8-bit images: 256-bin histograms.
+// The kernels come first, all host code (tuning, workspace layouts, the plan, the launches, the C ABI) after the last of them.
 #include <stdlib.h>
 #include <type_traits>
 #include <algorithm>
@@ -1645,380 +1651,485 @@ __global__ __launch_bounds__(1024) void k_hist_ranks(const HistRanksArgs kargs) 
     hist_rank_job(hist, chunk_sums, chunk_sets, ntiles, ranks.v[blockIdx.x], out + blockIdx.x);
 }
 
-void ensure_lds_attr() {
-    static const bool done = [] {                        // (a function-local static: once, also with several pool threads here)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist16), hipFuncAttributeMaxDynamicSharedMemorySize, HIST16 * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist16_slices<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, HIST16 * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist16_slices<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, HIST16 * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist16_slices<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, HIST16 * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist16_slices<true, 16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  HIST16 * 2 + kFusedMaxSliceRows * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist16_slices<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  HIST16 * 2 + kFusedMaxSliceRows * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist16_slices<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  HIST16 * 2 + kFusedMaxSliceRows * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_lut16_blocks<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2048 * 16 * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_lut16_blocks<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2048 * 16 * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_image_hist16), hipFuncAttributeMaxDynamicSharedMemorySize, HIST16 * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_lut16_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (HIST16 + HIST16 / 64) * 2);
-        return true;
-    }();
-    (void)done;
-}
+// ---- host code: tuning, workspace layouts, the plan, the launches ---------------------------------------------------------
 
-}  // namespace
-
-extern "C" size_t shg_clahe_workspace_bytes(int tiles, int bytes_per_px) {
-    if (tiles < 1 || tiles > 16 || (bytes_per_px != 1 && bytes_per_px != 2)) return 0;
-    const size_t hist = bytes_per_px == 1 ? 256 : HIST16;
-    return (size_t)tiles * tiles * hist * (sizeof(uint32_t) + sizeof(uint16_t));
-}
-
-namespace {
-// sel_hist (may be NULL): the zeroed slot histograms of the select that follows on dst; the kernel then counts its first pass
-// The disks of one launch: their images, where their results go, how many, and the byte distance between their workspaces.
-struct RanksJob {                                        // two order statistics of every disk's frame -> out[disk * out_zstride + {0, 1}]
-    int64_t rank[2];
-    double* out;
-    int out_zstride;
+// Every environment knob of this file (INTEGRATION.md documents them for users):
+//   knob                 meaning                                                                  default              read
+//   SHG_INTERP_TILED     0: the blend deals its lanes along rows instead of in tiles              tiled                once per process
+//   SHG_INTERP_SHAPE     the blend's tile, lw | wx << 4 | (8 px a lane) << 8                      2 | 2 << 4, 8 px     every call: a test compares
+//                                                                                                 from four disks up   the lane widths in one process
+//   SHG_CLAHE_SLICE_PX   pixels per u16 histogram slice of a stack of disks (<= 65535)            65535                once per process
+//   SHG_CLAHE_BIG_FROM   disks per launch from which those big slices are taken                   4                    once per process
+//   SHG_CLAHE_SAT        0: never the clamped counters; 8: bytes even where nibbles would do      1 (where they fit)   every call: the tests hold one
+//   SHG_CLAHE_SAT_PX     pixels per slice of the clamped counters                                 0 (chosen by cost)   setting against another
+//   SHG_SELECT_WGS       workgroups in all of a select pass over several disks                    2048                 once per process
+//   SHG_SELECT_WINDOW    0 / 1: never / always the percentile window                              from four disks up   every call: the tests run both
+//   SHG_CONTRAST_BATCH   0: every disk through shg_contrast_stats_u16, one after the other        batched              every call: the tests run both
+// (once per process: sweeps set these before the process starts, nothing sets them in it; the first read_tuning() latches all four)
+struct Tuning {
+    bool interp_tiled, contrast_batch;
+    int interp_shape, big_from, sat_mode, select_window;     // (select_window: 0 / 1, or -1: from four disks a launch on)
+    int64_t slice_px, sat_px, select_wgs;
+    bool window_for(int disks) const { return select_window < 0 ? disks >= 4 : select_window != 0; }
 };
+inline int env_int(const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; }
+inline bool env_is(const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; }
+inline Tuning read_tuning() {
+    static const Tuning once = [] {                      // (a function-local static: once, also with several pool threads here)
+        Tuning t = {};
+        t.interp_tiled = !env_is("SHG_INTERP_TILED", '0');
+        t.slice_px = env_int("SHG_CLAHE_SLICE_PX", 65535);
+        t.big_from = env_int("SHG_CLAHE_BIG_FROM", 4);
+        t.select_wgs = env_int("SHG_SELECT_WGS", 2048);
+        return t;
+    }();
+    Tuning t = once;
+    t.interp_shape = env_int("SHG_INTERP_SHAPE", 0);
+    t.sat_mode = env_int("SHG_CLAHE_SAT", 1);
+    t.sat_px = std::max(env_int("SHG_CLAHE_SAT_PX", 0), 0);
+    t.select_window = env_is("SHG_SELECT_WINDOW", '0') ? 0 : env_is("SHG_SELECT_WINDOW", '1') ? 1 : -1;
+    t.contrast_batch = !env_is("SHG_CONTRAST_BATCH", '0');
+    return t;
+}
+
+// tile geometry as OpenCV pads it (copyMakeBorder(0, t - h%t, 0, t - w%t, REFLECT_101), clahe.cpp)
+inline void tile_geometry(int64_t h, int64_t w, int tiles, int64_t* th, int64_t* tw) {
+    const bool pad = h % tiles != 0 || w % tiles != 0;
+    *th = (pad ? h + (tiles - h % tiles) : h) / tiles;
+    *tw = (pad ? w + (tiles - w % tiles) : w) / tiles;
+}
+
+// a tile's slices are runs of whole rows holding at most slice_px pixels (a tile row longer than that: one row a slice --
+// the u16 counters of such a slice can wrap, and plan_clahe keeps those images off the slice route)
+inline int64_t slice_rows_of(int64_t tw, int64_t slice_px) { return tw >= slice_px ? 1 : slice_px / tw; }
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+constexpr size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+
+// The CLAHE workspace: [hist | lut] (shg_clahe_workspace_bytes), then for the slice route of a 16-bit image, from the next
+// multiple of 256 bytes on, [slices | chunk sums | se] (shg_clahe_workspace_bytes_for).  Offsets in bytes.
+struct ClaheLayout {
+    size_t lut, small;               // [hist | lut]: where the LUTs start, where they end
+    size_t slices, chunk, se, total; // h, w > 0 and 16 bits: the slice route's areas; else total == small
+    int64_t n_slices;                // u16 slice histograms per tile that `slices` has room for (SLICE_PX pixels each)
+};
+inline ClaheLayout clahe_layout(int64_t h, int64_t w, int tiles, int bytes_per_px) {
+    const size_t ntiles = (size_t)tiles * tiles, hist_size = bytes_per_px == 1 ? 256 : HIST16;
+    ClaheLayout l = {};
+    l.lut = ntiles * hist_size * sizeof(uint32_t);
+    l.small = l.total = l.lut + ntiles * hist_size * sizeof(uint16_t);
+    if (bytes_per_px != 2 || h <= 0 || w <= 0) return l;
+    int64_t th, tw;
+    tile_geometry(h, w, tiles, &th, &tw);
+    l.n_slices = ceil_div(th, slice_rows_of(tw, SLICE_PX));
+    l.slices = up256(l.small);
+    l.chunk = l.slices + ntiles * (size_t)l.n_slices * (HIST16 / 2) * sizeof(uint32_t);
+    l.se = l.chunk + ntiles * 1024 * sizeof(uint32_t);
+    l.total = l.se + ntiles * 128 * sizeof(int32_t);         // (32 x 2 for the u16 slices, 128 for the saturated ones)
+    return l;
+}
+
+// The contrast-stats workspace: [clahe | select2 | select3 + window + SelWin | chunk sums], every area a multiple of 256 bytes.
+// select<n>: SEL_SLOTS copies of the (1 + n) histograms of an n-rank select, then its ranks; the window: SEL_WIN_WORDS counts.
+inline size_t select_bytes(int n_ranks) { return (size_t)SEL_SLOTS * (1 + n_ranks) * 256 * sizeof(uint32_t) + (size_t)n_ranks * sizeof(int64_t); }
+struct StatsLayout { size_t select2, select3, chunk_sums, total; };      // (the CLAHE area starts at 0 and ends at select2)
+inline StatsLayout stats_layout(size_t clahe_bytes) {
+    StatsLayout l;
+    l.select2 = up256(clahe_bytes);
+    l.select3 = l.select2 + up256(select_bytes(2));
+    l.chunk_sums = l.select3 + up256(select_bytes(3) + (size_t)SEL_WIN_WORDS * sizeof(uint32_t) + sizeof(SelWin));
+    l.total = l.chunk_sums + up256(1024 * sizeof(uint32_t));       // 64-bin chunk sums of the summed tile histograms
+    return l;
+}
+
+// ---- requests and results --------------------------------------------------------------------------------------------------
+// The disks of one launch: their images, where their results go, how many, and the byte distance between their workspaces.
 struct Disks {
     shg::PtrBatch src, dst;
     int n;
     size_t zs;
     bool fused = false;              // src is still to be made, from `from` (k_tile_hist16_slices<true>)
     FusedSrc from = {};
-    bool aligned(unsigned mask) const {
+    uintptr_t bits_of(const shg::PtrBatch& b) const {         // OR of a batch's pointers: what the alignment decisions need
         uintptr_t bits = 0;
-        for (int i = 0; i < n; ++i) bits |= reinterpret_cast<uintptr_t>(src.p[i]) | reinterpret_cast<uintptr_t>(dst.p[i]);
-        return (bits & mask) == 0;
+        for (int i = 0; i < n; ++i) bits |= reinterpret_cast<uintptr_t>(b.p[i]);
+        return bits;
+    }
+    bool from_in_vectors(int64_t w) const {      // the fused histogram may read its raw source in 16-byte vectors
+        return (bits_of(from.raw) & 15) == 0 && from.raw_pitch % 8 == 0 && from.sx0 == 0 && from.dx0 == 0 && from.ncopy == w;
     }
 };
 inline Disks one_disk(const void* src, void* dst) {
-    Disks d;
-    d.src = {};
-    d.dst = {};
+    Disks d = {};
     d.src.p[0] = src;
     d.dst.p[0] = dst ? dst : src;
     d.n = 1;
-    d.zs = 0;
     return d;
 }
+struct Shape { int64_t h, w, pitch, dst_pitch; int bytes_per_px; double clip_limit; int tiles; };
+struct RanksJob { int64_t rank[2]; double* out; int out_zstride; };    // two order statistics (0-based, from the bottom) of every disk's frame -> out[disk * out_zstride + {0, 1}]
+struct ClaheRequest {
+    Disks disks;                     // several images of one shape go through one launch per kernel, disk i working in the workspace
+    Shape im;                        // at `workspace + i * disks.zs`; only the slice route takes more than one
+    void* workspace; size_t workspace_bytes; shg_stream_t stream;
+    bool want_chunks = false;        // the caller reads ClaheResult::chunk_tile: the slices keep the true counts unless `ranks` rides along
+    uint32_t* sel_hist = nullptr;    // the slot histograms of the select that follows on dst: zeroed on the way, and the blend
+    int sel_stride = 0;              // kernel counts the select's first pass where it can; words per slot
+    bool want_window = false;        // sel_hist has the window's room behind its slots (stats_layout) and wants it used
+    const RanksJob* ranks = nullptr; // the frame's order statistics ride on the LUT kernel
+};
+struct ClaheResult {
+    int err = 0;
+    const uint32_t* chunk_tile = nullptr;    // where the per-tile 64-bin chunk sums were left; NULL: the call took an atomics route
+    bool sel_zeroed = false;                 // sel_hist is zero but for what the blend counted (by the histogram reduction, or a memset)
+    bool pass0_done = false;                 // sel_hist holds the high-byte counts of dst: the select starts at its second pass
+    bool window_used = false;                // ... and the window's counts (SelWin behind the slots)
+    bool ranks_done = false;                 // the ranks job ran
+};
 
-inline int launch_interp16(const Disks& d, int64_t h, int64_t w, int64_t pitch, int tiles, float inv_tw, float inv_th,
-                           const uint16_t* lut, bool value_major, int64_t dst_pitch, uint32_t* sel_hist, int sel_stride,
-                           hipStream_t st, bool* counted, bool sel_window = false) {
-    *counted = false;
-    const unsigned nz = (unsigned)d.n;
-    if (!value_major) {                                  // (single image only: the caller checked)
-        k_clahe_interp<uint16_t, HIST16><<<dim3((unsigned)((w + 255) / 256), (unsigned)h), 256, 0, st>>>(
-            static_cast<const uint16_t*>(d.src.p[0]), h, w, pitch, tiles, inv_tw, inv_th, lut, static_cast<uint16_t*>(const_cast<void*>(d.dst.p[0])), dst_pitch);
-        return shg::check_launch("k_clahe_interp");
-    }
-    const bool vec = d.aligned(7) && pitch % 4 == 0 && dst_pitch % 4 == 0;
-    auto blocks = [&](int px, int rounds) {              // workgroups for the flat (row, vector) sequence
-        const int64_t lanes = ((w + px - 1) / px) * h;
-        return (unsigned)((lanes + 256 * (int64_t)rounds - 1) / (256 * (int64_t)rounds));
-    };
-    static const bool tiled_ok = [] { const char* v = getenv("SHG_INTERP_TILED"); return !(v && v[0] == '0'); }();
-    InterpVmArgs a{d.src, h, w, pitch, tiles, inv_tw, inv_th, lut, d.dst, dst_pitch, 1, nullptr, 0, d.zs, 0, 1u, 0};
-    if (vec && sel_hist) {
-        const int rows = 4;                              // rounds per workgroup: amortises the histogram's zeroing and flush
-        a.rows = rows;
-        a.sel_hist = sel_hist;
-        a.sel_stride = sel_stride;
-        a.sel_window = sel_window ? 1 : 0;
-        *counted = true;
-        if (tiled_ok) {
-            // 4 lanes x 16 rows per wave, 4 waves across: 64 pixels x 16 rows a round (measured over 21 disks: 243 us; 2 waves
-            // across 242, one 270; 2 lanes x 32 rows 262-384; 8 lanes x 8 rows 246-253; the flat sequence 300)
-            // Eight pixels a lane (16-byte loads and stores) from four disks up: 222 us against 243 over 21 disks -- and 17.5 against 13.7 us
-            // on one, where the launch is too small to fill the device.  (SHG_INTERP_SHAPE = lw | wx << 4 | (8 px) << 8: tools' sweeps;
-            // halving the kernel's L2 requests this way does not change what it costs a pass A beside it, profiles/r04_sweeps.txt.)
-            const char* shape_env = getenv("SHG_INTERP_SHAPE");      // (read per call: a test compares the two lane widths in one process)
-            const int shape = shape_env ? atoi(shape_env) : 0;
-            const int lw = shape ? (shape & 15) : 2, wx = shape ? ((shape >> 4) & 15) : 2;
-            const bool px8 = (shape ? ((shape >> 8) & 1) != 0 : nz >= 4) && d.aligned(15) && pitch % 8 == 0 && dst_pitch % 8 == 0;
-            const int pxn = px8 ? 8 : 4;
-            const int64_t wg_px = (int64_t)pxn << (lw + wx), wg_rows = (int64_t)(64 >> lw) * (4 >> wx);
-            const uint32_t tx = (uint32_t)((w + wg_px - 1) / wg_px), ty = (uint32_t)((h + wg_rows * rows - 1) / (wg_rows * rows));
-            a.tiled = 0x10000 | lw | (wx << 8);
-            a.tiles_x = tx;
-            const dim3 g(tx * ty, 1u, nz);
-            if (tiles == 2) return px8 ? shg::launch(k_clahe_interp_vm<8, true, true>, g, dim3(256), 0, st, a, "k_clahe_interp_vm")
-                                       : shg::launch(k_clahe_interp_vm<4, true, true>, g, dim3(256), 0, st, a, "k_clahe_interp_vm");
-            if (px8) return shg::launch(k_clahe_interp_vm<8, true, false>, g, dim3(256), 0, st, a, "k_clahe_interp_vm");
-            return shg::launch(k_clahe_interp_vm<4, true, false>, g, dim3(256), 0, st, a, "k_clahe_interp_vm");
-        }
-        if (tiles == 2) return shg::launch(k_clahe_interp_vm<4, true, true>, dim3(blocks(4, rows), 1u, nz), dim3(256), 0, st, a, "k_clahe_interp_vm");
-        return shg::launch(k_clahe_interp_vm<4, true, false>, dim3(blocks(4, rows), 1u, nz), dim3(256), 0, st, a, "k_clahe_interp_vm");
-    }
-    if (vec) return tiles == 2 ? shg::launch(k_clahe_interp_vm<4, false, true>, dim3(blocks(4, 1), 1u, nz), dim3(256), 0, st, a, "k_clahe_interp_vm")
-                               : shg::launch(k_clahe_interp_vm<4, false, false>, dim3(blocks(4, 1), 1u, nz), dim3(256), 0, st, a, "k_clahe_interp_vm");
-    return tiles == 2 ? shg::launch(k_clahe_interp_vm<1, false, true>, dim3(blocks(1, 1), 1u, nz), dim3(256), 0, st, a, "k_clahe_interp_vm")
-                      : shg::launch(k_clahe_interp_vm<1, false, false>, dim3(blocks(1, 1), 1u, nz), dim3(256), 0, st, a, "k_clahe_interp_vm");
-}
+struct SelectRequest {
+    Disks disks;                     // src: the images; disk i with its histograms at workspace + i * zs and its results at out + i * out_zstride
+    int64_t h, w, pitch;
+    const int64_t* ranks; int n_ranks;       // host array
+    double* out; int out_zstride;
+    void* workspace; size_t workspace_bytes; shg_stream_t stream;
+    ClaheResult after = {};          // what the CLAHE call on these histograms left in them (sel_zeroed: required for several disks)
+};
 
-// tile geometry as OpenCV pads it (copyMakeBorder(0, t - h%t, 0, t - w%t, REFLECT_101), clahe.cpp)
-inline void tile_geometry(int64_t h, int64_t w, int tiles, int64_t* th, int64_t* tw) {
-    int64_t he = h, we = w;
-    if (!(w % tiles == 0 && h % tiles == 0)) {
-        he = h + (tiles - h % tiles);
-        we = w + (tiles - w % tiles);
-    }
-    *th = he / tiles;
-    *tw = we / tiles;
-}
+// ---- the plan: which kernels a CLAHE call runs, and how (the routes: the head of this file) --------------------------------
+enum class Route { Atomics8, Atomics16, Slices16, Slices8, Slices4 };          // (slices: with 16-, 8- or 4-bit counters)
+inline bool is_slices(Route r) { return r >= Route::Slices16; }
 
-// a tile's slices are runs of whole rows holding at most slice_px pixels (a tile row longer than that: one row a slice --
-// the u16 counters of such a slice can wrap, and clahe_impl keeps those images off this path)
-inline int64_t slice_rows_of(int64_t tw, int64_t slice_px) { return tw >= slice_px ? 1 : slice_px / tw; }
-inline int64_t slice_count(int64_t th, int64_t tw, int64_t slice_px) {
-    const int64_t rows = slice_rows_of(tw, slice_px);
-    return (th + rows - 1) / rows;
-}
+struct Plan {
+    int err; char msg[120];          // 0, or the SHG_E_ code with its text in msg: nothing may be launched
+    Route route;
+    ClaheLayout lay;
+    int ntiles, clip;
+    int64_t th, tw, area;
+    float lut_scale;
+    // the slice routes only, from here on.  The histograms: bits of a counter, 16-byte loads, the slices' shape
+    int bits, hist_vec;
+    int64_t slice_rows, slices, chunk_rows;
+    bool window;                     // the reduction zeroes the window's counts with the select's, the blend counts it
+    bool lut_all_tiles;              // a LUT workgroup builds its 2048 entries for every tile
+    int64_t lut_rank[2];             // the frame's ranks as the LUT kernel takes them: from the bottom, or on the clamped routes the k-th largest
+    // the blend: pixels a lane (1, 4, 8); the select's first pass rides along; rounds per workgroup; 0 for the flat (row, vector)
+    // sequence or 0x10000 | lw | wx << 8; workgroups across; workgroups in all
+    int blend_px, blend_rounds, blend_tiled;
+    bool blend_counts;
+    uint32_t blend_tiles_x, blend_blocks;
+};
 
-// extra workspace of the atomics-free 16-bit path, after the [hist | lut] block: slice histograms, chunk sums, se
-struct FastLayout { size_t part, chunk, se, total; int64_t slices; };
-inline FastLayout fast_layout(int64_t h, int64_t w, int tiles) {
-    int64_t th, tw;
-    tile_geometry(h, w, tiles, &th, &tw);
-    FastLayout f;
-    const size_t ntiles = (size_t)tiles * tiles;
-    f.slices = slice_count(th, tw, SLICE_PX);
-    f.part = 0;
-    f.chunk = ntiles * (size_t)f.slices * (HIST16 / 2) * sizeof(uint32_t);
-    f.se = f.chunk + ntiles * 1024 * sizeof(uint32_t);
-    f.total = f.se + ntiles * 128 * sizeof(int32_t);         // (32 x 2 for the u16 slices, 128 for the saturated ones)
-    return f;
-}
-}  // namespace
+#define PLAN_REQUIRE(cond, code, ...) \
+    do { if (!(cond)) { p.err = (code); snprintf(p.msg, sizeof(p.msg), __VA_ARGS__); return p; } } while (0)
 
-extern "C" size_t shg_clahe_workspace_bytes_for(int64_t h, int64_t w, int tiles, int bytes_per_px) {
-    const size_t base = shg_clahe_workspace_bytes(tiles, bytes_per_px);
-    if (base == 0 || h <= 0 || w <= 0) return 0;
-    if (bytes_per_px != 2) return base;
-    return (base + 255) / 256 * 256 + fast_layout(h, w, tiles).total;
-}
-
-namespace {
-// chunk_tile_out (may be NULL): where the per-tile 64-bin chunk sums were left, or NULL when the call took the
-// histogram-with-atomics path (small workspace, 8-bit image, clip out of the u16 range).
-// disks (may be NULL: the one image img -> dst): several images of one shape in one launch per kernel, disk i working in the
-// workspace at `workspace + i * disks->zs`; only the atomics-free 16-bit path takes more than one.
-int clahe_impl(const void* img, int64_t h, int64_t w, int64_t pitch, int bytes_per_px, double clip_limit, int tiles,
-               void* dst, int64_t dst_pitch, void* workspace, size_t workspace_bytes, shg_stream_t stream, const uint32_t** chunk_tile_out,
-               uint32_t* sel_hist, int sel_stride, bool* sel_pass0_done, const Disks* disks = nullptr, bool* sel_zeroed = nullptr,
-               const RanksJob* ranks_job = nullptr, bool* ranks_done = nullptr, bool* sel_window = nullptr) {
-    // sel_window (in / out): the caller's sel_hist has the window's room behind its slots (select_window_bytes) and wants it used;
-    // -> false when this call did not take the path that fills it
-    const bool want_window = sel_window && *sel_window;
-    if (sel_window) *sel_window = false;
-    if (ranks_done) *ranks_done = false;
-    if (sel_zeroed) *sel_zeroed = false;                 // -> true when the histogram reduction has zeroed sel_hist (the caller asked by passing it)
-    if (chunk_tile_out) *chunk_tile_out = nullptr;
-    if (sel_pass0_done) *sel_pass0_done = false;
-    SHG_REQUIRE(img && dst && workspace, SHG_E_ARG, "shg_clahe: null pointer");
-    const Disks dset = disks ? *disks : one_disk(img, dst);
-    SHG_REQUIRE(h > 0 && w > 0 && pitch >= w && dst_pitch >= w, SHG_E_ARG, "shg_clahe: bad image size");
-    SHG_REQUIRE(bytes_per_px == 1 || bytes_per_px == 2, SHG_E_ARG, "shg_clahe: bytes_per_px must be 1 or 2");
-    SHG_REQUIRE(tiles >= 1 && tiles <= 16, SHG_E_UNSUPPORTED, "shg_clahe: tiles must be in 1..16");
-    SHG_REQUIRE(h < 65536, SHG_E_UNSUPPORTED, "shg_clahe: more than 65535 rows");
-    SHG_REQUIRE(workspace_bytes >= shg_clahe_workspace_bytes(tiles, bytes_per_px), SHG_E_WORKSPACE, "shg_clahe: workspace too small");
+// No HIP call in here, and no pointer followed: the same function answers "would this shape take the slices?" (batched_route).
+inline Plan plan_clahe(const ClaheRequest& r, const Tuning& tune) {
+    Plan p = {};
+    const Disks& d = r.disks;
+    const int64_t h = r.im.h, w = r.im.w, pitch = r.im.pitch, dst_pitch = r.im.dst_pitch;
+    const int tiles = r.im.tiles, bytes_per_px = r.im.bytes_per_px;
+    PLAN_REQUIRE(h > 0 && w > 0 && pitch >= w && dst_pitch >= w, SHG_E_ARG, "shg_clahe: bad image size");
+    PLAN_REQUIRE(bytes_per_px == 1 || bytes_per_px == 2, SHG_E_ARG, "shg_clahe: bytes_per_px must be 1 or 2");
+    PLAN_REQUIRE(tiles >= 1 && tiles <= 16, SHG_E_UNSUPPORTED, "shg_clahe: tiles must be in 1..16");
+    PLAN_REQUIRE(h < 65536, SHG_E_UNSUPPORTED, "shg_clahe: more than 65535 rows");
+    p.lay = clahe_layout(h, w, tiles, bytes_per_px);
+    PLAN_REQUIRE(r.workspace_bytes >= p.lay.small, SHG_E_WORKSPACE, "shg_clahe: workspace too small");
     // a reflect-101 extension needs at least `tiles` + 1 pixels along an extended axis
-    SHG_REQUIRE((h % tiles == 0 && w % tiles == 0) || (h > tiles && w > tiles), SHG_E_UNSUPPORTED, "shg_clahe: image smaller than the tile grid");
-    hipStream_t st = shg::as_stream(stream);
+    PLAN_REQUIRE((h % tiles == 0 && w % tiles == 0) || (h > tiles && w > tiles), SHG_E_UNSUPPORTED, "shg_clahe: image smaller than the tile grid");
     const int hist_size = bytes_per_px == 1 ? 256 : HIST16;
-    const int ntiles = tiles * tiles;
-    int64_t th, tw;
-    tile_geometry(h, w, tiles, &th, &tw);
-    const int64_t area = th * tw;
-    SHG_REQUIRE(area < (1ll << 31), SHG_E_UNSUPPORTED, "shg_clahe: tile too large");
-    const float lut_scale = (float)(hist_size - 1) / (float)area;
-    int clip = 0;
-    if (clip_limit > 0.0) {
-        clip = (int)(clip_limit * (double)area / hist_size);
-        clip = clip > 1 ? clip : 1;
+    p.ntiles = tiles * tiles;
+    tile_geometry(h, w, tiles, &p.th, &p.tw);
+    const int64_t th = p.th, tw = p.tw;
+    p.area = th * tw;
+    PLAN_REQUIRE(p.area < (1ll << 31), SHG_E_UNSUPPORTED, "shg_clahe: tile too large");
+    p.lut_scale = (float)(hist_size - 1) / (float)p.area;
+    if (r.im.clip_limit > 0.0) p.clip = std::max((int)(r.im.clip_limit * (double)p.area / hist_size), 1);
+    const int clip = p.clip;
+
+    if (!(bytes_per_px == 2 && clip > 0 && clip <= 65535 && tw <= 65535 && r.workspace_bytes >= p.lay.total)) {
+        PLAN_REQUIRE(d.n == 1 && !d.fused, SHG_E_UNSUPPORTED, "shg_clahe: several disks per launch need the roomy 16-bit workspace");
+        p.route = bytes_per_px == 2 ? Route::Atomics16 : Route::Atomics8;
+        return p;
     }
-    uint32_t* hist = static_cast<uint32_t*>(workspace);
-    uint16_t* lut = reinterpret_cast<uint16_t*>(hist + (size_t)ntiles * hist_size);
-    const float inv_tw = 1.0f / (float)tw, inv_th = 1.0f / (float)th;
-    dim3 igrid((unsigned)((w + 255) / 256), (unsigned)h);
-    if (bytes_per_px == 2 && clip > 0 && clip <= 65535 && tw <= 65535 && workspace_bytes >= shg_clahe_workspace_bytes_for(h, w, tiles, 2)) {
-        // no atomics, no memset: slice histograms stored whole, one reduction, the LUT by 32 workgroups per tile
-        ensure_lds_attr();
-        const FastLayout f = fast_layout(h, w, tiles);
-        char* extra = static_cast<char*>(workspace) + (shg_clahe_workspace_bytes(tiles, 2) + 255) / 256 * 256;
-        uint32_t* part = reinterpret_cast<uint32_t*>(extra + f.part);
-        uint32_t* chunk_tile = reinterpret_cast<uint32_t*>(extra + f.chunk);
-        int32_t* se = reinterpret_cast<int32_t*>(extra + f.se);
-        bool sat_path = false;
-        int64_t sat_k_top[2] = {0, 0};
-        { SHG_PROF("clahe_hist", st);
-          const unsigned nz = (unsigned)dset.n;
-          // One image: 32768-pixel slices spread a tile over enough workgroups to fill the chip.  A stack of disks fills it
-          // anyway: the largest slice a u16 counter allows halves the slice histograms written here and read back by the
-          // reduction (the layout's f.slices is the upper bound the workspace was sized for).
-          static const int64_t big = [] { const char* v = getenv("SHG_CLAHE_SLICE_PX"); return v ? (int64_t)atoi(v) : (int64_t)65535; }();
-          static const int big_from = [] { const char* v = getenv("SHG_CLAHE_BIG_FROM"); return v ? atoi(v) : 4; }();      // disks per launch from which the big slices are taken
-          // Saturated counters (k_tile_hist16_slices<., 8 / 4>): whenever the clip limit fits a byte and nobody needs the true counts
-          // -- the frame's order statistics may ride along when they lie within `clip` pixels of the top (np.percentile(frame, 99.9999)
-          // of a 4 Mpx image: the 5th and 6th largest), a caller who wants the chunk sums (shg_contrast_stats_u16) gets the u16 slices.
-          // (read at every call, three getenv: the tests hold one setting against another in one process)
-          const int sat_mode = [] { const char* v = getenv("SHG_CLAHE_SAT"); return v ? atoi(v) : 1; }();         // 0: never; 8: bytes even where nibbles would do
-          const int64_t sat_px = [] { const char* v = getenv("SHG_CLAHE_SAT_PX"); return v && atoi(v) > 0 ? (int64_t)atoi(v) : (int64_t)0; }();      // pixels per slice (0: chosen below)
-          const bool want_ranks = ranks_job && ranks_done;
-          bool sat = sat_mode != 0 && clip <= 255 && tw <= 65280 && (chunk_tile_out == nullptr || want_ranks);
-          int64_t k_top[2] = {0, 0};
-          if (sat && want_ranks) {
-              for (int r = 0; r < 2; ++r) {
-                  k_top[r] = h * w - ranks_job->rank[r];         // rank (from the bottom, 0-based) -> the k-th largest
-                  sat = sat && k_top[r] >= 1 && k_top[r] <= clip;
-              }
-          }
-          const int bits = !sat ? 16 : (clip <= 15 && sat_mode != 8 ? 4 : 8);
-          int64_t slice_px = (dset.n >= big_from && big > SLICE_PX && big <= 65535) ? big : SLICE_PX;
-          if (sat && sat_px) slice_px = sat_px;
-          const int64_t chunk_rows = slice_rows_of(tw, 65280);                    // (sat: rows counted between two clamps of the u16 counters)
-          int64_t slice_rows = slice_rows_of(tw, slice_px), slices = slice_count(th, tw, slice_px);
-          if (sat) {
-              // as many slices as the byte sums of k_hist_reduce_sat hold (256) and the workspace has room for (sized for f.slices u16 slices)
-              const int64_t max_slices = std::min<int64_t>(256, f.slices * (16 / bits));
-              if (!sat_px) {
-                  // A slice may be any length now, and a workgroup has a CU to itself (its histogram is 128 KB of the 160 KB of LDS): the
-                  // launch takes ceil(workgroups / CUs) rounds of one slice each.  The number of slices per tile that makes rounds x
-                  // (pixels of a slice + what zeroing, clamping and storing 64 K counters costs, about 8000 pixels' worth) smallest:
-                  // 63 at one 2000 x 2098 disk (252 workgroups, one round), 3 for a stack of 21 (252 again) -- not the 4 that
-                  // would leave two thirds of the chip idle in a second round.
-                  int64_t best = 1, best_cost = INT64_MAX;
-                  for (int64_t sl = 1; sl <= std::min<int64_t>(max_slices, th); ++sl) {
-                      const int64_t rows = (th + sl - 1) / sl, n_sl = (th + rows - 1) / rows;
-                      if (dset.fused && rows > kFusedMaxSliceRows) continue;
-                      const int64_t wgs = n_sl * ntiles * (int64_t)dset.n, rounds = (wgs + shg::kCUs - 1) / shg::kCUs;
-                      const int64_t cost = rounds * (rows * tw + 8192);
-                      if (cost < best_cost) { best_cost = cost; best = rows; }
-                  }
-                  slice_rows = best;
-              }
-              slices = (th + slice_rows - 1) / slice_rows;
-              if (slices > max_slices) slice_rows = (th + max_slices - 1) / max_slices;
-              if (dset.fused) slice_rows = std::min<int64_t>(slice_rows, kFusedMaxSliceRows);      // (the factors' room in LDS; th < 65536: 32 slices at most)
-              slices = (th + slice_rows - 1) / slice_rows;
-          }
-          // (tw >= 64: the last tile column then holds columns of the image itself, and a row's loose ends fit half a wave)
-          int vec = tw >= 64 && pitch % 8 == 0 && dset.aligned(15);
-          const dim3 hgrid((unsigned)slices, (unsigned)ntiles, nz);
-          if (dset.fused) {
-              SHG_REQUIRE(slice_rows <= kFusedMaxSliceRows, SHG_E_ARG, "shg_clahe: the fused histogram's slices hold at most %d rows", kFusedMaxSliceRows);
-              uintptr_t abits = 0;
-              for (int i = 0; i < dset.n; ++i) abits |= reinterpret_cast<uintptr_t>(dset.from.raw.p[i]);
-              vec = vec && (abits & 15) == 0 && dset.from.raw_pitch % 8 == 0 && dset.from.sx0 == 0 && dset.from.dx0 == 0 && dset.from.ncopy == w;
-          }
-          const HistSlicesArgs ha{dset.src, h, w, pitch, tiles, th, tw, part, dset.zs, (int)slice_rows, vec, dset.fused ? dset.from : FusedSrc{}, clip, (int)chunk_rows};
-          const size_t lds = HIST16 * 2 + (dset.fused ? (size_t)slice_rows * 8 : 0);
-          int e = 0;
-          if (dset.fused) {
-              e = bits == 16 ? shg::launch(k_tile_hist16_slices<true, 16>, hgrid, dim3(1024), lds, st, ha, "k_tile_hist16_slices")
-                  : bits == 8 ? shg::launch(k_tile_hist16_slices<true, 8>, hgrid, dim3(1024), lds, st, ha, "k_tile_hist16_slices")
-                              : shg::launch(k_tile_hist16_slices<true, 4>, hgrid, dim3(1024), lds, st, ha, "k_tile_hist16_slices");
-          } else {
-              e = bits == 16 ? shg::launch(k_tile_hist16_slices<false, 16>, hgrid, dim3(1024), lds, st, ha, "k_tile_hist16_slices")
-                  : bits == 8 ? shg::launch(k_tile_hist16_slices<false, 8>, hgrid, dim3(1024), lds, st, ha, "k_tile_hist16_slices")
-                              : shg::launch(k_tile_hist16_slices<false, 4>, hgrid, dim3(1024), lds, st, ha, "k_tile_hist16_slices");
-          }
-          if (e) return e;
-          const bool zero_sel = sel_hist && sel_zeroed;
-          const bool window = zero_sel && want_window;
-          const HistReduceArgs ra{part, (int)slices, clip, hist, chunk_tile, se, dset.zs, zero_sel ? sel_hist : nullptr, zero_sel ? SEL_SLOTS * sel_stride : 0, window ? 1 : 0};
-          e = bits == 16 ? shg::launch(k_hist_reduce, dim3(32, (unsigned)ntiles, nz), dim3(1024), 0, st, ra, "k_hist_reduce")
-              : bits == 8 ? shg::launch(k_hist_reduce_sat<8>, dim3(64, (unsigned)ntiles, nz), dim3(256), 0, st, ra, "k_hist_reduce_sat")
-                          : shg::launch(k_hist_reduce_sat<4>, dim3(32, (unsigned)ntiles, nz), dim3(256), 0, st, ra, "k_hist_reduce_sat");
-          if (e) return e;
-          sat_path = sat;
-          sat_k_top[0] = k_top[0];
-          sat_k_top[1] = k_top[1];
-          if (zero_sel) *sel_zeroed = true; }
-        { SHG_PROF("clahe_lut", st);
-          LutBlocksArgs la{hist, se, clip, lut_scale, lut, dset.zs, 0, {0, 0}, nullptr, 0, nullptr, 0, (int)area, ntiles, BorderPx{{}, h, w, pitch, h, w}};
-          if (ranks_job && ranks_done) {                     // the frame's order statistics ride along (two more workgroups per disk)
-              la.border = BorderPx{dset.src, h, w, pitch, th * tiles, tw * tiles};
-              la.n_ranks = 2;
-              la.rank[0] = sat_path ? sat_k_top[0] : ranks_job->rank[0];
-              la.rank[1] = sat_path ? sat_k_top[1] : ranks_job->rank[1];
-              la.chunk_sums = chunk_tile;
-              la.chunk_sets = ntiles;
-              la.ranks_out = ranks_job->out;
-              la.ranks_zstride = ranks_job->out_zstride;
-              *ranks_done = true;
-          }
-          // (measured: 22.4 against 24.9 us over a 21-disk stack, but 10.6 against 5.0 us for one disk -- the tiles of a block one
-          // after the other in 32 workgroups: taken from eight disks a launch on)
-          const bool allt = ntiles <= 16 && dset.n >= 8;      // a workgroup builds its 2048 entries for every tile and stores them as one run
-          const dim3 lgrid(32u + (unsigned)la.n_ranks, allt ? 1u : (unsigned)ntiles, (unsigned)dset.n);
-          const size_t llds = allt ? (size_t)2048 * ntiles * sizeof(uint16_t) : 0;
-          int e;
-          if (allt) e = sat_path ? shg::launch(k_tile_lut16_blocks<true, true>, lgrid, dim3(1024), llds, st, la, "k_tile_lut16_blocks")
-                                 : shg::launch(k_tile_lut16_blocks<false, true>, lgrid, dim3(1024), llds, st, la, "k_tile_lut16_blocks");
-          else e = sat_path ? shg::launch(k_tile_lut16_blocks<true, false>, lgrid, dim3(1024), 0, st, la, "k_tile_lut16_blocks")
-                            : shg::launch(k_tile_lut16_blocks<false, false>, lgrid, dim3(1024), 0, st, la, "k_tile_lut16_blocks");
-          if (e) return e; }
-        { SHG_PROF("clahe_interp", st);
-          bool counted = false;
-          const bool window = sel_hist && sel_zeroed && want_window;
-          if (int e = launch_interp16(dset, h, w, pitch, tiles, inv_tw, inv_th, lut, true, dst_pitch, sel_hist, sel_stride, st, &counted, window)) return e;
-          if (sel_pass0_done) *sel_pass0_done = counted;
-          if (sel_window) *sel_window = window && counted; }
-        if (chunk_tile_out) *chunk_tile_out = chunk_tile;
-        return 0;
+
+    // Saturated counters (k_tile_hist16_slices<., 8 / 4>): whenever the clip limit fits a byte and nobody needs the true counts
+    // -- the frame's order statistics may ride along when they lie within `clip` pixels of the top (np.percentile(frame, 99.9999)
+    // of a 4 Mpx image: the 5th and 6th largest), a caller who wants the chunk sums (shg_contrast_stats_u16) gets the u16 slices.
+    bool sat = tune.sat_mode != 0 && clip <= 255 && tw <= 65280 && (!r.want_chunks || r.ranks);
+    int64_t k_top[2] = {0, 0};
+    for (int i = 0; i < 2 && sat && r.ranks; ++i) {
+        k_top[i] = h * w - r.ranks->rank[i];               // rank (from the bottom, 0-based) -> the k-th largest
+        sat = k_top[i] >= 1 && k_top[i] <= clip;
     }
-    SHG_REQUIRE(dset.n == 1 && !dset.fused, SHG_E_UNSUPPORTED, "shg_clahe: several disks per launch need the roomy 16-bit workspace");
-    if (hipError_t e = hipMemsetAsync(hist, 0, (size_t)ntiles * hist_size * sizeof(uint32_t), st)) {
-        shg::set_error("shg_clahe: memset: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    if (bytes_per_px == 2) {
-        ensure_lds_attr();
-        dim3 hgrid((unsigned)((area + SLICE_PX - 1) / SLICE_PX), (unsigned)ntiles);
-        { SHG_PROF("clahe_hist", st); k_tile_hist16<<<hgrid, 1024, HIST16 * 2, st>>>(static_cast<const uint16_t*>(img), h, w, pitch, tiles, th, tw, hist); }
-        if (int e = shg::check_launch("k_tile_hist16")) return e;
-        if (clip > 0 && clip <= 65535) {
-            SHG_PROF("clahe_lut", st);
-            k_tile_lut16_lds<<<ntiles, 1024, (HIST16 + HIST16 / 64) * sizeof(uint16_t), st>>>(hist, clip, lut_scale, lut);
-        } else {
-            SHG_PROF("clahe_lut", st);
-            k_tile_lut<HIST16><<<ntiles, 1024, 0, st>>>(hist, clip, lut_scale, lut);
+    for (int i = 0; i < 2 && r.ranks; ++i) p.lut_rank[i] = sat ? k_top[i] : r.ranks->rank[i];
+    p.bits = !sat ? 16 : (clip <= 15 && tune.sat_mode != 8 ? 4 : 8);
+    p.route = p.bits == 16 ? Route::Slices16 : p.bits == 8 ? Route::Slices8 : Route::Slices4;
+    // One image: 32768-pixel slices spread a tile over enough workgroups to fill the chip.  A stack of disks fills it
+    // anyway: the largest slice a u16 counter allows halves the slice histograms written here and read back by the
+    // reduction (the layout's n_slices is the upper bound the workspace was sized for).
+    int64_t slice_px = (d.n >= tune.big_from && tune.slice_px > SLICE_PX && tune.slice_px <= 65535) ? tune.slice_px : SLICE_PX;
+    if (sat && tune.sat_px) slice_px = tune.sat_px;
+    p.chunk_rows = slice_rows_of(tw, 65280);                 // (sat: rows counted between two clamps of the u16 counters)
+    p.slice_rows = slice_rows_of(tw, slice_px);
+    if (sat) {
+        // as many slices as the byte sums of k_hist_reduce_sat hold (256) and the workspace has room for (sized for n_slices u16 slices)
+        const int64_t max_slices = std::min<int64_t>(256, p.lay.n_slices * (16 / p.bits));
+        if (!tune.sat_px) {
+            // A slice may be any length now, and a workgroup has a CU to itself (its histogram is 128 KB of the 160 KB of LDS): the
+            // launch takes ceil(workgroups / CUs) rounds of one slice each.  The number of slices per tile that makes rounds x
+            // (pixels of a slice + what zeroing, clamping and storing 64 K counters costs, about 8000 pixels' worth) smallest:
+            // 63 at one 2000 x 2098 disk (252 workgroups, one round), 3 for a stack of 21 (252 again) -- not the 4 that
+            // would leave two thirds of the chip idle in a second round.
+            int64_t best = 1, best_cost = INT64_MAX;
+            for (int64_t sl = 1; sl <= std::min<int64_t>(max_slices, th); ++sl) {
+                const int64_t rows = ceil_div(th, sl);
+                if (d.fused && rows > kFusedMaxSliceRows) continue;
+                const int64_t cost = ceil_div(ceil_div(th, rows) * p.ntiles * (int64_t)d.n, shg::kCUs) * (rows * tw + 8192);
+                if (cost < best_cost) { best_cost = cost; best = rows; }
+            }
+            p.slice_rows = best;
         }
-        if (int e = shg::check_launch("k_tile_lut")) return e;
-        { SHG_PROF("clahe_interp", st);
-          bool counted = false;
-          if (int e = launch_interp16(dset, h, w, pitch, tiles, inv_tw, inv_th, lut, false, dst_pitch, nullptr, 0, st, &counted)) return e; }
+        if (ceil_div(th, p.slice_rows) > max_slices) p.slice_rows = ceil_div(th, max_slices);
+        if (d.fused) p.slice_rows = std::min<int64_t>(p.slice_rows, kFusedMaxSliceRows);      // (the factors' room in LDS; th < 65536: 32 slices at most)
+    }
+    p.slices = ceil_div(th, p.slice_rows);
+    PLAN_REQUIRE(!d.fused || p.slice_rows <= kFusedMaxSliceRows, SHG_E_ARG, "shg_clahe: the fused histogram's slices hold at most %d rows", kFusedMaxSliceRows);
+    // (tw >= 64: the last tile column then holds columns of the image itself, and a row's loose ends fit half a wave)
+    const uintptr_t ptr_bits = d.bits_of(d.src) | d.bits_of(d.dst);
+    p.hist_vec = tw >= 64 && pitch % 8 == 0 && (ptr_bits & 15) == 0 && (!d.fused || d.from_in_vectors(w));
+    p.window = r.sel_hist && r.want_window;
+    // (measured: 22.4 against 24.9 us over a 21-disk stack, but 10.6 against 5.0 us for one disk -- the tiles of a block one
+    // after the other in 32 workgroups: taken from eight disks a launch on)
+    p.lut_all_tiles = p.ntiles <= 16 && d.n >= 8;            // and stores them as one run
+
+    const bool vec = (ptr_bits & 7) == 0 && pitch % 4 == 0 && dst_pitch % 4 == 0;
+    p.blend_px = vec ? 4 : 1;
+    p.blend_counts = vec && r.sel_hist;
+    p.blend_rounds = p.blend_counts ? 4 : 1;                 // (4: amortises the histogram's zeroing and flush)
+    p.blend_tiles_x = 1u;
+    if (p.blend_counts && tune.interp_tiled) {
+        // 4 lanes x 16 rows per wave, 4 waves across: 64 pixels x 16 rows a round (measured over 21 disks: 243 us; 2 waves
+        // across 242, one 270; 2 lanes x 32 rows 262-384; 8 lanes x 8 rows 246-253; the flat sequence 300)
+        // Eight pixels a lane (16-byte loads and stores) from four disks up: 222 us against 243 over 21 disks -- and 17.5 against 13.7 us
+        // on one, where the launch is too small to fill the device.  (SHG_INTERP_SHAPE = lw | wx << 4 | (8 px) << 8: tools' sweeps;
+        // halving the kernel's L2 requests this way does not change what it costs a pass A beside it, profiles/r04_sweeps.txt.)
+        const int shape = tune.interp_shape;
+        const int lw = shape ? (shape & 15) : 2, wx = shape ? ((shape >> 4) & 15) : 2;
+        const bool px8 = (shape ? ((shape >> 8) & 1) != 0 : d.n >= 4) && (ptr_bits & 15) == 0 && pitch % 8 == 0 && dst_pitch % 8 == 0;
+        p.blend_px = px8 ? 8 : 4;
+        const int64_t wg_px = (int64_t)p.blend_px << (lw + wx), wg_rows = (int64_t)(64 >> lw) * (4 >> wx);
+        p.blend_tiles_x = (uint32_t)ceil_div(w, wg_px);
+        p.blend_tiled = 0x10000 | lw | (wx << 8);
+        p.blend_blocks = p.blend_tiles_x * (uint32_t)ceil_div(h, wg_rows * p.blend_rounds);
     } else {
-        int64_t hb = (area + 4095) / 4096;
-        if (hb > 256) hb = 256;
-        dim3 hgrid((unsigned)hb, (unsigned)ntiles);
-        { SHG_PROF("clahe_hist", st); k_tile_hist8<<<hgrid, 256, 0, st>>>(static_cast<const uint8_t*>(img), h, w, pitch, tiles, th, tw, hist); }
-        if (int e = shg::check_launch("k_tile_hist8")) return e;
-        { SHG_PROF("clahe_lut", st); k_tile_lut<256><<<ntiles, 1024, 0, st>>>(hist, clip, lut_scale, lut); }
-        if (int e = shg::check_launch("k_tile_lut")) return e;
-        { SHG_PROF("clahe_interp", st); k_clahe_interp<uint8_t, 256><<<igrid, 256, 0, st>>>(static_cast<const uint8_t*>(img), h, w, pitch, tiles, inv_tw, inv_th, lut,
-                                                            static_cast<uint8_t*>(dst), dst_pitch); }
+        p.blend_blocks = (unsigned)ceil_div(ceil_div(w, p.blend_px) * h, 256 * (int64_t)p.blend_rounds);   // the flat (row, vector) sequence
     }
-    if (int e = shg::check_launch("k_clahe_interp")) return e;
-    if (sel_hist && sel_zeroed) {                        // nothing has counted into sel_hist on this path: zero it the plain way
-        if (hipError_t e = hipMemsetAsync(sel_hist, 0, (size_t)SEL_SLOTS * sel_stride * sizeof(uint32_t), st)) {
-            shg::set_error("shg_clahe: memset: %s", hipGetErrorString(e));
-            return (int)e;
+    return p;
+}
+#undef PLAN_REQUIRE
+
+// ---- kernels by their template arguments (every instantiation of a kernel has one signature) -------------------------------
+template <typename Args> using Kernel = void (*)(Args);
+inline Kernel<HistSlicesArgs> pick_hist_slices(bool fused, int bits) {
+    if (fused) return bits == 16 ? k_tile_hist16_slices<true, 16> : bits == 8 ? k_tile_hist16_slices<true, 8> : k_tile_hist16_slices<true, 4>;
+    return bits == 16 ? k_tile_hist16_slices<false, 16> : bits == 8 ? k_tile_hist16_slices<false, 8> : k_tile_hist16_slices<false, 4>;
+}
+inline Kernel<HistReduceArgs> pick_hist_reduce(int bits) { return bits == 16 ? k_hist_reduce : bits == 8 ? k_hist_reduce_sat<8> : k_hist_reduce_sat<4>; }
+inline Kernel<LutBlocksArgs> pick_lut_blocks(bool sat, bool all_tiles) {
+    if (all_tiles) return sat ? k_tile_lut16_blocks<true, true> : k_tile_lut16_blocks<false, true>;
+    return sat ? k_tile_lut16_blocks<true, false> : k_tile_lut16_blocks<false, false>;
+}
+inline Kernel<InterpVmArgs> pick_interp_vm(int px, bool counts, bool t2) {       // (counting: 4 or 8 pixels a lane; not counting: 1 or 4)
+    if (counts && px == 8) return t2 ? k_clahe_interp_vm<8, true, true> : k_clahe_interp_vm<8, true, false>;
+    if (counts) return t2 ? k_clahe_interp_vm<4, true, true> : k_clahe_interp_vm<4, true, false>;
+    if (px == 4) return t2 ? k_clahe_interp_vm<4, false, true> : k_clahe_interp_vm<4, false, false>;
+    return t2 ? k_clahe_interp_vm<1, false, true> : k_clahe_interp_vm<1, false, false>;
+}
+
+void ensure_lds_attr() {
+    static const bool done = [] {                        // (a function-local static: once, also with several pool threads here)
+        auto allow = [](auto kernel, size_t lds) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        };
+        for (int bits : {16, 8, 4}) {
+            allow(pick_hist_slices(false, bits), HIST16 * 2);
+            allow(pick_hist_slices(true, bits), HIST16 * 2 + kFusedMaxSliceRows * 8);
         }
-        *sel_zeroed = true;
+        allow(pick_lut_blocks(true, true), 2048 * 16 * 2);
+        allow(pick_lut_blocks(false, true), 2048 * 16 * 2);
+        allow(k_tile_hist16, HIST16 * 2);
+        allow(k_image_hist16, HIST16 * 2);
+        allow(k_tile_lut16_lds, (HIST16 + HIST16 / 64) * 2);
+        return true;
+    }();
+    (void)done;
+}
+
+// ---- the launches ----------------------------------------------------------------------------------------------------------
+ClaheResult clahe_slices(const ClaheRequest& r, const Plan& p) {
+    ClaheResult out;
+    ensure_lds_attr();
+    hipStream_t st = shg::as_stream(r.stream);
+    const Disks& d = r.disks;
+    const Shape& im = r.im;
+    char* ws = static_cast<char*>(r.workspace);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(ws);
+    uint16_t* lut = reinterpret_cast<uint16_t*>(ws + p.lay.lut);
+    uint32_t* part = reinterpret_cast<uint32_t*>(ws + p.lay.slices);
+    uint32_t* chunk_tile = reinterpret_cast<uint32_t*>(ws + p.lay.chunk);
+    int32_t* se = reinterpret_cast<int32_t*>(ws + p.lay.se);
+    const unsigned nz = (unsigned)d.n, ntiles = (unsigned)p.ntiles;
+    const bool sat = p.bits != 16;
+    { SHG_PROF("clahe_hist", st);
+      const HistSlicesArgs ha{d.src, im.h, im.w, im.pitch, im.tiles, p.th, p.tw, part, d.zs, (int)p.slice_rows, p.hist_vec, d.fused ? d.from : FusedSrc{}, p.clip, (int)p.chunk_rows};
+      const size_t lds = HIST16 * 2 + (d.fused ? (size_t)p.slice_rows * 8 : 0);                // (fused: the slice's row factors behind the histogram)
+      if ((out.err = shg::launch(pick_hist_slices(d.fused, p.bits), dim3((unsigned)p.slices, ntiles, nz), dim3(1024), lds, st, ha, "k_tile_hist16_slices")))
+          return out;
+      const HistReduceArgs ra{part, (int)p.slices, p.clip, hist, chunk_tile, se, d.zs, r.sel_hist, r.sel_hist ? SEL_SLOTS * r.sel_stride : 0, p.window ? 1 : 0};
+      if ((out.err = shg::launch(pick_hist_reduce(p.bits), dim3(p.bits == 8 ? 64u : 32u, ntiles, nz), dim3(sat ? 256u : 1024u), 0, st, ra, sat ? "k_hist_reduce_sat" : "k_hist_reduce")))
+          return out;
+      out.sel_zeroed = r.sel_hist != nullptr; }
+    { SHG_PROF("clahe_lut", st);
+      LutBlocksArgs la{hist, se, p.clip, p.lut_scale, lut, d.zs, 0, {0, 0}, nullptr, 0, nullptr, 0, (int)p.area, p.ntiles, BorderPx{{}, im.h, im.w, im.pitch, im.h, im.w}};
+      if (r.ranks) {                                         // two more workgroups per disk
+          la.border = BorderPx{d.src, im.h, im.w, im.pitch, p.th * im.tiles, p.tw * im.tiles};
+          la.n_ranks = 2, la.rank[0] = p.lut_rank[0], la.rank[1] = p.lut_rank[1];
+          la.chunk_sums = chunk_tile, la.chunk_sets = p.ntiles;
+          la.ranks_out = r.ranks->out, la.ranks_zstride = r.ranks->out_zstride;
+          out.ranks_done = true;
+      }
+      const dim3 grid(32u + (unsigned)la.n_ranks, p.lut_all_tiles ? 1u : ntiles, nz);
+      const size_t lds = p.lut_all_tiles ? (size_t)2048 * p.ntiles * sizeof(uint16_t) : 0;
+      if ((out.err = shg::launch(pick_lut_blocks(sat, p.lut_all_tiles), grid, dim3(1024), lds, st, la, "k_tile_lut16_blocks"))) return out; }
+    { SHG_PROF("clahe_interp", st);
+      const InterpVmArgs ia{d.src, im.h, im.w, im.pitch, im.tiles, 1.0f / (float)p.tw, 1.0f / (float)p.th, lut, d.dst, im.dst_pitch, p.blend_rounds,
+                            p.blend_counts ? r.sel_hist : nullptr, p.blend_counts ? r.sel_stride : 0, d.zs, p.blend_tiled, p.blend_tiles_x, p.blend_counts && p.window ? 1 : 0};
+      if ((out.err = shg::launch(pick_interp_vm(p.blend_px, p.blend_counts, im.tiles == 2), dim3(p.blend_blocks, 1u, nz), dim3(256), 0, st, ia, "k_clahe_interp_vm")))
+          return out;
+      out.pass0_done = p.blend_counts;
+      out.window_used = p.window && p.blend_counts; }
+    out.chunk_tile = chunk_tile;
+    return out;
+}
+
+// One image into a zeroed histogram with global atomics, T its pixel and HS its histogram's size; the select's histograms, which
+// nothing here counts into, zeroed the plain way.
+template <typename T, int HS> ClaheResult clahe_atomics(const ClaheRequest& r, const Plan& p) {
+    constexpr bool b16 = HS == HIST16;
+    ClaheResult out;
+    hipStream_t st = shg::as_stream(r.stream);
+    const Shape& im = r.im;
+    const T* img = static_cast<const T*>(r.disks.src.p[0]);
+    T* dst = static_cast<T*>(const_cast<void*>(r.disks.dst.p[0]));
+    uint32_t* hist = static_cast<uint32_t*>(r.workspace);
+    uint16_t* lut = reinterpret_cast<uint16_t*>(static_cast<char*>(r.workspace) + p.lay.lut);
+    auto zero = [&](void* ptr, size_t bytes) {
+        const hipError_t e = hipMemsetAsync(ptr, 0, bytes, st);
+        if (e != hipSuccess) { shg::set_error("shg_clahe: memset: %s", hipGetErrorString(e)); out.err = (int)e; }
+        return e == hipSuccess;
+    };
+    if (!zero(hist, p.lay.lut)) return out;
+    if (b16) ensure_lds_attr();
+    { SHG_PROF("clahe_hist", st);
+      if constexpr (b16) k_tile_hist16<<<dim3((unsigned)ceil_div(p.area, SLICE_PX), p.ntiles), 1024, HIST16 * 2, st>>>(img, im.h, im.w, im.pitch, im.tiles, p.th, p.tw, hist);
+      else k_tile_hist8<<<dim3((unsigned)std::min<int64_t>(ceil_div(p.area, 4096), 256), p.ntiles), 256, 0, st>>>(img, im.h, im.w, im.pitch, im.tiles, p.th, p.tw, hist); }
+    if ((out.err = shg::check_launch(b16 ? "k_tile_hist16" : "k_tile_hist8"))) return out;
+    { SHG_PROF("clahe_lut", st);
+      if (b16 && p.clip > 0 && p.clip <= 65535) k_tile_lut16_lds<<<p.ntiles, 1024, (HIST16 + HIST16 / 64) * sizeof(uint16_t), st>>>(hist, p.clip, p.lut_scale, lut);
+      else k_tile_lut<HS><<<p.ntiles, 1024, 0, st>>>(hist, p.clip, p.lut_scale, lut); }
+    if ((out.err = shg::check_launch("k_tile_lut"))) return out;
+    { SHG_PROF("clahe_interp", st);
+      k_clahe_interp<T, HS><<<dim3((unsigned)ceil_div(im.w, 256), (unsigned)im.h), 256, 0, st>>>(img, im.h, im.w, im.pitch, im.tiles, 1.0f / (float)p.tw, 1.0f / (float)p.th, lut, dst, im.dst_pitch); }
+    if ((out.err = shg::check_launch("k_clahe_interp"))) return out;
+    if (r.sel_hist) out.sel_zeroed = zero(r.sel_hist, (size_t)SEL_SLOTS * r.sel_stride * sizeof(uint32_t));
+    return out;
+}
+
+ClaheResult clahe_impl(const ClaheRequest& r, const Tuning& tune) {
+    const Plan p = r.disks.src.p[0] && r.disks.dst.p[0] && r.workspace ? plan_clahe(r, tune) : Plan{SHG_E_ARG, "shg_clahe: null pointer"};
+    if (p.err) {
+        shg::set_error("%s", p.msg);
+        return ClaheResult{p.err};
+    }
+    return is_slices(p.route) ? clahe_slices(r, p) : p.route == Route::Atomics16 ? clahe_atomics<uint16_t, HIST16>(r, p) : clahe_atomics<uint8_t, 256>(r, p);
+}
+
+int select_u16_impl(const SelectRequest& r, const Tuning& tune) {
+    const Disks& d = r.disks;
+    const int64_t h = r.h, w = r.w;
+    SHG_REQUIRE(d.src.p[0] && r.ranks && r.out && r.workspace, SHG_E_ARG, "shg_select_u16: null pointer");
+    SHG_REQUIRE(h > 0 && w > 0 && r.pitch >= w && r.n_ranks >= 1 && r.n_ranks <= 8, SHG_E_ARG, "shg_select_u16: bad sizes");
+    SHG_REQUIRE(r.workspace_bytes >= select_bytes(r.n_ranks), SHG_E_WORKSPACE, "shg_select_u16: workspace too small");
+    for (int i = 0; i < r.n_ranks; ++i)
+        SHG_REQUIRE(r.ranks[i] >= 0 && r.ranks[i] < h * w, SHG_E_ARG, "shg_select_u16: rank %lld outside the image", (long long)r.ranks[i]);
+    hipStream_t st = shg::as_stream(r.stream);
+    uint32_t* hist = static_cast<uint32_t*>(r.workspace);
+    Ranks8 ranks = {};
+    for (int i = 0; i < r.n_ranks; ++i) ranks.v[i] = r.ranks[i];
+    if (!r.after.sel_zeroed) {
+        hipError_t e = hipMemsetAsync(hist, 0, (size_t)SEL_SLOTS * (1 + r.n_ranks) * 256 * sizeof(uint32_t), st);
+        if (e != hipSuccess) { shg::set_error("shg_select_u16: %s", hipGetErrorString(e)); return (int)e; }
+    }
+    // ~8192 pixels per workgroup, at most 1024 workgroups, whole rows each
+    // (measured, tools/bench_select.py: 2048 / 4096 / 8192 / 16384 pixels per workgroup -> 92 / 58 / 45 / 44 us for two ranks)
+    // Several disks in one launch: the chip is full with ~2048 workgroups in all (Tuning::select_wgs), and a workgroup's share then
+    // grows with the number of disks (the replay, zeroing and flush around the pixel loop are paid per workgroup).
+    int64_t per_wg = 8192;
+    if (d.n > 1 && h * w * d.n / per_wg > tune.select_wgs) per_wg = h * w * d.n / tune.select_wgs;
+    const unsigned blocks = (unsigned)std::min(h, std::min<int64_t>(std::max<int64_t>(ceil_div(h * w, per_wg), 1), 1024));
+    const int vec_ok = ((d.bits_of(d.src) & 15) == 0) && (r.pitch % 8 == 0), window = r.after.window_used ? 1 : 0;
+    SHG_REQUIRE(r.after.sel_zeroed || d.n == 1, SHG_E_ARG, "shg_select_u16: several disks need their histograms zeroed by the caller");
+    SHG_PROF("select_u16", st);
+    for (int pass = r.after.pass0_done ? 1 : 0; pass < 2; ++pass) {
+        // 512 threads: the zeroing / replay / flush around the pixel loop is shared by twice the waves (256 / 512 / 1024
+        // threads: 44.7 / 40.6 / 40.3 us for two ranks, tools/bench_select.py)
+        if (int err = shg::launch(k_select16_pass, dim3(blocks, 1u, (unsigned)d.n), dim3(512), 0, st,
+                                 SelectPassArgs{d.src, h, w, r.pitch, pass, ranks, r.n_ranks, hist, vec_ok, d.zs, window, h * w}, "k_select16_pass"))
+            return err;
+    }
+    return shg::launch(k_select16_final, dim3((unsigned)r.n_ranks, 1u, (unsigned)d.n), dim3(256), 0, st,
+                       SelectFinalArgs{ranks, hist, r.out, d.zs, r.out_zstride, window, h * w}, "k_select16_final");
+}
+
+// Whether images of this shape take the batched route of the contrast stage: one launch per kernel for all disks on CLAHE's slice
+// route, the frame's percentiles read off the histograms -- the route that can also MAKE the images on its way (FrameSource).
+// The one predicate: what plan_clahe says about the most demanding launch the route may be asked for (a full batch of fused
+// disks with u16 counters in a roomy workspace).  A shape it refuses goes disk by disk through shg_contrast_stats_u16.
+inline bool batched_route(int64_t h, int64_t w, int tiles, double clip_limit, const Tuning& tune) {
+    ClaheRequest r{Disks{}, Shape{h, w, w, w, 2, clip_limit, tiles}, nullptr, SIZE_MAX, nullptr};
+    r.disks.n = shg::kMaxBatch;
+    r.disks.fused = r.want_chunks = true;
+    const Plan p = plan_clahe(r, tune);
+    return tune.contrast_batch && p.err == 0 && is_slices(p.route);
+}
+
+inline int frame_ranks(const int64_t* ranks_frame2, int64_t px, Ranks8* ranks) {
+    *ranks = {};
+    for (int i = 0; i < 2; ++i) {
+        SHG_REQUIRE(ranks_frame2[i] >= 0 && ranks_frame2[i] < px, SHG_E_ARG, "shg_contrast_stats_u16: rank %lld outside the image", (long long)ranks_frame2[i]);
+        ranks->v[i] = ranks_frame2[i];
     }
     return 0;
 }
+
 }  // namespace
+
+// ---- the C ABI ---------------------------------------------------------------------------------------------------------------
+extern "C" size_t shg_clahe_workspace_bytes(int tiles, int bytes_per_px) {
+    if (tiles < 1 || tiles > 16 || (bytes_per_px != 1 && bytes_per_px != 2)) return 0;
+    return clahe_layout(0, 0, tiles, bytes_per_px).small;
+}
+
+extern "C" size_t shg_clahe_workspace_bytes_for(int64_t h, int64_t w, int tiles, int bytes_per_px) {
+    if (shg_clahe_workspace_bytes(tiles, bytes_per_px) == 0 || h <= 0 || w <= 0) return 0;
+    return clahe_layout(h, w, tiles, bytes_per_px).total;
+}
 
 extern "C" int shg_clahe(const void* img, int64_t h, int64_t w, int64_t pitch, int bytes_per_px, double clip_limit, int tiles,
                          void* dst, int64_t dst_pitch, void* workspace, size_t workspace_bytes, shg_stream_t stream) {
-    return clahe_impl(img, h, w, pitch, bytes_per_px, clip_limit, tiles, dst, dst_pitch, workspace, workspace_bytes, stream, nullptr, nullptr, 0, nullptr);
+    SHG_REQUIRE(img && dst, SHG_E_ARG, "shg_clahe: null pointer");
+    const ClaheRequest r{one_disk(img, dst), Shape{h, w, pitch, dst_pitch, bytes_per_px, clip_limit, tiles}, workspace, workspace_bytes, stream};
+    return clahe_impl(r, read_tuning()).err;
 }
 
 extern "C" int shg_hist(const void* img, int64_t h, int64_t w, int64_t pitch, int bytes_per_px, uint32_t* hist, shg_stream_t stream) {
@@ -2034,179 +2145,92 @@ extern "C" int shg_hist(const void* img, int64_t h, int64_t w, int64_t pitch, in
     const int64_t n = h * w;
     if (bytes_per_px == 2) {
         ensure_lds_attr();
-        { SHG_PROF("hist", st); k_image_hist16<<<(unsigned)((n + SLICE_PX - 1) / SLICE_PX), 1024, HIST16 * 2, st>>>(static_cast<const uint16_t*>(img), h, w, pitch, hist); }
+        { SHG_PROF("hist", st); k_image_hist16<<<(unsigned)ceil_div(n, SLICE_PX), 1024, HIST16 * 2, st>>>(static_cast<const uint16_t*>(img), h, w, pitch, hist); }
     } else {
-        int64_t hb = (n + 4095) / 4096;
-        if (hb > 256) hb = 256;
-        { SHG_PROF("hist", st); k_image_hist8<<<(unsigned)hb, 256, 0, st>>>(static_cast<const uint8_t*>(img), h, w, pitch, hist); }
+        { SHG_PROF("hist", st); k_image_hist8<<<(unsigned)std::min<int64_t>(ceil_div(n, 4096), 256), 256, 0, st>>>(static_cast<const uint8_t*>(img), h, w, pitch, hist); }
     }
     return shg::check_launch("k_image_hist");
 }
 
 extern "C" size_t shg_select_u16_workspace_bytes(int n_ranks) {
     if (n_ranks < 1 || n_ranks > 8) return 0;
-    return (size_t)8 * (1 + n_ranks) * 256 * sizeof(uint32_t) + (size_t)n_ranks * sizeof(int64_t);      // SEL_SLOTS histogram copies
+    return select_bytes(n_ranks);
 }
-
-namespace {
-// pass0_done: the slot histograms are zeroed and already hold the high-byte counts (k_clahe_interp_vm<.., true>)
-// disks (may be NULL: the one image img): several images per launch, disk i with its histograms at workspace + i * zs and its
-// results at out + i * out_zstride
-int select_u16_impl(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const int64_t* host_ranks, int n_ranks,
-                    double* out, void* workspace, size_t workspace_bytes, shg_stream_t stream, bool zeroed, bool pass0_done,
-                    const Disks* disks = nullptr, int out_zstride = 0, bool window = false) {
-    const Disks dset = disks ? *disks : one_disk(img, nullptr);
-    SHG_REQUIRE(img && host_ranks && out && workspace, SHG_E_ARG, "shg_select_u16: null pointer");
-    SHG_REQUIRE(h > 0 && w > 0 && pitch >= w && n_ranks >= 1 && n_ranks <= 8, SHG_E_ARG, "shg_select_u16: bad sizes");
-    SHG_REQUIRE(workspace_bytes >= shg_select_u16_workspace_bytes(n_ranks), SHG_E_WORKSPACE, "shg_select_u16: workspace too small");
-    for (int i = 0; i < n_ranks; ++i)
-        SHG_REQUIRE(host_ranks[i] >= 0 && host_ranks[i] < h * w, SHG_E_ARG, "shg_select_u16: rank %lld outside the image", (long long)host_ranks[i]);
-    hipStream_t st = shg::as_stream(stream);
-    uint32_t* hist = static_cast<uint32_t*>(workspace);
-    Ranks8 ranks = {};
-    for (int i = 0; i < n_ranks; ++i) ranks.v[i] = host_ranks[i];
-    if (!zeroed) {
-        hipError_t e = hipMemsetAsync(hist, 0, (size_t)SEL_SLOTS * (1 + n_ranks) * 256 * sizeof(uint32_t), st);
-        if (e != hipSuccess) { shg::set_error("shg_select_u16: %s", hipGetErrorString(e)); return (int)e; }
-    }
-    // ~8192 pixels per workgroup, at most 1024 workgroups, whole rows each
-    // (measured, tools/bench_select.py: 2048 / 4096 / 8192 / 16384 pixels per workgroup -> 92 / 58 / 45 / 44 us for two ranks)
-    // Several disks in one launch: the chip is full with ~2048 workgroups in all, and a workgroup's share then grows with the
-    // number of disks (the replay, zeroing and flush around the pixel loop are paid per workgroup).
-    static const int64_t wg_target = [] { const char* v = getenv("SHG_SELECT_WGS"); return v ? (int64_t)atoi(v) : (int64_t)2048; }();
-    int64_t per_wg = 8192;
-    if (dset.n > 1 && h * w * dset.n / per_wg > wg_target) per_wg = h * w * dset.n / wg_target;
-    int64_t want = (h * w + per_wg - 1) / per_wg;
-    want = want < 1 ? 1 : (want > 1024 ? 1024 : want);
-    const unsigned blocks = (unsigned)(h < want ? h : want);
-    uintptr_t bits = 0;
-    for (int i = 0; i < dset.n; ++i) bits |= reinterpret_cast<uintptr_t>(dset.src.p[i]);
-    const int vec_ok = ((bits & 15) == 0) && (pitch % 8 == 0);
-    SHG_REQUIRE(zeroed || dset.n == 1, SHG_E_ARG, "shg_select_u16: several disks need their histograms zeroed by the caller");
-    SHG_PROF("select_u16", st);
-    for (int pass = pass0_done ? 1 : 0; pass < 2; ++pass) {
-        // 512 threads: the zeroing / replay / flush around the pixel loop is shared by twice the waves (256 / 512 / 1024
-        // threads: 44.7 / 40.6 / 40.3 us for two ranks, tools/bench_select.py)
-        if (int err = shg::launch(k_select16_pass, dim3(blocks, 1u, (unsigned)dset.n), dim3(512), 0, st,
-                                 SelectPassArgs{dset.src, h, w, pitch, pass, ranks, n_ranks, hist, vec_ok, dset.zs, window ? 1 : 0, h * w}, "k_select16_pass"))
-            return err;
-    }
-    return shg::launch(k_select16_final, dim3((unsigned)n_ranks, 1u, (unsigned)dset.n), dim3(256), 0, st, SelectFinalArgs{ranks, hist, out, dset.zs, out_zstride, window ? 1 : 0, h * w}, "k_select16_final");
-}
-}  // namespace
 
 extern "C" int shg_select_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const int64_t* host_ranks, int n_ranks,
                               double* out, void* workspace, size_t workspace_bytes, shg_stream_t stream) {
-    return select_u16_impl(img, h, w, pitch, host_ranks, n_ranks, out, workspace, workspace_bytes, stream, false, false);
+    return select_u16_impl(SelectRequest{one_disk(img, nullptr), h, w, pitch, host_ranks, n_ranks, out, 0, workspace, workspace_bytes, stream}, read_tuning());
 }
 
 // ---- image_process in two calls (solex_util.py:527-547) -------------------------------------------------------------
 // The contrast stage is a dozen small launches around one host decision (three percentiles -> six rescale bounds).
 // Two composite entry points issue them from C instead of from a dozen ctypes calls: same kernels, same order.
-// the 3-rank select's area of the contrast stage: its slot histograms, then the window's counts and SelWin
-static size_t select3_area_bytes() {
-    return (size_t)SEL_SLOTS * (1 + 3) * 256 * sizeof(uint32_t) + (size_t)SEL_WIN_WORDS * sizeof(uint32_t) + sizeof(SelWin) + 3 * sizeof(int64_t);
-}
-// Measured (tools/ab_tables.sh): over a 21-disk stack the second pass falls from 73 to 14 us and the blend kernel grows from 212 to
-// 240 us (its workgroups flush their window counts with global atomics) -- 30 us gained; for ONE disk 12.7 -> 6.3 us against
-// 12.9 -> 24.8 us -- 6 us lost.  So: from four disks a launch on.  SHG_SELECT_WINDOW=0 / 1: never / always (the tests).
-static bool select_window_wanted(int disks) {                // (read at every call: tests hold one setting against the other)
-    const char* v = getenv("SHG_SELECT_WINDOW");
-    if (v && v[0] == '0') return false;
-    if (v && v[0] == '1') return true;
-    return disks >= 4;
-}
-
 extern "C" size_t shg_contrast_stats_workspace_bytes(int tiles) {
-    const size_t c = shg_clahe_workspace_bytes(tiles, 2), s2 = shg_select_u16_workspace_bytes(2), s3 = select3_area_bytes();
-    if (c == 0) return 0;
-    const size_t chunks = 1024 * sizeof(uint32_t);           // 64-bin chunk sums of the summed tile histograms
-    return ((c + 255) / 256 + (s2 + 255) / 256 + (s3 + 255) / 256 + (chunks + 255) / 256) * 256;
+    const size_t c = shg_clahe_workspace_bytes(tiles, 2);
+    return c ? stats_layout(c).total : 0;
 }
 
 extern "C" size_t shg_contrast_stats_workspace_bytes_for(int64_t h, int64_t w, int tiles) {
-    const size_t base = shg_contrast_stats_workspace_bytes(tiles);
-    if (base == 0 || h <= 0 || w <= 0) return 0;
-    const size_t c_old = (shg_clahe_workspace_bytes(tiles, 2) + 255) / 256 * 256, c_new = (shg_clahe_workspace_bytes_for(h, w, tiles, 2) + 255) / 256 * 256;
-    return base - c_old + c_new;
+    const size_t c = shg_clahe_workspace_bytes_for(h, w, tiles, 2);
+    return c ? stats_layout(c).total : 0;
 }
 
 extern "C" int shg_contrast_stats_u16(const uint16_t* frame, int64_t h, int64_t w, int64_t pitch, double clip_limit, int tiles,
                                       uint16_t* cl1, int64_t cl1_pitch, const int64_t* ranks_frame2, const int64_t* ranks_cl13,
                                       double* out5, void* workspace, size_t workspace_bytes, shg_stream_t stream) {
     SHG_REQUIRE(frame && cl1 && ranks_frame2 && ranks_cl13 && out5 && workspace, SHG_E_ARG, "shg_contrast_stats_u16: null pointer");
-    const size_t c_old = (shg_clahe_workspace_bytes(tiles, 2) + 255) / 256 * 256, s2 = (shg_select_u16_workspace_bytes(2) + 255) / 256 * 256;
-    SHG_REQUIRE(c_old != 0 && workspace_bytes >= shg_contrast_stats_workspace_bytes(tiles), SHG_E_WORKSPACE,
+    SHG_REQUIRE(shg_contrast_stats_workspace_bytes(tiles) != 0 && workspace_bytes >= shg_contrast_stats_workspace_bytes(tiles), SHG_E_WORKSPACE,
                 "shg_contrast_stats_u16: workspace too small or bad tile count");
     SHG_REQUIRE(h > 0 && w > 0, SHG_E_ARG, "shg_contrast_stats_u16: empty image");
     // a workspace of shg_contrast_stats_workspace_bytes_for(h, w, tiles) lets CLAHE build its histograms without atomics
     const bool roomy = workspace_bytes >= shg_contrast_stats_workspace_bytes_for(h, w, tiles);
-    const size_t c = roomy ? (shg_clahe_workspace_bytes_for(h, w, tiles, 2) + 255) / 256 * 256 : c_old;
+    const StatsLayout lay = stats_layout(roomy ? shg_clahe_workspace_bytes_for(h, w, tiles, 2) : shg_clahe_workspace_bytes(tiles, 2));
+    const Tuning tune = read_tuning();
     char* ws = static_cast<char*>(workspace);
-    const uint32_t* chunk_tile = nullptr;
-    // When the tile grid divides the image, CLAHE's tile histograms (still at the head of its workspace) add up to the
-    // histogram of the frame: np.percentile(frame, q)'s two order statistics are read off them (k_chunk_sums, k_hist_ranks)
-    // instead of selecting over the image again (two passes of k_select16_pass).
-    // the select on the CLAHE image (3 ranks): its histograms are zero before the interpolation kernel, which counts
-    // the first pass while the pixels are in its registers
-    uint32_t* sel3 = reinterpret_cast<uint32_t*>(ws + c + s2);
-    bool pass0_done = false, sel_zeroed = false;         // (zeroed by CLAHE's histogram reduction on the way, or by a memset where that does not run)
-    bool window = select_window_wanted(1);
-    if (int e = clahe_impl(frame, h, w, pitch, 2, clip_limit, tiles, cl1, cl1_pitch, ws, c, stream, &chunk_tile, sel3, (1 + 3) * 256, &pass0_done, nullptr,
-                           &sel_zeroed, nullptr, nullptr, &window))
-        return e;
-    SHG_REQUIRE(sel_zeroed, SHG_E_RUNTIME, "shg_contrast_stats_u16: the select histograms were not zeroed");
+    // the select on the CLAHE image (3 ranks): its histograms are zeroed by CLAHE's histogram reduction on the way (or by a memset
+    // where that does not run), and the blend kernel counts the first pass while the pixels are in its registers
+    ClaheRequest cr{one_disk(frame, cl1), Shape{h, w, pitch, cl1_pitch, 2, clip_limit, tiles}, ws, lay.select2, stream};
+    cr.want_chunks = true;
+    cr.sel_hist = reinterpret_cast<uint32_t*>(ws + lay.select3);
+    cr.sel_stride = (1 + 3) * 256;
+    cr.want_window = tune.window_for(1);
+    const ClaheResult c = clahe_impl(cr, tune);
+    if (c.err) return c.err;
+    SHG_REQUIRE(c.sel_zeroed, SHG_E_RUNTIME, "shg_contrast_stats_u16: the select histograms were not zeroed");
     if (h % tiles == 0 && w % tiles == 0) {
-        const size_t s3r = (select3_area_bytes() + 255) / 256 * 256;
-        uint32_t* chunk_sums = reinterpret_cast<uint32_t*>(ws + c + s2 + s3r);
-        Ranks8 ranks = {};
-        for (int i = 0; i < 2; ++i) {
-            SHG_REQUIRE(ranks_frame2[i] >= 0 && ranks_frame2[i] < h * w, SHG_E_ARG, "shg_contrast_stats_u16: rank %lld outside the image", (long long)ranks_frame2[i]);
-            ranks.v[i] = ranks_frame2[i];
-        }
+        // When the tile grid divides the image, CLAHE's tile histograms (still at the head of its workspace) add up to the
+        // histogram of the frame: np.percentile(frame, q)'s two order statistics are read off them (k_chunk_sums, k_hist_ranks)
+        // instead of selecting over the image again (two passes of k_select16_pass).
+        Ranks8 ranks;
+        if (int e = frame_ranks(ranks_frame2, h * w, &ranks)) return e;
         hipStream_t st = shg::as_stream(stream);
+        const uint32_t* hist = reinterpret_cast<const uint32_t*>(ws);
+        const int ntiles = tiles * tiles;
         SHG_PROF("hist_ranks", st);
-        if (chunk_tile) {                                // left by k_hist_reduce, one set per tile
-            if (int e = shg::launch(k_hist_ranks, dim3(2), dim3(1024), 0, st,
-                                   HistRanksArgs{reinterpret_cast<const uint32_t*>(ws), chunk_tile, tiles * tiles, tiles * tiles, ranks, out5, 0, 0}, "k_hist_ranks"))
-                return e;
-        } else {
-            k_chunk_sums<<<64, 1024, 0, st>>>(reinterpret_cast<const uint32_t*>(ws), tiles * tiles, chunk_sums);
+        const uint32_t* chunks = c.chunk_tile;           // left by k_hist_reduce, one set per tile -- or summed here, one set in all
+        if (!chunks) {
+            uint32_t* chunk_sums = reinterpret_cast<uint32_t*>(ws + lay.chunk_sums);
+            k_chunk_sums<<<64, 1024, 0, st>>>(hist, ntiles, chunk_sums);
             if (int e = shg::check_launch("k_chunk_sums")) return e;
-            if (int e = shg::launch(k_hist_ranks, dim3(2), dim3(1024), 0, st,
-                                   HistRanksArgs{reinterpret_cast<const uint32_t*>(ws), chunk_sums, 1, tiles * tiles, ranks, out5, 0, 0}, "k_hist_ranks"))
-                return e;
+            chunks = chunk_sums;
         }
-    } else if (int e = shg_select_u16(frame, h, w, pitch, ranks_frame2, 2, out5, ws + c, s2, stream)) return e;
-    return select_u16_impl(cl1, h, w, cl1_pitch, ranks_cl13, 3, out5 + 2, sel3, shg_select_u16_workspace_bytes(3), stream, true, pass0_done, nullptr, 0,
-                           window && pass0_done);
+        if (int e = shg::launch(k_hist_ranks, dim3(2), dim3(1024), 0, st, HistRanksArgs{hist, chunks, c.chunk_tile ? ntiles : 1, ntiles, ranks, out5, 0, 0}, "k_hist_ranks"))
+            return e;
+    } else if (int e = shg_select_u16(frame, h, w, pitch, ranks_frame2, 2, out5, ws + lay.select2, lay.select3 - lay.select2, stream)) return e;
+    SelectRequest sr{one_disk(cl1, nullptr), h, w, cl1_pitch, ranks_cl13, 3, out5 + 2, 0, cr.sel_hist, select_bytes(3), stream};
+    sr.after = c;
+    return select_u16_impl(sr, tune);
 }
+
+bool shg::contrast_stats_batches(int64_t h, int64_t w, int tiles, double clip_limit) { return batched_route(h, w, tiles, clip_limit, read_tuning()); }
 
 // image_process's CLAHE + order statistics for the k disks of a file in one launch per kernel (shg_stage_process_frames; a
 // Doppler stack, Solex_recon.py:105-133).  host_frames / host_cl1: device pointers of k images of one shape; out5: [k][5];
-// workspace: k areas of shg_contrast_stats_workspace_bytes_for(h, w, tiles) bytes.  The batched launches need the atomics-free
-// CLAHE path (clip limit within the u16 range); anything else goes disk by disk through shg_contrast_stats_u16 -- same results
-// either way.  The frame's percentiles are read off the tile histograms -- on a grid that does not divide the image less the pixels
-// of the reflected border (BorderPx), and there out5[5 i + 0 / 1] may come back NaN: "select over frame i instead" (hist_rank_top_job).
-// Whether contrast_stats_batch takes its batched route (one launch per kernel for all disks, the slice histograms, the percentiles
-// read off them) for images of this shape -- the route that can also MAKE the images on its way (FrameSource).
-// SHG_CONTRAST_BATCH=0 (the tests): every disk through shg_contrast_stats_u16, one after the other -- the route these launches replaced
-static bool contrast_batch_allowed() {                       // (read at every call: the tests hold one setting against the other)
-    const char* v = getenv("SHG_CONTRAST_BATCH");
-    return !(v && v[0] == '0');
-}
-
-bool shg::contrast_stats_batches(int64_t h, int64_t w, int tiles, double clip_limit) {
-    if (!contrast_batch_allowed()) return false;
-    if (!(tiles >= 1 && tiles <= 16 && h > 0 && w > 0 && h < 65536 && clip_limit > 0.0)) return false;
-    if (!(h % tiles == 0 && w % tiles == 0) && !(h > tiles && w > tiles)) return false;     // (a reflected border needs tiles + 1 pixels to mirror)
-    int64_t th, tw;
-    tile_geometry(h, w, tiles, &th, &tw);
-    if (th * tw >= (1ll << 31) || tw > 65535) return false;
-    const int clip = (int)(clip_limit * (double)(th * tw) / HIST16);
-    return clip <= 65535 && slice_rows_of(tw, 65535) <= kFusedMaxSliceRows;
-}
-
+// workspace: k areas of shg_contrast_stats_workspace_bytes_for(h, w, tiles) bytes.  Shapes that batched_route() refuses, a single
+// disk that is not to be made on the way, and a workspace too small for all disks at once go disk by disk through
+// shg_contrast_stats_u16 -- same results either way.
+// The frame's percentiles are read off the tile histograms -- on a grid that does not divide the image less the pixels of the
+// reflected border (BorderPx), and there out5[5 i + 0 / 1] may come back NaN: "select over frame i instead" (hist_rank_top_job).
 int shg::contrast_stats_batch(const uint16_t* const* host_frames, int64_t k, int64_t h, int64_t w, int64_t pitch, double clip_limit, int tiles,
                               uint16_t* const* host_cl1, int64_t cl1_pitch, const int64_t* ranks_frame2, const int64_t* ranks_cl13, double* out5,
                               void* workspace, size_t workspace_bytes, shg_stream_t stream, const FrameSource* from) {
@@ -2214,14 +2238,8 @@ int shg::contrast_stats_batch(const uint16_t* const* host_frames, int64_t k, int
     SHG_REQUIRE(h > 0 && w > 0, SHG_E_ARG, "shg_contrast_stats_u16: empty image");
     const size_t per = shg_contrast_stats_workspace_bytes_for(h, w, tiles);
     SHG_REQUIRE(per != 0, SHG_E_WORKSPACE, "shg_contrast_stats_u16: bad tile count");
-    bool batched = contrast_batch_allowed() && (k > 1 || from) && workspace_bytes >= (size_t)k * per && tiles >= 1 && tiles <= 16 && clip_limit > 0.0 &&
-                   ((h % tiles == 0 && w % tiles == 0) || (h > tiles && w > tiles));
-    if (batched) {
-        int64_t th, tw;
-        tile_geometry(h, w, tiles, &th, &tw);
-        const int clip = (int)(clip_limit * (double)(th * tw) / HIST16);
-        batched = clip <= 65535;                                   // (clip = max(clip, 1) >= 1)
-    }
+    const Tuning tune = read_tuning();
+    const bool batched = (k > 1 || from) && workspace_bytes >= (size_t)k * per && batched_route(h, w, tiles, clip_limit, tune);
     SHG_REQUIRE(batched || !from, SHG_E_ARG, "shg_contrast_stats_u16: a frame source needs the batched route (contrast_stats_batches)");
     if (!batched) {
         const size_t each = workspace_bytes >= (size_t)k * per ? per : 0;       // every disk its own area if there is room, else one after the other in the same
@@ -2232,56 +2250,36 @@ int shg::contrast_stats_batch(const uint16_t* const* host_frames, int64_t k, int
         return 0;
     }
     hipStream_t st = shg::as_stream(stream);
-    const size_t c = (shg_clahe_workspace_bytes_for(h, w, tiles, 2) + 255) / 256 * 256, s2 = (shg_select_u16_workspace_bytes(2) + 255) / 256 * 256;
-    Ranks8 ranks = {};
-    for (int i = 0; i < 2; ++i) {
-        SHG_REQUIRE(ranks_frame2[i] >= 0 && ranks_frame2[i] < h * w, SHG_E_ARG, "shg_contrast_stats_u16: rank %lld outside the image", (long long)ranks_frame2[i]);
-        ranks.v[i] = ranks_frame2[i];
-    }
+    const StatsLayout lay = stats_layout(shg_clahe_workspace_bytes_for(h, w, tiles, 2));
+    Ranks8 ranks;
+    if (int e = frame_ranks(ranks_frame2, h * w, &ranks)) return e;
     for (int64_t i0 = 0; i0 < k; i0 += shg::kMaxBatch) {
         const int m = (int)std::min<int64_t>(shg::kMaxBatch, k - i0);
         char* ws = static_cast<char*>(workspace) + (size_t)i0 * per;
-        Disks d;
-        d.src = {};
-        d.dst = {};
-        d.n = m;
-        d.zs = per;
-        for (int i = 0; i < m; ++i) {
-            SHG_REQUIRE(host_frames[i0 + i] && host_cl1[i0 + i], SHG_E_ARG, "shg_contrast_stats_u16: null image");
-            d.src.p[i] = host_frames[i0 + i];
-            d.dst.p[i] = host_cl1[i0 + i];
-            if (from) d.from.raw.p[i] = from->host_raw[i0 + i];
-        }
-        if (from) {
-            d.fused = true;
-            d.from.raw_pitch = from->raw_pitch;
-            d.from.c = from->factors ? from->factors + i0 * h : nullptr;
-            d.from.sx0 = from->sx0;
-            d.from.dx0 = from->dx0;
-            d.from.ncopy = from->ncopy;
-        }
-        // the selects on the CLAHE images: their slot histograms zeroed up front, every disk's in its own area
-        uint32_t* sel3 = reinterpret_cast<uint32_t*>(ws + c + s2);
-        const uint32_t* chunk_tile = nullptr;
-        bool pass0_done = false, sel_zeroed = false;
+        for (int i = 0; i < m; ++i) SHG_REQUIRE(host_frames[i0 + i] && host_cl1[i0 + i], SHG_E_ARG, "shg_contrast_stats_u16: null image");
+        Disks d{shg::make_batch(host_frames, (int)i0, m), shg::make_batch(host_cl1, (int)i0, m), m, per, from != nullptr};
+        if (from) d.from = FusedSrc{shg::make_batch(from->host_raw, (int)i0, m), from->raw_pitch, from->factors ? from->factors + i0 * h : nullptr,
+                                    from->sx0, from->dx0, from->ncopy};
         const RanksJob job{{ranks.v[0], ranks.v[1]}, out5 + 5 * i0, 5};
-        bool ranks_done = false;
-        bool window = select_window_wanted(m);
-        if (int e = clahe_impl(host_frames[i0], h, w, pitch, 2, clip_limit, tiles, host_cl1[i0], cl1_pitch, ws, c, stream, &chunk_tile, sel3, (1 + 3) * 256,
-                               &pass0_done, &d, &sel_zeroed, &job, &ranks_done, &window))
-            return e;
-        SHG_REQUIRE(chunk_tile && sel_zeroed, SHG_E_RUNTIME, "shg_contrast_stats_u16: the batched path did not take the slice histograms");
-        if (!ranks_done) {
+        ClaheRequest cr{d, Shape{h, w, pitch, cl1_pitch, 2, clip_limit, tiles}, ws, lay.select2, stream};
+        cr.want_chunks = true;
+        cr.sel_hist = reinterpret_cast<uint32_t*>(ws + lay.select3);     // the selects on the CLAHE images: every disk's slot histograms in its own area
+        cr.sel_stride = (1 + 3) * 256;
+        cr.want_window = tune.window_for(m);
+        cr.ranks = &job;
+        const ClaheResult c = clahe_impl(cr, tune);
+        if (c.err) return c.err;
+        SHG_REQUIRE(c.chunk_tile && c.sel_zeroed, SHG_E_RUNTIME, "shg_contrast_stats_u16: the batched path did not take the slice histograms");
+        if (!c.ranks_done) {
             SHG_PROF("hist_ranks", st);
             if (int e = shg::launch(k_hist_ranks, dim3(2u, 1u, (unsigned)m), dim3(1024), 0, st,
-                                   HistRanksArgs{reinterpret_cast<const uint32_t*>(ws), chunk_tile, tiles * tiles, tiles * tiles, ranks, out5 + 5 * i0, per, 5}, "k_hist_ranks"))
+                                   HistRanksArgs{reinterpret_cast<const uint32_t*>(ws), c.chunk_tile, tiles * tiles, tiles * tiles, ranks, out5 + 5 * i0, per, 5}, "k_hist_ranks"))
                 return e;
         }
-        Disks dc = d;
-        dc.src = d.dst;                                            // the selects read the CLAHE images
-        if (int e = select_u16_impl(host_cl1[i0], h, w, cl1_pitch, ranks_cl13, 3, out5 + 5 * i0 + 2, sel3, shg_select_u16_workspace_bytes(3), stream, true,
-                                    pass0_done, &dc, 5, window && pass0_done))
-            return e;
+        d.src = d.dst;                                             // the selects read the CLAHE images
+        SelectRequest sr{d, h, w, cl1_pitch, ranks_cl13, 3, out5 + 5 * i0 + 2, 5, cr.sel_hist, select_bytes(3), stream};
+        sr.after = c;
+        if (int e = select_u16_impl(sr, tune)) return e;
     }
     return 0;
 }

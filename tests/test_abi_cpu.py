@@ -44,6 +44,65 @@ def test_workspace_queries_need_no_gpu():
     assert lib.shg_contrast_stats_workspace_bytes_for(2000, 2096, 2) == lib.shg_contrast_stats_workspace_bytes(2) + 4 * 33 * 131072 + 4 * 1024 * 4 + 4 * 128 * 4
 
 
+def _up256(n):
+    return (n + 255) // 256 * 256
+
+
+def _clahe_bytes(tiles, bpp):
+    """[hist | lut]: a u32 histogram and a u16 LUT of hist_size entries per tile."""
+    if not 1 <= tiles <= 16 or bpp not in (1, 2):
+        return 0
+    return tiles * tiles * (256 if bpp == 1 else 65536) * (4 + 2)
+
+
+def _clahe_bytes_for(h, w, tiles, bpp):
+    """16-bit: behind [hist | lut] (rounded up to 256 bytes) one 128 KiB slice histogram per run of whole tile rows holding at most
+    32768 pixels, 1024 words of chunk sums a tile, 128 words of clipped totals a tile.  The tiles are OpenCV's: a grid that does
+    not divide the image extends BOTH axes to the next multiple (a dividing axis by a whole tile count)."""
+    base = _clahe_bytes(tiles, bpp)
+    if base == 0 or h <= 0 or w <= 0:
+        return 0
+    if bpp == 1:
+        return base
+    if h % tiles or w % tiles:
+        h, w = h + tiles - h % tiles, w + tiles - w % tiles
+    th, tw = h // tiles, w // tiles
+    rows = 1 if tw >= 32768 else 32768 // tw
+    slices = -(-th // rows)
+    return _up256(base) + tiles * tiles * (slices * 131072 + 1024 * 4 + 128 * 4)
+
+
+def _select_bytes(n_ranks):
+    """Eight copies of (1 + n_ranks) 256-bin histograms, then the ranks."""
+    return 8 * (1 + n_ranks) * 256 * 4 + n_ranks * 8 if 1 <= n_ranks <= 8 else 0
+
+
+def _contrast_stats_bytes(clahe_bytes):
+    """[clahe | 2-rank select | 3-rank select + window (8 copies of 8 x 256 counts) + its 16-byte state | chunk sums], each
+    rounded up to 256 bytes."""
+    if clahe_bytes == 0:
+        return 0
+    select3 = _select_bytes(3) + 8 * 8 * 256 * 4 + 16
+    return _up256(clahe_bytes) + _up256(_select_bytes(2)) + _up256(select3) + _up256(1024 * 4)
+
+
+def test_workspace_queries_follow_the_documented_layout():
+    from solex_ser_recon_en_amd._lib import lib
+    shapes = [(2000, 2096), (2000, 2097), (201, 304), (64, 2096), (77, 50), (2560, 2675), (17, 17)]
+    for tiles in (0, 1, 2, 3, 4, 8, 16, 17):
+        for bpp in (1, 2, 3):
+            assert lib.shg_clahe_workspace_bytes(tiles, bpp) == _clahe_bytes(tiles, bpp), (tiles, bpp)
+            for h, w in shapes + [(0, 17), (17, 0), (-1, 17), (17, -1)]:
+                assert lib.shg_clahe_workspace_bytes_for(h, w, tiles, bpp) == _clahe_bytes_for(h, w, tiles, bpp), (h, w, tiles, bpp)
+        assert lib.shg_contrast_stats_workspace_bytes(tiles) == _contrast_stats_bytes(_clahe_bytes(tiles, 2)), tiles
+        for h, w in shapes + [(0, 17), (17, 0), (-1, 17), (17, -1)]:
+            assert lib.shg_contrast_stats_workspace_bytes_for(h, w, tiles) == _contrast_stats_bytes(_clahe_bytes_for(h, w, tiles, 2)), (h, w, tiles)
+    for n_ranks in range(0, 10):
+        assert lib.shg_select_u16_workspace_bytes(n_ranks) == _select_bytes(n_ranks), n_ranks
+    assert lib.shg_select_u16_workspace_bytes(0) == 0 and lib.shg_select_u16_workspace_bytes(9) == 0
+    assert lib.shg_clahe_workspace_bytes(0, 2) == 0 and lib.shg_clahe_workspace_bytes(17, 2) == 0 and lib.shg_clahe_workspace_bytes(2, 3) == 0
+
+
 def test_argument_errors_are_reported_not_thrown():
     """Bad arguments are rejected before any HIP call, so this runs without a GPU."""
     from solex_ser_recon_en_amd import _lib
