@@ -424,7 +424,10 @@ int shg_scale_rows_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch,
  * shg_lin_filter_apply: delta = hl/linlen - (sum of hf over rows y-half_width..y+half_width except y)
  * /(2*half_width*linlen); kept on columns [xa[y], xb[y]), copied from column xa+edge_half into
  * [xa, xa+edge_half) when edge[y] & 1, from xb-edge_half-1 into [xb-edge_half, xb) when edge[y] & 2,
- * zero elsewhere; dst = min(img * exp(-delta * taper[y]), 65535) truncated (solex_util.py:352, 423). */
+ * zero elsewhere; dst = min(img * exp(-delta * taper[y]), 65535) truncated (solex_util.py:352, 423).
+ * Each edge zone must lie inside [xa, xb) and the two must not overlap (xb - xa >= 2*edge_half + 1 where
+ * both bits are set): the kernel takes the left zone first and writes nothing outside [xa, xb), the
+ * reference's two slice assignments let the right zone win, so an overlap is resolved differently. */
 int shg_lin_filter_row_sums(const uint16_t* img, int64_t h, int64_t w, int64_t pitch,
                             const double* row_factor, const float* log_lut, const uint8_t* flagged,
                             const int32_t* up, const int32_t* dn, int linlen, double* hl, double* hf,
