@@ -309,6 +309,37 @@ int shg_map_plane_moments(const float* map, int64_t h, int64_t w, int64_t pitch,
 int shg_map_detrend(const float* map, int64_t h, int64_t w, int64_t pitch, const double* plane3, float* out, int64_t out_pitch,
                     uint16_t* png, int64_t png_pitch, double display_range, shg_stream_t stream);
 
+/* ---- flattening the disk: the median of every one-pixel annulus around the centre, and the division by that profile (not a
+ * reference stage; tests/flatten_ref.py restates both calls in NumPy, bit for bit).
+ * The ring of a pixel.  circle3 (host) = (cx, cy, rad).  For the pixel in row r, column c: dx = (double)c - cx, dy = (double)r - cy,
+ * d2 = dx * dx + dy * dy -- the circle test's float64 steps, one IEEE operation each, no contraction.  The pixel is ON THE DISK iff
+ * not d2 > rad * rad (the test of shg_doppler_finish and shg_map_plane_moments).  Its RING is the largest integer k with
+ * (double)k * (double)k <= d2: no square root is part of the definition.  There are K = floor(rad) + 1 rings, and the ring of a pixel
+ * on the disk is < K.
+ * shg_ring_medians_u16: with n the number of pixels of the image that are on the disk and in ring k, for every k < n_rings
+ *   count[k] = n, lo[k] = the (n - 1) / 2-th smallest of their values, hi[k] = the n / 2-th smallest (0-based, integer division: the
+ *   median is (lo + hi) / 2); lo[k] = hi[k] = 0 when n = 0.
+ * count, lo and hi are device memory of n_rings elements; the call overwrites them.  Everything accumulated is an integer count, so
+ * the result depends neither on the launch grid nor on the order of any atomic.  workspace: shg_ring_medians_u16_workspace_bytes
+ * (n_rings), which is 0 for n_rings outside [1, 16384] and needs no GPU.  1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG for a
+ * null pointer, pitch < w, a circle that is not finite, rad < 0, rad >= 16384, |cx| or |cy| >= 65536, n_rings != floor(rad) + 1, or a
+ * workspace that is too small.  On any error nothing is written.  The call neither waits for the device nor copies from it. */
+size_t shg_ring_medians_u16_workspace_bytes(int64_t n_rings);
+int shg_ring_medians_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, int64_t n_rings,
+                         uint32_t* count, uint16_t* lo, uint16_t* hi, void* workspace, size_t workspace_bytes, shg_stream_t stream);
+
+/* shg_ring_flatten_u16: gain (host) = K = n_rings doubles, gain[k] standing for the radius k + 1/2.  Off the disk
+ * out[r * out_pitch + c] = v = img[r * pitch + c].  On the disk, one IEEE float64 operation a step:
+ *   rho = sqrt(d2), correctly rounded;  u = rho - 0.5;
+ *   g = gain[0] if u <= 0;  g = gain[K - 1] if u >= (double)(K - 1);
+ *   else j = (int64)u (truncation), t = u - (double)j, g = gain[j] + (gain[j + 1] - gain[j]) * t;
+ *   out = (uint16)clip(rint((double)v * g), 0, 65535), rint to nearest, ties to even.
+ * out may be img when the pitches are equal (in place).  Elements between w and a pitch are never touched.  Limits and codes as
+ * shg_ring_medians_u16; SHG_E_ARG also for a gain that is negative or not finite, an output pitch < w, and out == img with another
+ * pitch. */
+int shg_ring_flatten_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, const double* gain,
+                         int64_t n_rings, uint16_t* out, int64_t out_pitch, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

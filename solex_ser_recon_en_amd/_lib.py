@@ -101,6 +101,9 @@ SIGNATURES = {
                                          P, c_int64, c_int64, P, c_int64, c_int64, c_int, c_double, P]),
     'shg_map_plane_moments': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P]),
     'shg_map_detrend': (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, c_double, P]),
+    'shg_ring_medians_u16_workspace_bytes': (c_size_t, [c_int64]),
+    'shg_ring_medians_u16': (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P, P, P, P, c_size_t, P]),
+    'shg_ring_flatten_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
     'shg_blur_fits_fused': (c_int, [c_int64, c_int]),
     'shg_blur_row_mean_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, P, P]),
     'shg_blur_argmin_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int64, c_int64, P, P, P]),

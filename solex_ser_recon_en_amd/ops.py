@@ -971,3 +971,54 @@ def map_detrend(m, plane, display_range=None, out=None):
     _lib.check(lib.shg_map_detrend(ptr, h, w, pitch, _host_ptr(p3), optr, opitch, None if png is None else png.data_ptr(), w,
                                    0.0 if display_range is None else float(display_range), _stream()), 'shg_map_detrend')
     return out, png
+
+
+# ---- flattening the disk: ring medians and the division by the radial profile -------------------------
+def _circle3(circle):
+    """(circle as a host float64 [3] array, K = floor(rad) + 1 rings)."""
+    c3 = np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    if c3.size != 3:
+        raise ValueError('circle is (cx, cy, r)')
+    if not (np.isfinite(c3).all() and 0.0 <= c3[2] < 16384.0):
+        raise ValueError('circle (%r, %r, %r) must be finite with a radius in [0, 16384)' % tuple(c3))
+    return c3, int(np.floor(c3[2])) + 1
+
+
+def ring_medians_u16(img, circle, out=None):
+    """shg_ring_medians_u16: for each of the K = floor(r) + 1 one-pixel rings around the centre of `circle` (cx, cy, r), over the
+    pixels of the uint16 image that lie on the disk -> (count uint32 [K], lo uint16 [K], hi uint16 [K]) on the image's device: the
+    ring's pixels, its (n - 1) / 2-th and its n / 2-th smallest value (the median is (lo + hi) / 2; both 0 for an empty ring).
+    out: the caller's three tensors, overwritten."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    c3, k = _circle3(circle)
+    if out is None:
+        out = (torch.empty(k, dtype=torch.uint32, device=img.device), torch.empty(k, dtype=torch.uint16, device=img.device),
+               torch.empty(k, dtype=torch.uint16, device=img.device))
+    count, lo, hi = out
+    for t, dt in ((count, torch.uint32), (lo, torch.uint16), (hi, torch.uint16)):
+        if _dev(t, 'out').dtype != dt or tuple(t.shape) != (k,) or not t.is_contiguous():
+            raise ValueError('out is (count uint32 [%d], lo uint16 [%d], hi uint16 [%d]), contiguous' % (k, k, k))
+    need = lib.shg_ring_medians_u16_workspace_bytes(k)
+    ws = torch.empty(need, dtype=torch.uint8, device=img.device)
+    _lib.check(lib.shg_ring_medians_u16(ptr, h, w, pitch, _host_ptr(c3), k, count.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                                        ws.data_ptr(), need, _stream()), 'shg_ring_medians_u16')
+    return count, lo, hi
+
+
+def ring_flatten_u16(img, circle, gain, out=None):
+    """shg_ring_flatten_u16: every on-disk pixel of the uint16 image times the gain of its radius (gain float64 [K] on the host,
+    gain[k] at radius k + 1/2, linear in between, constant beyond either end), rounded to nearest even and saturated; pixels off
+    the disk as they are -> uint16 [h, w].  out: the caller's view (the image itself: in place), else a new one."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    c3, k = _circle3(circle)
+    g = np.ascontiguousarray(gain, dtype=np.float64).reshape(-1)
+    if g.size != k:
+        raise ValueError('gain must hold %d values (floor(r) + 1), got %d' % (k, g.size))
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.uint16, device=img.device)
+    optr, oh, ow, opitch = _img(out, 'out', torch.uint16)
+    if (oh, ow) != (h, w):
+        raise ValueError('out must be a uint16 [%d, %d] view' % (h, w))
+    _lib.check(lib.shg_ring_flatten_u16(ptr, h, w, pitch, _host_ptr(c3), _host_ptr(g), k, optr, opitch, _stream()),
+               'shg_ring_flatten_u16')
+    return out
