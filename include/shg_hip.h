@@ -340,6 +340,57 @@ int shg_ring_medians_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitc
 int shg_ring_flatten_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, const double* gain,
                          int64_t n_rings, uint16_t* out, int64_t out_pitch, shg_stream_t stream);
 
+/* ---- stacking a series of scans: the resample-and-combine of N registered disks in one launch, and the exact sum of squared
+ * differences over a window of integer offsets that refines a registration (not reference stages; tests/stack_ref.py restates both
+ * calls in NumPy, bit for bit).
+ * shg_stack_combine_u16.  host_srcs (host): n device pointers to uint16 images; host_dims3 (host) = [n][3] int64 (h_j, w_j, pitch_j);
+ * host_xform4 (host) = [n][4] doubles (s_j, tx_j, ty_j, gain_j): the similarity transform from the output grid into source j and
+ * the factor on its values.  Everything is float64, one IEEE operation a step, no contraction.  For the output pixel in row r,
+ * column c and source j, in source order:
+ *   sx = tx + s * (double)c;  sy = ty + s * (double)r;
+ *   the sample is PRESENT iff sx >= 0 && sx <= (double)(w - 1) && sy >= 0 && sy <= (double)(h - 1);
+ *   x0 = (int64)sx (truncation), x1 = min(x0 + 1, w - 1), fx = sx - (double)x0;  y0, y1, fy the same from sy and h;
+ *   with a = src[y0][x0], b = src[y0][x1], c = src[y1][x0], d = src[y1][x1] as doubles:
+ *   top = a + (b - a) * fx;  bot = c + (d - c) * fx;  val = top + (bot - top) * fy;  v_j = val * gain_j.
+ * With n' the number of present samples and v the present samples in source order:
+ *   n' = 0: out = 0, count = 0.
+ *   SHG_STACK_MEAN: m = (((v_0 + v_1) + v_2) + ...) / (double)n';  count = n'.
+ *   SHG_STACK_MEDIAN: with the v sorted, m = (v[(n' - 1) / 2] + v[n' / 2]) / 2 (integer division in the ranks);  count = n'.
+ *   SHG_STACK_SIGMA: the kappa-sigma clipped mean; count = the number of samples kept.  For n' < 3 it is the mean.  Otherwise the kept
+ *     set K is at first every present sample, and up to `iterations` times:
+ *       m = (the sum of the kept v, in source order) / (double)|K|;  q = the sum, in source order, of (v - m) * (v - m) over K;
+ *       lim = kappa * sqrt(q / (double)|K|), the square root correctly rounded;  K' = the j of K with |v_j - m| <= lim;
+ *       K' empty: K stays as it was and the passes end;  K' = K: the passes end;  else K = K', and the passes end when |K| < 3.
+ *     m = the in-order mean of K.
+ *   out[r * out_pitch + c] = (uint16)clip(rint(m), 0, 65535), rint to nearest, ties to even;  count[r * count_pitch + c] = the count
+ *   (count may be NULL).  (A v that overflows to infinity saturates the mean; under SIGMA its deviation is not a number, no sample
+ *   is kept, and the rule for an empty K' applies.)
+ * Elements between ow and a pitch are never touched.  1 <= n <= 32, else SHG_E_ARG.  1 <= oh, ow, h_j, w_j <= 16384, else
+ * SHG_E_UNSUPPORTED.  SHG_E_ARG for a null pointer (count excepted), a pitch below its width, an s that is not finite and > 0, a tx,
+ * ty or gain that is not finite, a gain < 0, an unknown mode, a kappa that is NaN or < 1, iterations outside [1, 3] (kappa and
+ * iterations are checked whatever the mode), and an output or count plane that overlaps a source or the other.  On any error
+ * nothing is written.  The call allocates nothing, waits for nothing and copies nothing from the device. */
+#define SHG_STACK_MEAN   0
+#define SHG_STACK_MEDIAN 1
+#define SHG_STACK_SIGMA  2
+int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
+                          double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
+                          int64_t count_pitch, shg_stream_t stream);
+
+/* shg_shift_ssd_u16: ref and img are uint16 images of h x w on one grid (pitches ref_pitch, img_pitch).  The pixel set, the same for
+ * every offset: every (r, c) with S <= c < w - S and S <= r < h - S that, given a circle3 (host; NULL or (-1, -1, -1): no circle),
+ * is ON THE DISK by the test of the flatten section above (not d2 > rad * rad in its float64 steps).  For every integer offset
+ * (u, v) with |u|, |v| <= S:
+ *   ssd[(v + S) * (2 S + 1) + (u + S)] = the sum over the set of (ref[r][c] - img[r + v][c + u])^2, as uint64;
+ *   ssd[(2 S + 1)^2] = the number of pixels in the set.
+ * ssd is device memory of (2 S + 1)^2 + 1 uint64; the call overwrites it (its clearing pass is part of the call).  A term is below
+ * (2^16)^2 and an image holds at most 2^28 pixels: a sum stays below 2^60 < 2^64.  All sums are integers: the result depends neither
+ * on the launch grid nor on the order of any atomic.  0 <= S <= 8, else SHG_E_ARG.  1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.
+ * SHG_E_ARG for a null pointer, a pitch < w, and a circle that is not finite (an empty set -- w or h < 2 S + 1, a circle off the
+ * image -- is no error: every sum and the count are 0).  On any error nothing is written. */
+int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w, int S,
+                      const double* circle3, uint64_t* ssd, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -1,0 +1,379 @@
+// Stacking a series of scans: the resample-and-combine of N registered disks (shg_stack_combine_u16) and the exact sum of squared
+// differences over a window of integer offsets (shg_shift_ssd_u16).  Not reference stages: the arithmetic is the one
+// include/shg_hip.h states, restated in NumPy by tests/stack_ref.py.  The host finds the transforms (stack.py); the GPU resamples,
+// combines and sums.
+//
+// Combine: one launch, the resampled planes never leave the registers.  A thread owns eight adjacent output columns of one row and
+// works through them one after the other: the four 2-byte gathers a source costs a pixel then fall, for the thread's own columns
+// and for those of the lanes beside it, into the same cache lines (s is within a few per cent of 1), and the eight results leave
+// in one 16-byte store (the counts in one 8-byte store) where pointer and pitch allow, element by element otherwise.  The source
+// count and the per-source records are wave-uniform: they are read from the kernel's arguments (32 records of 56 bytes), where
+// they are used (see k_stack_combine on why not once a thread).  The samples of a pixel sit in a private array that is only ever
+// indexed by compile-time constants -- the kernel is a template on a capacity of 4 / 8 / 16 / 32 sources and on the mode, every
+// loop over the array is unrolled, a bit mask says which samples are present or kept -- so the array lives in registers: no
+// scratch.  The median pads the absent samples with +inf, runs a fixed bitonic network of compare-exchanges whose indices are
+// template arguments and picks its two ranks by masking the samples' bits.
+//
+// SSD: a workgroup walks 64 x 16 tiles; it holds the tile of img with a border of S pixels in LDS and its own four pixels of ref
+// in registers, and for each of the (2 S + 1)^2 offsets sums the squared differences of its pixels (a term is below 2^32, the sum
+// 64-bit), folds the wave with DPP and adds the wave's total to a table in LDS; at its end it adds the table's non-zero entries
+// to the output with 64-bit integer atomics.  Everything accumulated is an integer: neither the grid nor the order of the atomics
+// can change a bit.  A tile without a pixel of the set is skipped before its border is loaded.
+#include "shg_common.h"
+
+#include <math.h>
+#include <utility>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxDim = 16384;
+constexpr int kMaxSources = 32;
+
+// ---- combine ----
+constexpr int kOct = 8;                           // columns a thread owns
+constexpr int kLanesX = 32;                       // threads along a row: a workgroup spans 256 columns ...
+constexpr int kRows = kThreads / kLanesX;         // ... of 8 rows
+
+struct SourceRec {
+    const uint16_t* p;
+    int h, w;
+    int64_t pitch;
+    double s, tx, ty, gain;
+};
+
+struct CombineArgs {
+    uint16_t* out;
+    uint8_t* count;
+    int oh, ow;
+    int64_t out_pitch, count_pitch;
+    int n, iterations;
+    double kappa;
+    int vec_out, vec_count;           // rows of the output / of the counts start on 16 / 8 bytes
+    SourceRec src[kMaxSources];
+};
+static_assert(sizeof(CombineArgs) <= 4096, "kernel arguments");
+
+// The sample of source `s` at the output pixel (rd, cd): false when it is absent.
+__device__ __forceinline__ bool sample(const SourceRec& s, double cd, double rd, double* v) {
+    const double sx = s.tx + s.s * cd, sy = s.ty + s.s * rd;
+    if (!(sx >= 0.0 && sx <= (double)(s.w - 1) && sy >= 0.0 && sy <= (double)(s.h - 1))) return false;
+    const int x0 = (int)sx, y0 = (int)sy;                            // (0 <= sx <= w - 1 < 16384)
+    const int x1 = min(x0 + 1, s.w - 1), y1 = min(y0 + 1, s.h - 1);
+    const double fx = sx - (double)x0, fy = sy - (double)y0;
+    const uint16_t* row0 = s.p + (int64_t)y0 * s.pitch;
+    const uint16_t* row1 = s.p + (int64_t)y1 * s.pitch;
+    const double a = (double)row0[x0], b = (double)row0[x1], c = (double)row1[x0], d = (double)row1[x1];
+    const double top = a + (b - a) * fx, bot = c + (d - c) * fx;
+    const double val = top + (bot - top) * fy;
+    *v = val * s.gain;
+    return true;
+}
+
+// The sum, in index order, of the samples whose bit is set.  (The samples are >= +0: starting from 0.0 changes no bit.)
+template <int CAP>
+__device__ __forceinline__ double sum_of(const double (&v)[CAP], uint32_t mask) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j)
+        if (mask >> j & 1u) s = s + v[j];
+    return s;
+}
+
+// A fixed bitonic network over the CAP samples, ascending: every index is a template argument, so that the array is split into
+// registers before any loop would have to be unrolled.
+template <int CAP, int K, int J, int I>
+__device__ __forceinline__ void compare_exchange(double (&v)[CAP]) {
+    constexpr int L = I ^ J;
+    if constexpr (L > I) {
+        const double lo = fmin(v[I], v[L]), hi = fmax(v[I], v[L]);
+        constexpr bool up = (I & K) == 0;
+        v[I] = up ? lo : hi;
+        v[L] = up ? hi : lo;
+    }
+}
+template <int CAP, int K, int J, int... I>
+__device__ __forceinline__ void network_stage(double (&v)[CAP], std::integer_sequence<int, I...>) {
+    (compare_exchange<CAP, K, J, I>(v), ...);
+}
+template <int CAP, int K, int J>
+__device__ __forceinline__ void network_merge(double (&v)[CAP]) {
+    network_stage<CAP, K, J>(v, std::make_integer_sequence<int, CAP>{});
+    if constexpr (J > 1) network_merge<CAP, K, J / 2>(v);
+}
+template <int CAP, int K = 2>
+__device__ __forceinline__ void sort_network(double (&v)[CAP]) {
+    network_merge<CAP, K, K / 2>(v);
+    if constexpr (K < CAP) sort_network<CAP, K * 2>(v);
+}
+
+// The sample of rank `rank`: the bits of every sample under a mask that is all ones for that rank only (a chain of selects on the
+// values is turned back into a run-time index by the compiler, and the array with it into memory).
+template <int CAP>
+__device__ __forceinline__ double pick(const double (&v)[CAP], int rank) {
+    unsigned long long bits = 0;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) bits |= (unsigned long long)__double_as_longlong(v[j]) & (j == rank ? ~0ull : 0ull);
+    return __longlong_as_double((long long)bits);
+}
+
+// One output pixel -> its 16-bit value and its count.
+template <int CAP, int MODE>
+__device__ __forceinline__ void combine_pixel(const CombineArgs& a, int r, int c, int zero, uint32_t* value, uint32_t* count) {
+    double v[CAP];
+    uint32_t present = 0;
+    const double cd = (double)c, rd = (double)r;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+        v[j] = INFINITY;
+        if (j < a.n) {
+            double t;
+            if (sample(a.src[j + zero], cd, rd, &t)) v[j] = t, present |= 1u << j;
+        }
+        // four sources' gathers in flight at a time: without the fence the scheduler hoists the loads of all CAP sources and
+        // the registers of their addresses and records with them
+        if (j % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+    const int n = __popc(present);
+    *value = 0, *count = 0;
+    if (n == 0) return;
+    double m;
+    uint32_t kept = present;
+    if (MODE == SHG_STACK_MEDIAN) {
+        sort_network<CAP>(v);
+        m = (pick<CAP>(v, (n - 1) / 2) + pick<CAP>(v, n / 2)) / 2.0;
+    } else {
+        if (MODE == SHG_STACK_SIGMA && n >= 3) {
+            for (int pass = 0; pass < a.iterations; ++pass) {
+                const double size = (double)__popc(kept), mean = sum_of<CAP>(v, kept) / size;
+                double q = 0.0;
+#pragma unroll
+                for (int j = 0; j < CAP; ++j)
+                    if (kept >> j & 1u) {
+                        const double d = v[j] - mean;
+                        q = q + d * d;
+                    }
+                const double lim = a.kappa * sqrt(q / size);
+                uint32_t next = 0;
+#pragma unroll
+                for (int j = 0; j < CAP; ++j)
+                    if ((kept >> j & 1u) && fabs(v[j] - mean) <= lim) next |= 1u << j;
+                if (next == 0 || next == kept) break;
+                kept = next;
+                if (__popc(kept) < 3) break;
+            }
+        }
+        m = sum_of<CAP>(v, kept) / (double)__popc(kept);
+    }
+    *value = (uint32_t)fmin(fmax(rint(m), 0.0), 65535.0);
+    *count = (uint32_t)__popc(kept);
+}
+
+template <int CAP, int MODE>
+__global__ __launch_bounds__(kThreads) void k_stack_combine(const CombineArgs a) {
+    const int c0 = (blockIdx.x * kLanesX + (int)threadIdx.x % kLanesX) * kOct, r = blockIdx.y * kRows + (int)threadIdx.x / kLanesX;
+    if (r >= a.oh || c0 >= a.ow) return;
+    const int nc = min(kOct, a.ow - c0);
+    uint64_t lo = 0, hi = 0, counts = 0;          // columns 0 .. 3, columns 4 .. 7, a byte a column
+#pragma unroll 1
+    for (int j = 0; j < nc; ++j) {
+        // A zero the compiler cannot see through, new for every column, in the index of the source records: they are then read
+        // from the kernel's arguments where they are used.  Hoisted out of this loop as invariants, the 14 words of each of up
+        // to 32 records outnumber the scalar registers and spill.
+        int zero = 0;
+        asm volatile("" : "+s"(zero));
+        uint32_t value, count;
+        combine_pixel<CAP, MODE>(a, r, c0 + j, zero, &value, &count);
+        if (j < 4) lo |= (uint64_t)value << (16 * j);
+        else hi |= (uint64_t)value << (16 * (j - 4));
+        counts |= (uint64_t)count << (8 * j);
+    }
+    uint16_t* orow = a.out + (int64_t)r * a.out_pitch + c0;
+    if (nc == kOct && a.vec_out) {
+        uint4 q;
+        q.x = (uint32_t)lo, q.y = (uint32_t)(lo >> 32), q.z = (uint32_t)hi, q.w = (uint32_t)(hi >> 32);
+        *reinterpret_cast<uint4*>(orow) = q;
+    } else {
+        for (int j = 0; j < nc; ++j) orow[j] = (uint16_t)((j < 4 ? lo >> (16 * j) : hi >> (16 * (j - 4))) & 0xFFFFu);
+    }
+    if (a.count) {
+        uint8_t* crow = a.count + (int64_t)r * a.count_pitch + c0;
+        if (nc == kOct && a.vec_count) {
+            uint2 q;
+            q.x = (uint32_t)counts, q.y = (uint32_t)(counts >> 32);
+            *reinterpret_cast<uint2*>(crow) = q;
+        } else {
+            for (int j = 0; j < nc; ++j) crow[j] = (uint8_t)(counts >> (8 * j) & 0xFFu);
+        }
+    }
+}
+
+template <int CAP>
+int launch_combine(int mode, dim3 grid, hipStream_t st, const CombineArgs& a) {
+    const char* what = "k_stack_combine";
+    if (mode == SHG_STACK_MEAN) return shg::launch(k_stack_combine<CAP, SHG_STACK_MEAN>, grid, dim3(kThreads), 0, st, a, what);
+    if (mode == SHG_STACK_MEDIAN) return shg::launch(k_stack_combine<CAP, SHG_STACK_MEDIAN>, grid, dim3(kThreads), 0, st, a, what);
+    return shg::launch(k_stack_combine<CAP, SHG_STACK_SIGMA>, grid, dim3(kThreads), 0, st, a, what);
+}
+
+// [p, p + ((h - 1) pitch + w) item) of an image
+struct Span {
+    uintptr_t lo, hi;
+};
+Span span_of(const void* p, int64_t h, int64_t w, int64_t pitch, size_t item) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+    return {lo, lo + (uintptr_t)((h - 1) * pitch + w) * item};
+}
+bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// ---- SSD ----
+constexpr int kTW = 64, kTH = 16;                 // the tile; a thread owns column threadIdx.x % 64 of rows threadIdx.x / 64 + 4 i
+constexpr int kPerThread = kTW * kTH / kThreads;
+constexpr int kRowStep = kThreads / kTW;
+constexpr int kMaxS = 8;
+constexpr int kLW = kTW + 2 * kMaxS, kLH = kTH + 2 * kMaxS;
+constexpr int kMaxOffsets = (2 * kMaxS + 1) * (2 * kMaxS + 1);
+constexpr int kSsdBlocks = 1024;
+
+struct SsdArgs {
+    const uint16_t* ref;
+    const uint16_t* img;
+    int64_t ref_pitch, img_pitch;
+    int h, w, S, masked;
+    double cx, cy, rad2;
+    unsigned long long* ssd;
+    int tiles_x, tiles;
+};
+
+__global__ __launch_bounds__(kThreads) void k_shift_ssd(const SsdArgs a) {
+    __shared__ uint16_t tile[kLH * kLW];
+    __shared__ unsigned long long acc[kMaxOffsets + 1];
+    const int S = a.S, side = 2 * S + 1, n_off = side * side;
+    for (int i = threadIdx.x; i <= n_off; i += kThreads) acc[i] = 0;
+    const int lx = (int)threadIdx.x % kTW, ly = (int)threadIdx.x / kTW;
+    const bool first_lane = shg::lane_id() == 0;
+    for (int t = blockIdx.x; t < a.tiles; t += gridDim.x) {
+        const int tx0 = (t % a.tiles_x) * kTW, ty0 = (t / a.tiles_x) * kTH;
+        const int c = tx0 + lx;
+        const double dx = (double)c - a.cx, dx2 = dx * dx;
+        uint32_t mine[kPerThread];
+        bool valid[kPerThread];
+        int n_valid = 0;
+#pragma unroll
+        for (int i = 0; i < kPerThread; ++i) {
+            const int r = ty0 + ly + i * kRowStep;
+            bool ok = c >= S && c < a.w - S && r >= S && r < a.h - S;
+            if (ok && a.masked) {
+                const double dy = (double)r - a.cy, d2 = dx2 + dy * dy;
+                ok = !(d2 > a.rad2);
+            }
+            valid[i] = ok;
+            mine[i] = ok ? (uint32_t)a.ref[(int64_t)r * a.ref_pitch + c] : 0u;
+            n_valid += ok ? 1 : 0;
+        }
+        // (a barrier too: the tile of the round before has been read by everyone, and the table is clear before its first use)
+        if (!__syncthreads_or(n_valid)) continue;
+        const int lw = kTW + 2 * S, lh = kTH + 2 * S;
+        for (int i = threadIdx.x; i < lw * lh; i += kThreads) {
+            const int y = i / lw, x = i % lw, gr = ty0 - S + y, gc = tx0 - S + x;
+            // (outside the image: a pixel of the set never reads it)
+            tile[y * kLW + x] = gr >= 0 && gr < a.h && gc >= 0 && gc < a.w ? a.img[(int64_t)gr * a.img_pitch + gc] : (uint16_t)0;
+        }
+        __syncthreads();
+        const uint64_t total = shg::wave_sum((uint64_t)n_valid);
+        if (first_lane && total) atomicAdd(&acc[n_off], (unsigned long long)total);
+        for (int v = 0; v < side; ++v) {
+            for (int u = 0; u < side; ++u) {
+                uint64_t s = 0;
+#pragma unroll
+                for (int i = 0; i < kPerThread; ++i) {
+                    const uint32_t other = tile[(ly + i * kRowStep + v) * kLW + lx + u];
+                    const uint32_t d = mine[i] > other ? mine[i] - other : other - mine[i];
+                    s += valid[i] ? (uint64_t)(d * d) : 0;           // d <= 65535: d * d < 2^32
+                }
+                s = shg::wave_sum(s);
+                if (first_lane && s) atomicAdd(&acc[v * side + u], (unsigned long long)s);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i <= n_off; i += kThreads)
+        if (acc[i]) atomicAdd(a.ssd + i, acc[i]);
+}
+
+}  // namespace
+
+extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
+                                     double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
+                                     int64_t count_pitch, shg_stream_t stream) {
+    const char* fn = "shg_stack_combine_u16";
+    SHG_REQUIRE(host_srcs && host_dims3 && host_xform4 && out, SHG_E_ARG, "%s: null pointer", fn);
+    SHG_REQUIRE(n >= 1 && n <= kMaxSources, SHG_E_ARG, "%s: %d sources (1 to %d)", fn, n, kMaxSources);
+    SHG_REQUIRE(oh >= 1 && oh <= kMaxDim && ow >= 1 && ow <= kMaxDim, SHG_E_UNSUPPORTED, "%s: an output of %lld x %lld (1 to %d either way)",
+                fn, (long long)oh, (long long)ow, kMaxDim);
+    SHG_REQUIRE(out_pitch >= ow, SHG_E_ARG, "%s: output pitch < ow", fn);
+    SHG_REQUIRE(!count || count_pitch >= ow, SHG_E_ARG, "%s: count pitch < ow", fn);
+    SHG_REQUIRE(mode == SHG_STACK_MEAN || mode == SHG_STACK_MEDIAN || mode == SHG_STACK_SIGMA, SHG_E_ARG, "%s: unknown mode %d", fn, mode);
+    SHG_REQUIRE(kappa >= 1.0, SHG_E_ARG, "%s: kappa %g is not a number or < 1", fn, kappa);
+    SHG_REQUIRE(iterations >= 1 && iterations <= 3, SHG_E_ARG, "%s: %d iterations (1 to 3)", fn, iterations);
+    const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
+    const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
+    SHG_REQUIRE(!count || !overlap(out_span, count_span), SHG_E_ARG, "%s: the count plane overlaps the output", fn);
+    CombineArgs a{};
+    for (int j = 0; j < n; ++j) {
+        const int64_t h = host_dims3[3 * j], w = host_dims3[3 * j + 1], pitch = host_dims3[3 * j + 2];
+        const double s = host_xform4[4 * j], tx = host_xform4[4 * j + 1], ty = host_xform4[4 * j + 2], gain = host_xform4[4 * j + 3];
+        SHG_REQUIRE(host_srcs[j], SHG_E_ARG, "%s: source %d is a null pointer", fn, j);
+        SHG_REQUIRE(h >= 1 && h <= kMaxDim && w >= 1 && w <= kMaxDim, SHG_E_UNSUPPORTED, "%s: source %d of %lld x %lld (1 to %d either way)", fn,
+                    j, (long long)h, (long long)w, kMaxDim);
+        SHG_REQUIRE(pitch >= w, SHG_E_ARG, "%s: source %d: pitch < w", fn, j);
+        SHG_REQUIRE(isfinite(s) && s > 0.0, SHG_E_ARG, "%s: source %d: scale %g is not finite and > 0", fn, j, s);
+        SHG_REQUIRE(isfinite(tx) && isfinite(ty), SHG_E_ARG, "%s: source %d: translation (%g, %g) is not finite", fn, j, tx, ty);
+        SHG_REQUIRE(isfinite(gain) && gain >= 0.0, SHG_E_ARG, "%s: source %d: gain %g is negative or not finite", fn, j, gain);
+        const Span src_span = span_of(host_srcs[j], h, w, pitch, sizeof(uint16_t));
+        SHG_REQUIRE(!overlap(out_span, src_span), SHG_E_ARG, "%s: the output overlaps source %d", fn, j);
+        SHG_REQUIRE(!count || !overlap(count_span, src_span), SHG_E_ARG, "%s: the count plane overlaps source %d", fn, j);
+        a.src[j] = SourceRec{host_srcs[j], (int)h, (int)w, pitch, s, tx, ty, gain};
+    }
+    a.out = out, a.count = count, a.oh = (int)oh, a.ow = (int)ow, a.out_pitch = out_pitch, a.count_pitch = count ? count_pitch : 0;
+    a.n = n, a.iterations = iterations, a.kappa = kappa;
+    a.vec_out = reinterpret_cast<uintptr_t>(out) % 16 == 0 && (out_pitch * (int64_t)sizeof(uint16_t)) % 16 == 0;
+    a.vec_count = count && reinterpret_cast<uintptr_t>(count) % 8 == 0 && count_pitch % 8 == 0;
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("stack_combine", st);
+    const dim3 grid((unsigned)((ow + kLanesX * kOct - 1) / (kLanesX * kOct)), (unsigned)((oh + kRows - 1) / kRows));
+    if (n <= 4) return launch_combine<4>(mode, grid, st, a);
+    if (n <= 8) return launch_combine<8>(mode, grid, st, a);
+    if (n <= 16) return launch_combine<16>(mode, grid, st, a);
+    return launch_combine<32>(mode, grid, st, a);
+}
+
+extern "C" int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w, int S,
+                                 const double* circle3, uint64_t* ssd, shg_stream_t stream) {
+    const char* fn = "shg_shift_ssd_u16";
+    SHG_REQUIRE(ref && img && ssd, SHG_E_ARG, "%s: null pointer", fn);
+    SHG_REQUIRE(h >= 1 && h <= kMaxDim && w >= 1 && w <= kMaxDim, SHG_E_UNSUPPORTED, "%s: images of %lld x %lld (1 to %d either way)", fn,
+                (long long)h, (long long)w, kMaxDim);
+    SHG_REQUIRE(ref_pitch >= w && img_pitch >= w, SHG_E_ARG, "%s: pitch < w", fn);
+    SHG_REQUIRE(S >= 0 && S <= kMaxS, SHG_E_ARG, "%s: a search of %d pixels (0 to %d)", fn, S, kMaxS);
+    SsdArgs a{};
+    a.masked = circle3 && !(circle3[0] == -1.0 && circle3[1] == -1.0 && circle3[2] == -1.0);
+    if (a.masked) {
+        SHG_REQUIRE(isfinite(circle3[0]) && isfinite(circle3[1]) && isfinite(circle3[2]), SHG_E_ARG, "%s: the circle (%g, %g, %g) is not finite",
+                    fn, circle3[0], circle3[1], circle3[2]);
+        a.cx = circle3[0], a.cy = circle3[1], a.rad2 = circle3[2] * circle3[2];
+    }
+    a.ref = ref, a.img = img, a.ref_pitch = ref_pitch, a.img_pitch = img_pitch, a.h = (int)h, a.w = (int)w, a.S = S;
+    a.ssd = reinterpret_cast<unsigned long long*>(ssd);
+    a.tiles_x = (int)((w + kTW - 1) / kTW);
+    a.tiles = a.tiles_x * (int)((h + kTH - 1) / kTH);
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("shift_ssd", st);
+    const size_t words = (size_t)(2 * S + 1) * (2 * S + 1) + 1;
+    if (hipError_t e = hipMemsetAsync(ssd, 0, words * sizeof(uint64_t), st)) {
+        shg::set_error("%s: %s", fn, hipGetErrorString(e));
+        return (int)e;
+    }
+    if (w < 2 * S + 1 || h < 2 * S + 1) return 0;                        // the set is empty: the zeros are the result
+    return shg::launch(k_shift_ssd, dim3((unsigned)(a.tiles < kSsdBlocks ? a.tiles : kSsdBlocks)), dim3(kThreads), 0, st, a, "k_shift_ssd");
+}

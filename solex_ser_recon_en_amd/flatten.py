@@ -90,12 +90,12 @@ def flatten_disk(image, circle, smooth=1, level=None, max_gain=8.0):
     return ops.ring_flatten_u16(t, circle, gain), profile, gain
 
 
-def flatten_scan(file_or_reader, options=None, shift=0, smooth=1, level=None, max_gain=8.0):
-    """A scan's disk at `shift`, flattened: the image _uncontrasted.png shows for that shift before img_rotate -- through the
-    package's own stages as Solex_recon.solex_process composes them: line fit, the disks of the ellipse-fit shift and of `shift`,
-    the limb fit, the ellipse -> circle warp, transversalium, crop -- and its circle, then flatten_disk.  -> {'image', 'flat' (uint16
-    device tensors), 'circle' (of the image), 'profile', 'gain', 'level', 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe /
-    slant_fix (no limb fit, hence no circle), de-vignette (a float64 frame) and a frame-sharded reader."""
+def scan_disk_and_circle(file_or_reader, options=None, shift=0, what=('flattening', 'flattening needs', 'flattening takes')):
+    """A scan's disk at `shift`: the image _uncontrasted.png shows for that shift before img_rotate -- through the package's own
+    stages as Solex_recon.solex_process composes them: line fit, the disks of the ellipse-fit shift and of `shift`, the limb fit,
+    the ellipse -> circle warp, transversalium, crop -- and its circle.  -> {'image' (a uint16 device tensor), 'circle' (of the
+    image), 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe / slant_fix (no limb fit, hence no circle), de-vignette (a
+    float64 frame) and a frame-sharded reader; `what` words the messages for the caller (flatten_scan, stack.scan_disk)."""
     from . import SHG_MAIN, dist
     from .device import DeviceImage, to_device_u16
     from .ellipse_to_circle import correct_image, ellipse_to_circle
@@ -105,13 +105,13 @@ def flatten_scan(file_or_reader, options=None, shift=0, smooth=1, level=None, ma
     from .video_reader import video_reader
     opts = SHG_MAIN.default_options() if options is None else dict(options)
     if opts['ratio_fixe'] is not None or opts['slant_fix'] is not None:
-        raise ValueError('flattening needs the limb fit\'s circle: ratio_fixe / slant_fix give none')
+        raise ValueError('%s the limb fit\'s circle: ratio_fixe / slant_fix give none' % what[1])
     if opts['de-vignette']:
-        raise ValueError('flattening takes the 16-bit disk: de-vignette leaves a float64 one')
+        raise ValueError('%s the 16-bit disk: de-vignette leaves a float64 one' % what[2])
     opts.update(save_fit=False, flag_display=False, _nolog=True, basefich0='')
     rdr = file_or_reader if hasattr(file_or_reader, 'device_stack') else video_reader(file_or_reader)
     if dist.is_sharded(rdr):
-        raise ValueError('flattening is single-process: give it the whole scan, not a frame shard')
+        raise ValueError('%s is single-process: give it the whole scan, not a frame shard' % what[0])
     shift = int(shift)
     ih, iw = int(rdr.ih), int(rdr.iw)
     with contextlib.redirect_stdout(io.StringIO()):               # the stages report on stdout
@@ -129,12 +129,20 @@ def flatten_scan(file_or_reader, options=None, shift=0, smooth=1, level=None, ma
         h, w = to_device_u16(frame).shape
         crop, _ = crop_plan(h, w, circle, opts)
         (frame,), circle_out = crop_to_width([frame], circle, opts)
-    image = to_device_u16(frame)
-    circle_out = tuple(float(v) for v in circle_out)
+    return {'image': to_device_u16(frame), 'circle': tuple(float(v) for v in circle_out), 'shift': shift, 'ratio': float(ratio),
+            'phi': float(phi), 'crop': crop}
+
+
+def flatten_scan(file_or_reader, options=None, shift=0, smooth=1, level=None, max_gain=8.0):
+    """A scan's disk at `shift` (scan_disk_and_circle), flattened by flatten_disk.  -> {'image', 'flat' (uint16 device tensors),
+    'circle' (of the image), 'profile', 'gain', 'level', 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe / slant_fix (no
+    limb fit, hence no circle), de-vignette (a float64 frame) and a frame-sharded reader."""
+    disk = scan_disk_and_circle(file_or_reader, options, shift)
+    image, circle_out = disk['image'], disk['circle']
     flat, profile, gain = flatten_disk(image, circle_out, smooth, level, max_gain)
     used = float(level) if level is not None else float(default_level(filled_profile(profile, smooth)))
-    return {'image': image, 'flat': flat, 'circle': circle_out, 'profile': profile, 'gain': gain, 'level': used, 'shift': shift,
-            'ratio': float(ratio), 'phi': float(phi), 'crop': crop, 'smooth': int(smooth), 'max_gain': float(max_gain)}
+    return {'image': image, 'flat': flat, 'circle': circle_out, 'profile': profile, 'gain': gain, 'level': used, 'shift': disk['shift'],
+            'ratio': disk['ratio'], 'phi': disk['phi'], 'crop': disk['crop'], 'smooth': int(smooth), 'max_gain': float(max_gain)}
 
 
 # ---- command line ---------------------------------------------------------------------------------

@@ -1022,3 +1022,66 @@ def ring_flatten_u16(img, circle, gain, out=None):
     _lib.check(lib.shg_ring_flatten_u16(ptr, h, w, pitch, _host_ptr(c3), _host_ptr(g), k, optr, opitch, _stream()),
                'shg_ring_flatten_u16')
     return out
+
+
+# ---- stacking a series of scans: resample-and-combine, and the SSD over a window of integer offsets ----
+STACK_MODES = {'mean': 0, 'median': 1, 'sigma': 2}
+
+
+def stack_combine_u16(images, transforms, shape, mode='sigma', kappa=2.5, iterations=2, out=None, count=None, want_count=True):
+    """shg_stack_combine_u16: the N uint16 images (2-D views, any sizes) resampled into one grid of `shape` = (oh, ow) by their
+    transforms -- N rows (s, tx, ty, gain): the output pixel (r, c) reads source j at (tx + s c, ty + s r), bilinear, times gain --
+    and combined pixel by pixel in one launch; mode 'mean', 'median' or 'sigma' (the kappa-sigma clipped mean, `iterations` passes)
+    -> (out uint16 [oh, ow], count uint8 [oh, ow] or None): the samples that went into each pixel.  out, count: the caller's
+    views."""
+    if mode not in STACK_MODES:
+        raise ValueError('mode is one of %s, got %r' % (', '.join(STACK_MODES), mode))
+    images = list(images)
+    n = len(images)
+    xf = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4))
+    if n < 1 or xf.shape[0] != n:
+        raise ValueError('%d images and %d transforms (s, tx, ty, gain)' % (n, xf.shape[0]))
+    geo = [_img(t, 'image', torch.uint16) for t in images]
+    dev = images[0].device
+    oh, ow = int(shape[0]), int(shape[1])
+    if out is None:
+        out = torch.empty((oh, ow), dtype=torch.uint16, device=dev)
+    optr, h, w, opitch = _img(out, 'out', torch.uint16)
+    if (h, w) != (oh, ow):
+        raise ValueError('out must be a uint16 [%d, %d] view' % (oh, ow))
+    cptr, cpitch = None, 0
+    if count is None and want_count:
+        count = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+    if count is not None:
+        cptr, h, w, cpitch = _img(count, 'count', torch.uint8)
+        if (h, w) != (oh, ow):
+            raise ValueError('count must be a uint8 [%d, %d] view' % (oh, ow))
+    ptrs = (ctypes.c_void_p * n)(*[g[0] for g in geo])
+    dims = np.ascontiguousarray([[g[1], g[2], g[3]] for g in geo], dtype=np.int64)
+    _lib.check(lib.shg_stack_combine_u16(ptrs, _host_ptr(dims), _host_ptr(xf), n, STACK_MODES[mode], float(kappa), int(iterations), optr,
+                                         oh, ow, opitch, cptr, cpitch, _stream()), 'shg_stack_combine_u16')
+    return out, count
+
+
+def shift_ssd_u16(ref, img, search, circle=None, out=None):
+    """shg_shift_ssd_u16: the sums of squared differences between two uint16 images of one shape, for every integer offset (u, v)
+    with |u|, |v| <= search (0 to 8): out[(v + S) (2 S + 1) + (u + S)] = sum (ref[r, c] - img[r + v, c + u])^2 over the pixels at
+    least S from every edge and, with `circle` (cx, cy, r; None or (-1, -1, -1): none), on that disk; out[(2 S + 1)^2] = how many
+    -> int64 [(2 S + 1)^2 + 1] on the images' device (the sums stay below 2^60).  out: the caller's, overwritten."""
+    rptr, h, w, rpitch = _img(ref, 'ref', torch.uint16)
+    iptr, ih, iw, ipitch = _img(img, 'img', torch.uint16)
+    if (ih, iw) != (h, w):
+        raise ValueError('ref [%d, %d] and img [%d, %d] must have one shape' % (h, w, ih, iw))
+    s = int(search)
+    if not 0 <= s <= 8:
+        raise ValueError('search must be 0 to 8, got %r' % (search,))
+    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    if c3 is not None and c3.size != 3:
+        raise ValueError('circle is (cx, cy, r)')
+    words = (2 * s + 1) ** 2 + 1
+    if out is None:
+        out = torch.empty(words, dtype=torch.int64, device=ref.device)
+    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (words,) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int64 [%d] tensor' % words)
+    _lib.check(lib.shg_shift_ssd_u16(rptr, rpitch, iptr, ipitch, h, w, s, _host_ptr(c3), out.data_ptr(), _stream()), 'shg_shift_ssd_u16')
+    return out
