@@ -194,12 +194,6 @@ static inline double polyval_desc(const double* p, double x) {
     return y;
 }
 
-// NumPy's _lerp for np.percentile's linear method
-static inline double np_lerp(double a, double b, double gamma) {
-    const double diff = b - a;
-    return gamma >= 0.5 ? b - diff * (1 - gamma) : a + diff * gamma;
-}
-
 }  // namespace host
 }  // namespace shg
 
@@ -621,7 +615,7 @@ extern "C" int shg_host_percentile_plan(int64_t n, double q, int64_t* rank_lo, i
     return 0;
 }
 
-extern "C" double shg_host_lerp(double a, double b, double gamma) { return np_lerp(a, b, gamma); }
+extern "C" double shg_host_lerp(double a, double b, double gamma) { return shg::np_lerp(a, b, gamma); }
 
 // ---- a8 / a6 / a7: the limb geometry with NumPy's own BLAS / LAPACK calls --------------------------------
 // LsqEllipse().fit (Halir & Flusser), two_step, get_correction_matrix and correct_image's geometry

@@ -13,11 +13,13 @@
 #include <math.h>
 #include <stdlib.h>
 #include "shg_common.h"
+#include "limb_math.h"
 
 namespace {
 
-constexpr int MAXR = 16;                     // Gaussian radius: int(4 * sigma + 0.5), sigma <= 4
-struct GaussW { double w[2 * MAXR + 1]; int radius; };
+using namespace shg::limb;
+using shg::f64_key;
+using shg::key_f64;
 
 // cv2.blur(float64): horizontal sums (left to right), then vertical sums (top to bottom), times 1/(k*k)
 __global__ __launch_bounds__(256) void k_boxf_rows(const double* __restrict__ src, int h, int w, int k, double* __restrict__ tmp) {
@@ -48,20 +50,16 @@ __global__ __launch_bounds__(256) void k_gauss_v2(const double* __restrict__ blu
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= h * w) return;
     const int y = i / w, x = i - y * w;
-    auto px = [&](int yy) -> double {          // img_blurred[< thresh3] = 0; [>= thresh3] = 65000 (:226-227)
+    auto px = [&](int j) -> double {           // the flood image; outside it: 0 (gaussian_filter mode='constant')
+        const int yy = y + j;
         if (yy < 0 || yy >= h) return 0.0;
-        return blurred[(int64_t)yy * w + x] < flood_thresh ? 0.0 : 65000.0;
+        return flood_value(flood_below(blurred[(int64_t)yy * w + x], flood_thresh));
     };
-    auto one = [&](int yy) -> double { return (yy < 0 || yy >= h) ? 0.0 : 1.0; };
-    const int R = g.radius;
-    double t = px(y) * g.w[R];
-    double u = one(y) * g.w[R];
-    for (int j = -R; j < 0; ++j) {
-        t += (px(y + j) + px(y - j)) * g.w[R + j];
-        u += (one(y + j) + one(y - j)) * g.w[R + j];
-    }
-    img_v[i] = t;
-    one_v[i] = u;
+    auto one = [&](int j) -> double { return (y + j < 0 || y + j >= h) ? 0.0 : 1.0; };
+    double t[2];
+    correlate1d_sym(g, t, px, one);
+    img_v[i] = t[0];
+    one_v[i] = t[1];
 }
 
 // Gaussian along axis 1 of both planes, then smoothed = image / (bleed_over + eps)
@@ -73,41 +71,9 @@ __global__ __launch_bounds__(256) void k_gauss_h2_div(const double* __restrict__
     const double* a = img_v + (int64_t)y * w;
     const double* b = one_v + (int64_t)y * w;
     auto at = [&](const double* p, int xx) -> double { return (xx < 0 || xx >= w) ? 0.0 : p[xx]; };
-    const int R = g.radius;
-    double t = a[x] * g.w[R];
-    double u = b[x] * g.w[R];
-    for (int j = -R; j < 0; ++j) {
-        t += (at(a, x + j) + at(a, x - j)) * g.w[R + j];
-        u += (at(b, x + j) + at(b, x - j)) * g.w[R + j];
-    }
-    smoothed[i] = t / (u + 2.220446049250313e-16);
-}
-
-// glibc 2.35 hypot (sysdeps/ieee754/dbl-64/e_hypot.c, the non-FMA kernel), for finite normal-range inputs:
-// this is what np.hypot evaluates on the reference's x86-64 hosts.
-__device__ __forceinline__ double hypot_glibc(double x, double y) {
-    x = fabs(x);
-    y = fabs(y);
-    const double ax = x < y ? y : x;
-    const double ay = x < y ? x : y;
-    if (ax >= ay / 0x1p-54) return ax + ay;
-    double h = sqrt(ax * ax + ay * ay);
-    double t1, t2;
-    if (h <= 2.0 * ay) {
-        const double delta = h - ay;
-        t1 = ax * (2.0 * delta - ax);
-        t2 = (delta - 2.0 * (ax - ay)) * delta;
-    } else {
-        const double delta = h - ax;
-        t1 = 2.0 * delta * (ax - 2.0 * ay);
-        t2 = (4.0 * delta - ay) * ay + delta * delta;
-    }
-    h -= (t1 + t2) / (2.0 * h);
-    return h;
-}
-
-__device__ __forceinline__ int refl(int i, int n) {       // scipy mode 'reflect': d c b a | a b c d | d c b a
-    return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i);
+    double t[2];
+    correlate1d_sym(g, t, [&](int j) { return at(a, x + j); }, [&](int j) { return at(b, x + j); });
+    smoothed[i] = bleed_over_div(t[0], t[1]);
 }
 
 // ndi.sobel(axis=0) and (axis=1): derivative [-1,0,1] along the axis, then [1,2,1] along the other
@@ -116,16 +82,8 @@ __global__ __launch_bounds__(256) void k_sobel_mag(const double* __restrict__ s,
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= h * w) return;
     const int y = i / w, x = i - y * w;
-    const int ym = refl(y - 1, h), yp = refl(y + 1, h), xm = refl(x - 1, w), xp = refl(x + 1, w);
-    auto S = [&](int yy, int xx) -> double { return s[(int64_t)yy * w + xx]; };
-    // correlate1d([-1,0,1]): t = x[0]*0 + (x[-1] - x[+1]) * (-1)
-    auto dy = [&](int xx) -> double { double t = S(y, xx) * 0.0; t += (S(ym, xx) - S(yp, xx)) * -1.0; return t; };
-    auto dx = [&](int yy) -> double { double t = S(yy, x) * 0.0; t += (S(yy, xm) - S(yy, xp)) * -1.0; return t; };
-    // correlate1d([1,2,1]): t = x[0]*2 + (x[-1] + x[+1]) * 1
-    double iv = dy(x) * 2.0;
-    iv += (dy(xm) + dy(xp)) * 1.0;
-    double jv = dx(y) * 2.0;
-    jv += (dx(ym) + dx(yp)) * 1.0;
+    double iv, jv;
+    sobel_pair([&](int yy, int xx) -> double { return s[(int64_t)yy * w + xx]; }, y, x, h, w, iv, jv);
     isob[i] = iv;
     jsob[i] = jv;
     mag[i] = hypot_glibc(iv, jv);
@@ -138,42 +96,34 @@ __global__ __launch_bounds__(256) void k_nms(const double* __restrict__ isob, co
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= h * w) return;
     const int y = i / w, x = i - y * w;
-    bool local = false;
-    const double m = mag[i];
-    // eroded all-ones mask (border_value 0) & magnitude > 0
-    if (y > 0 && y < h - 1 && x > 0 && x < w - 1 && m > 0.0) {
-        const double is = isob[i], js = jsob[i];
-        const double ai = fabs(is), aj = fabs(js);
-        auto M = [&](int dy, int dx) -> double { return mag[(int64_t)(y + dy) * w + (x + dx)]; };
-        const bool same = (is >= 0 && js >= 0) || (is <= 0 && js <= 0);
-        const bool opp = (is <= 0 && js >= 0) || (is >= 0 && js <= 0);
-        auto test = [&](double wgt, double p1, double p2, double m1, double m2) -> bool {
-            const bool c_plus = p2 * wgt + p1 * (1 - wgt) <= m;
-            const bool c_minus = m2 * wgt + m1 * (1 - wgt) <= m;
-            return c_plus && c_minus;
-        };
-        // later sectors overwrite earlier ones, as the sequential assignments in skimage do
-        if (same && ai >= aj) local = test(aj / ai, M(1, 0), M(1, 1), M(-1, 0), M(-1, -1));
-        if (same && ai <= aj) local = test(ai / aj, M(0, 1), M(1, 1), M(0, -1), M(-1, -1));
-        if (opp && ai <= aj) local = test(ai / aj, M(0, 1), M(-1, 1), M(0, -1), M(1, -1));
-        if (opp && ai >= aj) local = test(aj / ai, M(-1, 0), M(-1, 1), M(1, 0), M(1, -1));
-    }
-    low_mask[i] = (local && m >= low) ? 1 : 0;
-    high_mask[i] = (local && m >= high) ? 1 : 0;
+    const unsigned bits = nms_bits(y, x, h, w, mag[i],
+                                   [&](double& is, double& js) { is = isob[i]; js = jsob[i]; },
+                                   [&](int dy, int dx) -> double { return mag[(int64_t)(y + dy) * w + (x + dx)]; }, low, high);
+    low_mask[i] = bits & 1;
+    high_mask[i] = bits >> 1;
 }
 
 // ---- exact order statistics of a float64 array: MSB-first radix select, 8 bits per launch -------------
 // np.median / np.percentile (ellipse_to_circle.py:165, 241) need the k-th smallest values exactly.
-__device__ __forceinline__ uint64_t f64_key(double v) {          // monotone map double -> uint64
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_f64(uint64_t k) {
-    const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-
+// (on shg::f64_key's order-preserving keys)
 struct SelectState { uint64_t prefix; int64_t rank; };
+
+// Inclusive scan of one value per thread over the 256-thread workgroup: a __shfl_up ladder inside each wave, the waves'
+// totals through wave_tot[4].  Holds a barrier; the caller puts another one before wave_tot is used again.
+template <typename T>
+__device__ __forceinline__ T scan_256(T v, T* wave_tot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(incl, d);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    for (int i = 0; i < wave; ++i) incl += wave_tot[i];
+    return incl;
+}
 
 // Replay the digit choices of passes 0 .. pass-1 from their global histograms, with the whole
 // 256-thread workgroup: one bin per thread, a workgroup-wide inclusive scan, the bin whose
@@ -182,18 +132,10 @@ __device__ __forceinline__ SelectState select_replay(const uint32_t* __restrict_
     __shared__ int64_t wave_tot[4];
     __shared__ int64_t chosen[2];          // digit, count below it
     SelectState st{0, rank};
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     for (int p = 0; p < pass; ++p) {
         const int64_t c = hist[p * 256 + tid];
-        int64_t incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        for (int i = 0; i < wave; ++i) incl += wave_tot[i];
+        const int64_t incl = scan_256(c, wave_tot);
         const int64_t excl = incl - c;
         if (excl <= st.rank && st.rank < incl) { chosen[0] = tid; chosen[1] = excl; }
         __syncthreads();
@@ -245,7 +187,7 @@ __global__ __launch_bounds__(256) void k_boxf_cols_key(const double* __restrict_
     double s = 0.0;
     for (int j = 0; j < k; ++j) s += tmp[(int64_t)shg::reflect101(ya + j, h) * w + x];
     dst[i] = s * scale;
-    keys[i] = (uint32_t)(s * 1048576.0);                  // exact: s is a whole number of 2^-20 units
+    keys[i] = (uint32_t)(s * kPerUnit);                   // exact: s is a whole number of 2^-20 units
 }
 
 constexpr int SEL32_BITS = 11, SEL32_BINS = 1 << SEL32_BITS, SEL32_PASSES = 3;      // 33 bits >= 32
@@ -256,20 +198,12 @@ struct Pairs8 { const uint32_t* keys[8]; int64_t rank[8]; double scale[8]; };
 __device__ __forceinline__ void pick_bin(const uint32_t* __restrict__ hist, int64_t rank, int& digit, int64_t& below) {
     __shared__ int64_t wave_tot[4];
     __shared__ int64_t chosen[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     constexpr int PER = SEL32_BINS / 256;
     int64_t c[PER], local = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) { c[j] = hist[tid * PER + j]; local += c[j]; }
-    int64_t incl = local;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    for (int i = 0; i < wave; ++i) incl += wave_tot[i];
+    const int64_t incl = scan_256(local, wave_tot);
     int64_t excl = incl - local;
     if (excl <= rank && rank < incl) {
 #pragma unroll
@@ -322,42 +256,36 @@ __global__ __launch_bounds__(256) void k_select32_final(Pairs8 p, const uint32_t
         rank -= below;
         key = (key << SEL32_BITS) | (uint64_t)digit;
     }
-    if (threadIdx.x == 0) out[blockIdx.x] = ((double)key * 9.5367431640625e-07) * p.scale[blockIdx.x];
+    if (threadIdx.x == 0) out[blockIdx.x] = ((double)key * kUnit) * p.scale[blockIdx.x];
 }
 
 // ---- get_flood_image's statistics (ellipse_to_circle.py:159-169) ----------------------------------------
 // stats[0] = sum(image) (every value is k / 2^20 and the total < 2^18: exact in any order),
 // then over data = blurred[blurred < very_bright]: stats[1] = min, stats[2] = max, counts[20] = np.histogram(data, 20)
-// accumulators, the 20 counters, and very_bright: either the caller's value or NumPy's _lerp of two order statistics
-// that are still on the device (np.percentile(img_blurred, 99), ellipse_to_circle.py:165) -- no host round trip
-// Workgroups add their partial results to one of FLOOD_SLOTS slots (blockIdx % FLOOD_SLOTS), the reader folds the slots:
-// 128 workgroups on the same three addresses queue up in the memory-side atomic units for most of the kernel's 9 us.
-constexpr int FLOOD_SLOTS = 9;                            // 4 + 3 * 9 = 31 u64 of the 256-byte workspace
-
+// accumulators (limb_math.h: 31 u64 of the 256-byte workspace), the 20 counters, and very_bright: either the caller's value or
+// NumPy's _lerp of two order statistics that are still on the device (np.percentile(img_blurred, 99), ellipse_to_circle.py:165)
+// -- no host round trip
 __global__ void k_flood_init(unsigned long long* __restrict__ acc, uint32_t* __restrict__ counts, const double* __restrict__ order_stats,
                              double gamma, double very_bright) {
     if (threadIdx.x < 20) counts[threadIdx.x] = 0;
     if (threadIdx.x < FLOOD_SLOTS) {                      // per-slot sum, min key, max key (k_flood_minmax)
-        acc[4 + 3 * threadIdx.x] = 0ull;
-        acc[5 + 3 * threadIdx.x] = ~0ull;
-        acc[6 + 3 * threadIdx.x] = 0ull;
+        acc[acc_sum(threadIdx.x)] = 0ull;
+        acc[acc_min(threadIdx.x)] = ~0ull;
+        acc[acc_max(threadIdx.x)] = 0ull;
     }
     if (threadIdx.x == 0) {
         acc[0] = 0ull;
         acc[1] = ~0ull;
         acc[2] = 0ull;
-        if (order_stats) {
-            const double a = order_stats[0], b = order_stats[1], diff = b - a;
-            very_bright = gamma >= 0.5 ? b - diff * (1.0 - gamma) : a + diff * gamma;
-        }
-        acc[3] = (unsigned long long)__double_as_longlong(very_bright);
+        if (order_stats) very_bright = shg::np_lerp(order_stats[0], order_stats[1], gamma);
+        acc[ACC_VERY_BRIGHT] = (unsigned long long)__double_as_longlong(very_bright);
     }
 }
 
 __global__ __launch_bounds__(256) void k_flood_minmax(const double* __restrict__ image, const double* __restrict__ blurred, int64_t n,
                                                       unsigned long long* __restrict__ acc) {
-    // acc[0] = sum as fixed point (units of 2^-20), acc[1] = min key, acc[2] = max key, acc[3] = very_bright (double bits, k_flood_init)
-    const double very_bright = __longlong_as_double((long long)acc[3]);
+    // per slot: sum as fixed point (units of 2^-20), min key, max key; very_bright: double bits (k_flood_init)
+    const double very_bright = __longlong_as_double((long long)acc[ACC_VERY_BRIGHT]);
     unsigned long long s = 0, lo = ~0ull, hi = 0ull;
     const int64_t stride = (int64_t)gridDim.x * 256;
     // four elements per trip, all eight loads issued before the first use (clamped index instead of a predicate)
@@ -374,7 +302,7 @@ __global__ __launch_bounds__(256) void k_flood_minmax(const double* __restrict__
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (!ok[u]) continue;
-            s += (unsigned long long)(im[u] * 1048576.0);
+            s += (unsigned long long)(im[u] * kPerUnit);
             if (bl[u] < very_bright) {
                 const uint64_t k = f64_key(bl[u]);
                 lo = k < lo ? k : lo;
@@ -395,46 +323,33 @@ __global__ __launch_bounds__(256) void k_flood_minmax(const double* __restrict__
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int i = 1; i < 4; ++i) { s += ws[i]; lo = wlo[i] < lo ? wlo[i] : lo; hi = whi[i] > hi ? whi[i] : hi; }
-        unsigned long long* slot = acc + 4 + 3 * (blockIdx.x % FLOOD_SLOTS);
-        atomicAdd(&slot[0], s);
-        atomicMin(&slot[1], lo);
-        atomicMax(&slot[2], hi);
+        const int slot = blockIdx.x % FLOOD_SLOTS;
+        atomicAdd(&acc[acc_sum(slot)], s);
+        atomicMin(&acc[acc_min(slot)], lo);
+        atomicMax(&acc[acc_max(slot)], hi);
     }
 }
 
 __global__ __launch_bounds__(256) void k_flood_hist(const double* __restrict__ blurred, int64_t n,
                                                     const unsigned long long* __restrict__ acc, double* __restrict__ stats,
                                                     uint32_t* __restrict__ counts) {
-    const double very_bright = __longlong_as_double((long long)acc[3]);
-    __shared__ double edges[21];
-    __shared__ uint32_t lc[20];
-    unsigned long long total = 0, klo = ~0ull, khi = 0ull;
-    for (int k = 0; k < FLOOD_SLOTS; ++k) {
-        total += acc[4 + 3 * k];
-        klo = acc[5 + 3 * k] < klo ? acc[5 + 3 * k] : klo;
-        khi = acc[6 + 3 * k] > khi ? acc[6 + 3 * k] : khi;
-    }
-    const double mn = key_f64(klo), mx = key_f64(khi);
-    if (threadIdx.x < 21) {
-        // np.histogram: first == last -> (first - 0.5, last + 0.5); bin_edges = np.linspace(first, last, 21)
-        double first = mn, last = mx;
-        if (first == last) { first = first - 0.5; last = last + 0.5; }
-        const double step = (last - first) / 20.0;
-        edges[threadIdx.x] = threadIdx.x == 20 ? last : (double)threadIdx.x * step + first;
-    }
-    if (threadIdx.x < 20) lc[threadIdx.x] = 0;
+    const double very_bright = __longlong_as_double((long long)acc[ACC_VERY_BRIGHT]);
+    __shared__ double edges[HIST_BINS + 1];
+    __shared__ uint32_t lc[HIST_BINS];
+    const FloodFold f = flood_fold(acc);
+    const double mn = key_f64(f.klo), mx = key_f64(f.khi);
+    if (threadIdx.x < HIST_BINS + 1) edges[threadIdx.x] = hist_edge(mn, mx, threadIdx.x);
+    if (threadIdx.x < HIST_BINS) lc[threadIdx.x] = 0;
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double b = blurred[i];
         if (!(b < very_bright)) continue;
-        int bin = 0;                                  // largest bin with edges[bin] <= b; the last bin is closed
-        for (int j = 1; j < 20; ++j) bin = (b >= edges[j]) ? j : bin;
-        atomicAdd(&lc[bin], 1u);
+        atomicAdd(&lc[hist_bin([&](int j) { return edges[j]; }, b)], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < 20 && lc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], lc[threadIdx.x]);
+    if (threadIdx.x < HIST_BINS && lc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], lc[threadIdx.x]);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        stats[0] = (double)total / 1048576.0;
+        stats[0] = (double)f.total / kPerUnit;
         stats[1] = mn;
         stats[2] = mx;
     }
@@ -445,28 +360,6 @@ __global__ __launch_bounds__(256) void k_flood_hist(const double* __restrict__ b
 // neighbours; roots are the smallest linear index of a component, so sorting roots = scipy.ndimage.label's
 // raster numbering).  Components holding a high_mask pixel survive (skimage's hysteresis); their pixels
 // are emitted in raster order with their root.
-__device__ __forceinline__ int ccl_find(const int* L, int x) {
-    // agent-scope relaxed loads: parents are rewritten by other workgroups (other XCDs) during the merge,
-    // and a CU's L1 / an XCD's L2 is not refreshed by them.  A stale parent would still be a valid older
-    // ancestor (parents only ever decrease, and every link is validated by the atomicMin), but fresh reads
-    // keep the chains short.
-    int p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) { x = p; p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return x;
-}
-
-__device__ __forceinline__ void ccl_union(int* L, int a, int b) {
-    while (true) {
-        a = ccl_find(L, a);
-        b = ccl_find(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }      // link the larger root under the smaller
-        const int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t* __restrict__ low, int n, int* __restrict__ L, int* __restrict__ flag) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -478,12 +371,12 @@ __global__ __launch_bounds__(256) void k_ccl_merge(const uint8_t* __restrict__ l
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= h * w || !low[i]) return;
     const int y = i / w, x = i - y * w;
-    if (x > 0 && low[i - 1]) ccl_union(L, i, i - 1);
+    if (x > 0 && low[i - 1]) uf_union<AgentLoad>(L, i, i - 1);
     if (y > 0) {
         const int up = i - w;
-        if (x > 0 && low[up - 1]) ccl_union(L, i, up - 1);
-        if (low[up]) ccl_union(L, i, up);
-        if (x < w - 1 && low[up + 1]) ccl_union(L, i, up + 1);
+        if (x > 0 && low[up - 1]) uf_union<AgentLoad>(L, i, up - 1);
+        if (low[up]) uf_union<AgentLoad>(L, i, up);
+        if (x < w - 1 && low[up + 1]) uf_union<AgentLoad>(L, i, up + 1);
     }
 }
 
@@ -491,7 +384,7 @@ __global__ __launch_bounds__(256) void k_ccl_flatten(const uint8_t* __restrict__
                                                      int* __restrict__ L, int* __restrict__ flag) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n || !low[i]) return;
-    const int r = ccl_find(L, i);
+    const int r = uf_find<AgentLoad>(L, i);
     L[i] = r;            // benign race: every writer stores a value on the path to the same root
     if (high[i]) flag[r] = 1;
 }
@@ -512,7 +405,7 @@ __global__ __launch_bounds__(256) void k_ccl_emit(const int* __restrict__ L, con
         if (x < w) {
             const int l = L[y * w + x];
             if (l >= 0) {
-                const int r = L[l] == l ? l : ccl_find(L, l);
+                const int r = L[l] == l ? l : uf_find<AgentLoad>(L, l);
                 if (flag[r]) root = r;
             }
         }
@@ -538,23 +431,13 @@ __global__ __launch_bounds__(256) void k_ccl_scan(const int* __restrict__ counts
                                                   int* __restrict__ out_count) {
     __shared__ int wave_tot[4];
     __shared__ int carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
     for (int y0 = 0; y0 < h; y0 += 256) {
         const int y = y0 + threadIdx.x;
         const int c = y < h ? counts[y] : 0;
-        int incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        int off = carry;
-        for (int i = 0; i < wave; ++i) off += wave_tot[i];
-        if (y < h) offsets[y] = off + incl - c;
+        const int incl = scan_256(c, wave_tot);
+        if (y < h) offsets[y] = carry + incl - c;
         __syncthreads();
         if (threadIdx.x == 0) carry += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
         __syncthreads();

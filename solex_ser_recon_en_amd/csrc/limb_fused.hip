@@ -22,8 +22,13 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "shg_common.h"
+#include "limb_math.h"
 
 namespace {
+
+using namespace shg::limb;
+using shg::f64_key;
+using shg::key_f64;
 
 // "Everything this workgroup has added to the shared histograms has been performed": what a workgroup says before it counts
 // itself done.  Its results are device-scope atomics (performed at the memory side, read back by the last workgroup with
@@ -58,20 +63,7 @@ inline int limb_fence() {                                    // (read at every c
 
 
 constexpr int TH = 16, TW = 64;              // output tile of both tiled kernels (1024 threads, a pixel each)
-constexpr int MAXR = 16;
-struct GaussW { double w[2 * MAXR + 1]; int radius; };
-constexpr int FLOOD_SLOTS = 9;
 constexpr int KMAX = 16;                     // largest cv2.blur window the fused path takes (int(0.01 * rows / 4): scans up to 6799 slit rows)
-constexpr double kUnit = 9.5367431640625e-07;        // 2^-20
-
-__device__ __forceinline__ uint64_t f64_key(double v) {          // monotone map double -> uint64
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_f64(uint64_t k) {
-    const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
 
 // ---- workspace layout of shg_limb_prepare (all 32-bit words unless noted) -------------------------------------------
 struct PrepLayout {
@@ -98,9 +90,9 @@ PrepLayout prep_layout(int64_t sh, int64_t sw, int k) {
     L.hist1 = off; off += (size_t)4 << L.bits1;
     L.coarse0 = off; off += 2 * 256;
     L.coarse1 = off; off += 4 * 256;
-    L.acc = off; off += 2 * (4 + 3 * FLOOD_SLOTS + 4 + FLOOD_SLOTS);     // u64 each: very_bright, the slots, the four order statistics, then the
-                                                                         // complemented keys of blur k's smallest values (k_limb_blur, one per slot)
-    L.counts = off; off += 20;
+    L.acc = off; off += 2 * ACC_WORDS;                          // u64 each: very_bright, the slots, the four order statistics, then the
+                                                                // complemented keys of blur k's smallest values (k_limb_blur, one per slot)
+    L.counts = off; off += HIST_BINS;
     L.done = off; off += 4;                                     // [0]: workgroups of the second radix pass that are through, [1]: of the histogram
     L.zero_words = off;                                         // everything up to here is zeroed by the call
     off = (off + 63) / 64 * 64;
@@ -233,11 +225,11 @@ __global__ __launch_bounds__(256) void k_limb_blur(const LimbBlurArgs kargs) {
     if (tid == 0) {
         const int slot = (blockIdx.y * gridDim.x + blockIdx.x) % FLOOD_SLOTS;
         const unsigned long long t = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (t) atomicAdd(&acc[4 + 3 * slot], t);
+        if (t) atomicAdd(&acc[acc_sum(slot)], t);
         // the smallest blurred value of the image: what min(blurred[blurred < very_bright]) is, once very_bright is known
         // (k_limb_select1).  Kept as the complement of its order-preserving key, so that zeroed memory is the neutral start.
         const uint32_t m = min(min(wmin[0], wmin[1]), min(wmin[2], wmin[3]));
-        if (m != 0xffffffffu) atomicMax(&acc[4 + 3 * FLOOD_SLOTS + 4 + slot], ~f64_key(((double)m * kUnit) * (1.0 / ((double)k * (double)k))));
+        if (m != 0xffffffffu) atomicMax(&acc[ACC_SMALLEST + slot], ~f64_key(((double)m * kUnit) * (1.0 / ((double)k * (double)k))));
     }
 }
 
@@ -387,10 +379,10 @@ __global__ __launch_bounds__(256) void k_limb_select1(const LimbSelect1Args karg
     __shared__ int scan_s;
     __shared__ unsigned long long wmax[4];
     if (threadIdx.x == 0) {
-        const double a = val[2], b = val[3], diff = b - a;
-        const double very_bright = gamma >= 0.5 ? b - diff * (1.0 - gamma) : a + diff * gamma;
+        const double a = val[2], b = val[3];
+        const double very_bright = shg::np_lerp(a, b, gamma);
         out4[0] = val[0]; out4[1] = val[1]; out4[2] = a; out4[3] = b;
-        acc[3] = (unsigned long long)__double_as_longlong(very_bright);
+        acc[ACC_VERY_BRIGHT] = (unsigned long long)__double_as_longlong(very_bright);
         vb_s = very_bright;
         scan_s = !(a < very_bright);
     }
@@ -416,10 +408,10 @@ __global__ __launch_bounds__(256) void k_limb_select1(const LimbSelect1Args karg
         if (scan_s) { hi = wmax[0]; for (int i = 1; i < 4; ++i) hi = wmax[i] > hi ? wmax[i] : hi; }
         else hi = f64_key(val[2]);
         unsigned long long inv = 0ull;
-        for (int s = 0; s < FLOOD_SLOTS; ++s) { const unsigned long long v = acc[4 + 3 * FLOOD_SLOTS + 4 + s]; inv = v > inv ? v : inv; }
+        for (int s = 0; s < FLOOD_SLOTS; ++s) { const unsigned long long v = acc[ACC_SMALLEST + s]; inv = v > inv ? v : inv; }
         unsigned long long lo = ~inv;                            // the key of the smallest value
         if (inv == 0ull || !(key_f64(lo) < very_bright)) { lo = ~0ull; hi = 0ull; }      // nothing below very_bright
-        for (int s = 0; s < FLOOD_SLOTS; ++s) { acc[5 + 3 * s] = s == 0 ? lo : ~0ull; acc[6 + 3 * s] = s == 0 ? hi : 0ull; }
+        for (int s = 0; s < FLOOD_SLOTS; ++s) { acc[acc_min(s)] = s == 0 ? lo : ~0ull; acc[acc_max(s)] = s == 0 ? hi : 0ull; }
     }
 }
 
@@ -444,96 +436,39 @@ __global__ __launch_bounds__(256) void k_limb_flood_hist(const LimbFloodHistArgs
     uint32_t* __restrict__ counts = kargs.counts;
     uint32_t* __restrict__ done = kargs.done;
     double* __restrict__ packed = kargs.packed;
-    const double very_bright = __longlong_as_double((long long)acc[3]);
-    __shared__ double edges[21];
-    __shared__ uint32_t lc[20];
+    const double very_bright = __longlong_as_double((long long)acc[ACC_VERY_BRIGHT]);
+    __shared__ double edges[HIST_BINS + 1];
+    __shared__ uint32_t lc[HIST_BINS];
     __shared__ int last;
-    unsigned long long total = 0, klo = ~0ull, khi = 0ull;
-    for (int s = 0; s < FLOOD_SLOTS; ++s) {
-        total += acc[4 + 3 * s];
-        klo = acc[5 + 3 * s] < klo ? acc[5 + 3 * s] : klo;
-        khi = acc[6 + 3 * s] > khi ? acc[6 + 3 * s] : khi;
-    }
-    const double mn = key_f64(klo), mx = key_f64(khi);
-    if (threadIdx.x < 21) {
-        // np.histogram: first == last -> (first - 0.5, last + 0.5); bin_edges = np.linspace(first, last, 21)
-        double first = mn, lastv = mx;
-        if (first == lastv) { first = first - 0.5; lastv = lastv + 0.5; }
-        const double step = (lastv - first) / 20.0;
-        edges[threadIdx.x] = threadIdx.x == 20 ? lastv : (double)threadIdx.x * step + first;
-    }
-    if (threadIdx.x < 20) lc[threadIdx.x] = 0;
+    const FloodFold f = flood_fold(acc);
+    const double mn = key_f64(f.klo), mx = key_f64(f.khi);
+    if (threadIdx.x < HIST_BINS + 1) edges[threadIdx.x] = hist_edge(mn, mx, threadIdx.x);
+    if (threadIdx.x < HIST_BINS) lc[threadIdx.x] = 0;
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double b = ((double)keysk[i] * kUnit) * scale_k;
         if (!(b < very_bright)) continue;
-        int bin = 0;                                  // largest bin with edges[bin] <= b; the last bin is closed
-        for (int j = 1; j < 20; ++j) bin = (b >= edges[j]) ? j : bin;
-        atomicAdd(&lc[bin], 1u);
+        atomicAdd(&lc[hist_bin([&](int j) { return edges[j]; }, b)], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < 20 && lc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], lc[threadIdx.x]);
+    if (threadIdx.x < HIST_BINS && lc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], lc[threadIdx.x]);
     published();
     if (threadIdx.x == 0) last = count_done(done, gridDim.x, kargs.fence);
     __syncthreads();
     if (!last) return;
-    if (threadIdx.x < 20) {
+    if (threadIdx.x < HIST_BINS) {
         uint32_t* pc = reinterpret_cast<uint32_t*>(packed + 8);
         pc[threadIdx.x] = __hip_atomic_load(&counts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (threadIdx.x == 0) {
         packed[0] = out4[0]; packed[1] = out4[1]; packed[2] = out4[2]; packed[3] = out4[3];
-        packed[4] = (double)total / 1048576.0;
+        packed[4] = (double)f.total / kPerUnit;
         packed[5] = mn;
         packed[6] = mx;
     }
 }
 
 // ---- K5: canny up to its masks, and the union-find of the low mask inside the tile ----------------------------------------------
-// glibc 2.35 hypot (sysdeps/ieee754/dbl-64/e_hypot.c, the non-FMA kernel), as limb.hip
-__device__ __forceinline__ double hypot_glibc(double x, double y) {
-    x = fabs(x);
-    y = fabs(y);
-    const double ax = x < y ? y : x;
-    const double ay = x < y ? x : y;
-    if (ax >= ay / 0x1p-54) return ax + ay;
-    double hh = sqrt(ax * ax + ay * ay);
-    double t1, t2;
-    if (hh <= 2.0 * ay) {
-        const double delta = hh - ay;
-        t1 = ax * (2.0 * delta - ax);
-        t2 = (delta - 2.0 * (ax - ay)) * delta;
-    } else {
-        const double delta = hh - ax;
-        t1 = 2.0 * delta * (ax - 2.0 * ay);
-        t2 = (4.0 * delta - ay) * ay + delta * delta;
-    }
-    hh -= (t1 + t2) / (2.0 * hh);
-    return hh;
-}
-
-__device__ __forceinline__ int refl(int i, int n) {       // scipy mode 'reflect': d c b a | a b c d | d c b a
-    return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i);
-}
-
-__device__ __forceinline__ int lds_find(volatile int* lab, int x) {
-    int p = lab[x];
-    while (p != x) { x = p; p = lab[x]; }
-    return x;
-}
-
-__device__ __forceinline__ void lds_union(int* lab, int a, int b) {
-    while (true) {
-        a = lds_find(lab, a);
-        b = lds_find(lab, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }      // the larger root goes under the smaller
-        const int old = atomicMin(&lab[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 // Dynamic LDS (bytes): F u8 [(TH+4+2R)][(TW+4+2R)] | gv f64 [TH+4] | V f64 [(TH+4)][(TW+4+2R)] | Sm f64 [(TH+4)][(TW+4)] |
 // I, J, M f64 [(TH+2)][(TW+2)] each | lab int [TH*TW]
 struct LimbCannyArgs {
@@ -567,31 +502,25 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
     uint8_t* F = reinterpret_cast<uint8_t*>(lab + TH * TW);
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
-    // img_blurred[< thresh3] = 0, [>= thresh3] = 65000 (:226-227); outside the image: 0 (gaussian_filter mode='constant')
+    // the flood image, a byte per pixel: whether it is 65000; outside the image: 0 (gaussian_filter mode='constant')
     for (int e = tid; e < FH * FW; e += NT1) {
         const int r = e / FW, c = e - r * FW;
         const int y = y0 - 2 - R + r, x = x0 - 2 - R + c;
         uint8_t f = 0;
-        if (y >= 0 && y < h && x >= 0 && x < w) f = (((double)keysk[(int64_t)y * w + x] * kUnit) * scale_k < flood_thresh) ? 0 : 1;
+        if (y >= 0 && y < h && x >= 0 && x < w) f = flood_below(((double)keysk[(int64_t)y * w + x] * kUnit) * scale_k, flood_thresh) ? 0 : 1;
         F[e] = f;
     }
     // the all-ones mask after the first axis: a function of the row alone
     if (tid < VH) {
         const int y = y0 - 2 + tid;
-        auto one = [&](int yy) -> double { return (yy < 0 || yy >= h) ? 0.0 : 1.0; };
-        double u = one(y) * g.w[R];
-        for (int j = -R; j < 0; ++j) u += (one(y + j) + one(y - j)) * g.w[R + j];
-        gv[tid] = u;
+        gv[tid] = correlate1d_sym(g, [&](int j) -> double { return (y + j < 0 || y + j >= h) ? 0.0 : 1.0; });
     }
     __syncthreads();
     // Gaussian along axis 0
     for (int e = tid; e < VH * VW; e += NT1) {
         const int r = e / VW, c = e - r * VW;
         const int fr = r + R;                                   // row of F
-        auto px = [&](int rr) -> double { return F[rr * FW + c] ? 65000.0 : 0.0; };
-        double t = px(fr) * g.w[R];
-        for (int j = -R; j < 0; ++j) t += (px(fr + j) + px(fr - j)) * g.w[R + j];
-        V[e] = t;
+        V[e] = correlate1d_sym(g, [&](int j) -> double { return flood_value(!F[(fr + j) * FW + c]); });
     }
     __syncthreads();
     // Gaussian along axis 1 of both planes, then smoothed = image / (bleed_over + eps)
@@ -602,6 +531,8 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
         if (y >= 0 && y < h && x >= 0 && x < w) {
             const double* a = V + r * VW + c + R;
             const double gvr = gv[r];
+            // correlate1d_sym's order, written out: through the helper (two calls, or both lines in one) this kernel ran 0.2 us,
+            // 1.3 %, slower than with this loop, outside the spread of the kernel before the helpers (profiles/limb_shared_math_ab.txt)
             auto b = [&](int xx) -> double { return (xx < 0 || xx >= w) ? 0.0 : gvr; };
             double t = a[0] * g.w[R];
             double u = gvr * g.w[R];
@@ -609,7 +540,7 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
                 t += (a[j] + a[-j]) * g.w[R + j];
                 u += (b(x + j) + b(x - j)) * g.w[R + j];
             }
-            sm = t / (u + 2.220446049250313e-16);
+            sm = bleed_over_div(t, u);
         }
         Sm[e] = sm;
     }
@@ -620,14 +551,7 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
         const int y = y0 - 1 + r, x = x0 - 1 + c;
         double iv = 0.0, jv = 0.0, mg = 0.0;
         if (y >= 0 && y < h && x >= 0 && x < w) {
-            const int ym = refl(y - 1, h), yp = refl(y + 1, h), xm = refl(x - 1, w), xp = refl(x + 1, w);
-            auto S = [&](int yy, int xx) -> double { return Sm[(yy - (y0 - 2)) * SW + (xx - (x0 - 2))]; };
-            auto dy = [&](int xx) -> double { double t = S(y, xx) * 0.0; t += (S(ym, xx) - S(yp, xx)) * -1.0; return t; };
-            auto dx = [&](int yy) -> double { double t = S(yy, x) * 0.0; t += (S(yy, xm) - S(yy, xp)) * -1.0; return t; };
-            iv = dy(x) * 2.0;
-            iv += (dy(xm) + dy(xp)) * 1.0;
-            jv = dx(y) * 2.0;
-            jv += (dx(ym) + dx(yp)) * 1.0;
+            sobel_pair([&](int yy, int xx) -> double { return Sm[(yy - (y0 - 2)) * SW + (xx - (x0 - 2))]; }, y, x, h, w, iv, jv);
             mg = hypot_glibc(iv, jv);
         }
         I[e] = iv; J[e] = jv; M[e] = mg;
@@ -640,25 +564,9 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
         uint8_t bits = 0;
         if (y < h && x < w) {
             const int me = (ty + 1) * MW + tx + 1;
-            const double m = M[me];
-            bool local = false;
-            if (y > 0 && y < h - 1 && x > 0 && x < w - 1 && m > 0.0) {
-                const double is = I[me], js = J[me];
-                const double ai = fabs(is), aj = fabs(js);
-                auto Mn = [&](int dy, int dx) -> double { return M[me + dy * MW + dx]; };
-                const bool same = (is >= 0 && js >= 0) || (is <= 0 && js <= 0);
-                const bool opp = (is <= 0 && js >= 0) || (is >= 0 && js <= 0);
-                auto test = [&](double wgt, double p1, double p2, double m1, double m2) -> bool {
-                    const bool c_plus = p2 * wgt + p1 * (1 - wgt) <= m;
-                    const bool c_minus = m2 * wgt + m1 * (1 - wgt) <= m;
-                    return c_plus && c_minus;
-                };
-                if (same && ai >= aj) local = test(aj / ai, Mn(1, 0), Mn(1, 1), Mn(-1, 0), Mn(-1, -1));
-                if (same && ai <= aj) local = test(ai / aj, Mn(0, 1), Mn(1, 1), Mn(0, -1), Mn(-1, -1));
-                if (opp && ai <= aj) local = test(ai / aj, Mn(0, 1), Mn(-1, 1), Mn(0, -1), Mn(1, -1));
-                if (opp && ai >= aj) local = test(aj / ai, Mn(-1, 0), Mn(-1, 1), Mn(1, 0), Mn(1, -1));
-            }
-            bits = (uint8_t)(((local && m >= low) ? 1 : 0) | ((local && m >= high) ? 2 : 0));
+            bits = (uint8_t)nms_bits(y, x, h, w, M[me],
+                                     [&](double& is, double& js) { is = I[me]; js = J[me]; },
+                                     [&](int dy, int dx) -> double { return M[me + dy * MW + dx]; }, low, high);
             mask[(int64_t)y * w + x] = bits;
         }
         lab[e] = (bits & 1) ? e : -1;
@@ -668,11 +576,11 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
     for (int e = tid; e < TH * TW; e += NT1) {
         if (lab[e] < 0) continue;
         const int ty = e / TW, tx = e - ty * TW;
-        if (tx > 0 && lab[e - 1] >= 0) lds_union(lab, e, e - 1);
+        if (tx > 0 && lab[e - 1] >= 0) uf_union<LdsLoad>(lab, e, e - 1);
         if (ty > 0) {
-            if (tx > 0 && lab[e - TW - 1] >= 0) lds_union(lab, e, e - TW - 1);
-            if (lab[e - TW] >= 0) lds_union(lab, e, e - TW);
-            if (tx < TW - 1 && lab[e - TW + 1] >= 0) lds_union(lab, e, e - TW + 1);
+            if (tx > 0 && lab[e - TW - 1] >= 0) uf_union<LdsLoad>(lab, e, e - TW - 1);
+            if (lab[e - TW] >= 0) uf_union<LdsLoad>(lab, e, e - TW);
+            if (tx < TW - 1 && lab[e - TW + 1] >= 0) uf_union<LdsLoad>(lab, e, e - TW + 1);
         }
     }
     __syncthreads();
@@ -683,7 +591,7 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
         if (y >= h || x >= w) continue;
         int gl = -1;
         if (lab[e] >= 0) {
-            const int r = lds_find(lab, e);
+            const int r = uf_find<LdsLoad>(lab, e);
             gl = (y0 + r / TW) * w + x0 + (r % TW);
         }
         L[(int64_t)y * w + x] = gl;
@@ -697,24 +605,6 @@ __global__ __launch_bounds__(NT1) void k_limb_canny_tile(const LimbCannyArgs kar
 }
 
 // ---- K6: unions across tile borders (global atomics, as limb.hip's k_ccl_merge) ---------------------------------------------------
-__device__ __forceinline__ int g_find(const int* L, int x) {
-    int p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x) { x = p; p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return x;
-}
-
-__device__ __forceinline__ void g_union(int* L, int a, int b) {
-    while (true) {
-        a = g_find(L, a);
-        b = g_find(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 // one thread per pixel of a tile's first row (blockIdx.y = 0: tile row, x), first or last column (blockIdx.y = 1: column line, y)
 struct LimbBorderArgs {
     const uint8_t* mask;
@@ -741,12 +631,12 @@ __global__ __launch_bounds__(256) void k_limb_border_merge(const LimbBorderArgs 
     const int i = y * w + x;
     if (!(mask[i] & 1)) return;
     const bool top = (y % TH) == 0, left = (x % TW) == 0, right = (x % TW) == TW - 1;
-    if (left && x > 0 && (mask[i - 1] & 1)) g_union(L, i, i - 1);
+    if (left && x > 0 && (mask[i - 1] & 1)) uf_union<AgentLoad>(L, i, i - 1);
     if (y > 0) {
         const int up = i - w;
-        if ((top || left) && x > 0 && (mask[up - 1] & 1)) g_union(L, i, up - 1);
-        if (top && (mask[up] & 1)) g_union(L, i, up);
-        if ((top || right) && x < w - 1 && (mask[up + 1] & 1)) g_union(L, i, up + 1);
+        if ((top || left) && x > 0 && (mask[up - 1] & 1)) uf_union<AgentLoad>(L, i, up - 1);
+        if (top && (mask[up] & 1)) uf_union<AgentLoad>(L, i, up);
+        if ((top || right) && x < w - 1 && (mask[up + 1] & 1)) uf_union<AgentLoad>(L, i, up + 1);
     }
 }
 
@@ -785,7 +675,7 @@ __global__ __launch_bounds__(256) void k_limb_emit(const LimbEmitArgs kargs) {
             const int i = y * w + x;
             const int l = L[i];
             if (l >= 0) {
-                root = g_find(L, l);
+                root = uf_find<AgentLoad>(L, l);
                 hi = (mask[i] >> 1) & 1;
             }
         }
@@ -856,7 +746,7 @@ extern "C" int shg_limb_prepare(const uint16_t* img, int64_t h, int64_t w, int64
     uint32_t *counts = ws + lay.counts, *done = ws + lay.done;
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + lay.acc);
     uint32_t *keysk = ws + lay.keysk, *keys5 = k == 5 ? keysk : ws + lay.keys5;
-    double* out4 = reinterpret_cast<double*>(acc + 4 + 3 * FLOOD_SLOTS);
+    double* out4 = reinterpret_cast<double*>(acc + ACC_ORDER_STATS);
     SHG_PROF("limb_prepare", st);
     if (shg::t_prezeroed == workspace) {                       // the extraction's last launch has cleared them on its way (shg_scan_file)
         shg::t_prezeroed = nullptr;

@@ -188,14 +188,10 @@ __device__ __forceinline__ uint16_t rescale1(double px, double lo, double span) 
 // percentile, cl1: two of the 10th percentile, cl1 max}; NumPy's _lerp.  -> false where rescale_brightness's assert fails
 // (the kernel then writes nothing and the host, which sees the same numbers, reports it).
 struct StatsSource { const double* stats5; double g_bright, g_dark; double* mirror5; };
-__device__ __forceinline__ double lerp_np(double a, double b, double gamma) {
-    const double diff = b - a;
-    return gamma >= 0.5 ? b - diff * (1 - gamma) : a + diff * gamma;
-}
 __device__ __forceinline__ bool bounds_from_stats(const StatsSource& src, int disk, Bounds6& b) {
     const double* s = src.stats5 + 5 * disk;
-    const double bright = lerp_np(s[0], s[1], src.g_bright);                 // basically the same as max
-    const double dark_clahe = lerp_np(s[2], s[3], src.g_dark);
+    const double bright = shg::np_lerp(s[0], s[1], src.g_bright);                 // basically the same as max
+    const double dark_clahe = shg::np_lerp(s[2], s[3], src.g_dark);
     const double bright_clahe = (double)(int64_t)s[4];
     b.lo[0] = bright * 0.25; b.span[0] = bright - b.lo[0];
     b.lo[1] = 0.0;           b.span[1] = bright * 0.18 - 0.0;

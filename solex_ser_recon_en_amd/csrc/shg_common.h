@@ -1,10 +1,54 @@
 // Shared helpers for the libshg_hip.so translation units (gfx950 only).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#endif
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include <type_traits>
+
+// ---- plain C++, host and device: what tests/ also compiles with the host compiler (as fast_log.h) ----------------------
+#if defined(__HIPCC__)
+#define SHG_HD __host__ __device__ __forceinline__
+#else
+#define SHG_HD inline
+#endif
+
+namespace shg {
+
+// Monotone map double -> uint64 and back (no NaN): key order = value order, -0.0 below +0.0.  What the exact order
+// statistics (radix selects) and the atomicMin / atomicMax of float64 values run on.
+SHG_HD uint64_t f64_key(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+#else
+    uint64_t b;
+    memcpy(&b, &v, sizeof b);
+#endif
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+SHG_HD double key_f64(uint64_t k) {
+    const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __longlong_as_double((long long)b);
+#else
+    double v;
+    memcpy(&v, &b, sizeof v);
+    return v;
+#endif
+}
+
+// NumPy's _lerp for np.percentile's linear method: a, b the two order statistics, gamma the weight of b
+SHG_HD double np_lerp(double a, double b, double gamma) {
+    const double diff = b - a;
+    return gamma >= 0.5 ? b - diff * (1 - gamma) : a + diff * gamma;
+}
+
+}  // namespace shg
+
+#if defined(__HIPCC__)
 #include "../../include/shg_hip.h"
 
 namespace shg {
@@ -277,3 +321,5 @@ __host__ __device__ __forceinline__ int64_t reflect101(int64_t i, int64_t n) {
 }
 
 }  // namespace shg
+
+#endif  // __HIPCC__

@@ -301,16 +301,171 @@ int64_t keep_strong_components(int32_t* idx, int32_t* root, int64_t m, int64_t n
     for (int64_t i = 0; i < kept; ++i) strong[(size_t)root[i]] = 0;          // (every marked root kept at least its marking pixel)
     return kept;
 }
+// The two chains of the stage.  Each carves its device workspace and has two steps of its own:
+//   prepare(...)  get_flood_image's statistics into the pinned h_packed (a stream synchronisation later the host reads them):
+//                 [0..3] the order statistics `ranks`, [4] sum(image), [5] min, [6] max, then 20 uint32 counts at h_packed + 8
+//   edges(...)    canny at one rung of the ladder + labelling into the pinned h_comp = [m | idx[n] | root[n]];
+//                 kept(h_comp, n) after the synchronisation: the m edge pixels (hysteresis done) at idx / root
+// Everything else -- what is asked of prepare, the decisions taken from its numbers, the ladder, the point list -- is
+// limb_points_with() below, once.
+struct LimbImage { const uint16_t* disk; int64_t h, w, pitch, sh, sw, n; int k; };
+
+// limb_fused.hip
+struct FusedLimb {
+    size_t prep_bytes, edge_bytes;
+    char *prep_ws = nullptr, *edge_ws = nullptr;
+    const uint32_t* keys = nullptr;
+    FusedLimb(const LimbImage& im) : prep_bytes(shg_limb_prepare_workspace_bytes(im.sh, im.sw, im.k)), edge_bytes(shg_limb_edges_workspace_bytes(im.sh, im.sw)) {}
+    size_t bytes() const { return up(prep_bytes) + up(edge_bytes) + kAlign; }
+    bool carve(Arena& dev) {
+        prep_ws = dev.take<char>(prep_bytes);
+        edge_ws = dev.take<char>(edge_bytes);
+        return prep_ws && edge_ws;
+    }
+    int prepare(const LimbImage& im, const int64_t* ranks, double gamma99, double* packed_dev, shg_stream_t stream) {
+        return shg_limb_prepare(im.disk, im.h, im.w, im.pitch, im.k, ranks, gamma99, packed_dev, &keys, prep_ws, prep_bytes, stream);
+    }
+    int edges(const LimbImage& im, double thresh3, const double* taps, int radius, double low, double high, int32_t* comp_dev, shg_stream_t stream) {
+        return shg_limb_edges(keys, im.sh, im.sw, im.k, thresh3, taps, radius, low, high, comp_dev, edge_ws, edge_bytes, stream);
+    }
+    // the list holds the LOW mask's pixels: skimage's hysteresis on the host
+    int64_t kept(int32_t* h_comp, int64_t n) const { return keep_strong_components(h_comp + 1, h_comp + 1 + n, h_comp[0], n); }
+};
+
+// limb.hip: blur windows above the fused tile's, and SHG_LIMB_FUSED=0
+struct SeparateLimb {
+    size_t n, sel_bytes, canny_bytes, cc_bytes;
+    double *small = nullptr, *blurred = nullptr, *blur5 = nullptr, *tmp = nullptr, *packed = nullptr;   // packed: as h_packed
+    char *sel_ws = nullptr, *flood_ws = nullptr, *canny_ws = nullptr, *cc_ws = nullptr;
+    uint32_t *keys_k = nullptr, *keys_5 = nullptr;
+    uint8_t *low_mask = nullptr, *high_mask = nullptr;
+    int32_t* comp = nullptr;                                                                            // [count | idx[n] | root[n]]
+    SeparateLimb(const LimbImage& im)
+        : n((size_t)im.n), sel_bytes(std::max(shg_select_workspace_bytes(4), shg_select_keys_workspace_bytes(4))),
+          canny_bytes(shg_canny_workspace_bytes(im.sh, im.sw)), cc_bytes(shg_edge_components_workspace_bytes(im.sh, im.sw)) {}
+    // The one layout: carve() takes these areas in this order, bytes() is their sum (and three slots the size query has always
+    // counted beyond them, kept so that the size it reports does not change).
+    template <typename Take>
+    void layout(Take take) {
+        take(small, n); take(blurred, n); take(blur5, n); take(tmp, n);
+        take(sel_ws, sel_bytes);
+        take(keys_k, n); take(keys_5, n);
+        take(packed, 32);
+        take(flood_ws, 256);
+        take(low_mask, n); take(high_mask, n);
+        take(canny_ws, canny_bytes); take(cc_ws, cc_bytes);
+        take(comp, 2 * n + 1);
+    }
+    size_t bytes() {
+        size_t total = 0;
+        layout([&](auto*& p, size_t count) { total += up(count * sizeof(*p)); });
+        return total + 3 * kAlign + kAlign;
+    }
+    bool carve(Arena& dev) {
+        bool ok = true;
+        layout([&](auto*& p, size_t count) { p = dev.take<std::remove_reference_t<decltype(*p)>>(count); ok = ok && p; });
+        return ok;
+    }
+    int prepare(const LimbImage& im, const int64_t* ranks, double gamma99, double* packed_dev, shg_stream_t stream) {
+        const int64_t sh = im.sh, sw = im.sw;
+        const int k = im.k;
+        STAGE_TRY(shg_downscale_mean_u16(im.disk, im.h, im.w, im.pitch, kFactor, small, stream));
+        if (k <= 63) {
+            // the block means are whole numbers of 2^-20: select on the integer window sums (three passes instead of eight)
+            STAGE_TRY(shg_box_blur_key_f64(small, sh, sw, k, blurred, keys_k, tmp, stream));
+            if (k == 5) {                                    // 2000-2399 slit rows: cv2.blur(img, (k, k)) is the 5 x 5 blur itself
+                blur5 = blurred;
+                keys_5 = keys_k;
+            } else {
+                STAGE_TRY(shg_box_blur_key_f64(small, sh, sw, 5, blur5, keys_5, tmp, stream));
+            }
+            const uint32_t* karr[4] = {keys_5, keys_5, keys_k, keys_k};
+            const int kk[4] = {5, 5, k, k};
+            STAGE_TRY(shg_select_keys_u32(karr, im.n, ranks, kk, 4, packed, sel_ws, sel_bytes, stream));
+        } else {
+            STAGE_TRY(shg_box_blur_f64(small, sh, sw, k, blurred, tmp, stream));
+            STAGE_TRY(shg_box_blur_f64(small, sh, sw, 5, blur5, tmp, stream));      // (k > 63 here, never 5)
+            const double* arrays[4] = {blur5, blur5, blurred, blurred};
+            STAGE_TRY(shg_select_multi_f64(arrays, im.n, ranks, 4, packed, sel_ws, sel_bytes, stream));
+        }
+        STAGE_TRY(shg_flood_stats_lerp_f64(small, blurred, im.n, packed + 2, gamma99, packed + 4, reinterpret_cast<uint32_t*>(packed + 8), flood_ws, stream));
+        return move_words(packed_dev, packed, 8 * 8 + 20 * 4, shg::as_stream(stream));
+    }
+    int edges(const LimbImage& im, double thresh3, const double* taps, int radius, double low, double high, int32_t* comp_dev, shg_stream_t stream) {
+        STAGE_TRY(shg_canny_masks_f64(blurred, im.sh, im.sw, thresh3, taps, radius, low, high, low_mask, high_mask, canny_ws, canny_bytes, stream));
+        STAGE_TRY(shg_edge_components(low_mask, high_mask, im.sh, im.sw, comp + 1, comp + 1 + im.n, comp, cc_ws, cc_bytes, stream));
+        k_edge_list<<<16, 256, 0, shg::as_stream(stream)>>>(comp, im.n, comp_dev);                       // the device knows how many: one trip
+        return shg::check_launch("k_edge_list");
+    }
+    int64_t kept(int32_t* h_comp, int64_t) const { return h_comp[0]; }                                   // (the device kept the strong components)
+};
+
+inline LimbImage limb_image(const uint16_t* disk, int64_t h, int64_t w, int64_t pitch) {
+    const int64_t sh = small_dim(h), sw = small_dim(w);
+    return LimbImage{disk, h, w, pitch, sh, sw, sh * sw, (int)((double)sh * 0.01)};                      // cv2.blur kernel, :163
+}
+
+template <typename Chain>
+int limb_points_with(Chain chain, const LimbImage& im, const double* host_gauss_taps, int32_t* host_points, uint8_t* host_flags, int64_t points_cap,
+                     int64_t* host_counts2, void* workspace, size_t workspace_bytes, void* host_pinned, size_t host_pinned_bytes, shg_stream_t stream) {
+    const int64_t sh = im.sh, sw = im.sw, n = im.n;
+    hipStream_t st = shg::as_stream(stream);
+    Arena dev(workspace, workspace_bytes), pin(host_pinned, host_pinned_bytes);
+    const bool carved = chain.carve(dev);
+    double* h_packed = pin.take<double>(32);
+    int32_t* h_comp = pin.take<int32_t>(2 * (size_t)n + 1);
+    SHG_REQUIRE(carved, SHG_E_WORKSPACE, "shg_stage_limb_points: workspace too small");
+    SHG_REQUIRE(h_packed && h_comp, SHG_E_WORKSPACE, "shg_stage_limb_points: pinned staging area too small");
+    Staging stg;
+    STAGE_TRY(map_staging(host_pinned, &stg, "shg_stage_limb_points"));
+    // np.median(blur 5x5) (:241) and np.percentile(blurred, 99) (:165): their order statistics
+    int64_t ranks[4];
+    double gamma99;
+    ranks[0] = (n & 1) ? n / 2 : n / 2 - 1;
+    ranks[1] = n / 2;
+    STAGE_TRY(shg_host_percentile_plan(n, 99.0, &ranks[2], &ranks[3], &gamma99));
+    STAGE_TRY(chain.prepare(im, ranks, gamma99, stg.on_device(h_packed), stream));
+    STAGE_SYNC(st, "shg_stage_limb_points");
+    const double median5 = (n & 1) ? h_packed[0] : (h_packed[0] + h_packed[1]) / 2;
+    const double low = median5 / 10, high = low * 1.5;                                       // :241-243
+    int64_t counts64[20];
+    const uint32_t* hc = reinterpret_cast<const uint32_t*>(h_packed + 8);
+    for (int i = 0; i < 20; ++i) counts64[i] = hc[i];
+    double thresh3;
+    STAGE_TRY(shg_host_flood_threshold(h_packed[4], sh, sw, h_packed[5], h_packed[6], counts64, &thresh3));
+
+    int64_t m = 0;
+    const double* taps = host_gauss_taps;
+    for (int rung = 0;; ++rung) {                                                             // sigma = 2, 1.5, 1, 0.5
+        if (rung == 4) { shg::set_error("ellipse fit: could not find any edges of the solar disk"); return SHG_E_RUNTIME; }
+        const double sigma = 2.0 - 0.5 * rung;
+        const int radius = (int)(4.0 * sigma + 0.5);
+        STAGE_TRY(chain.edges(im, thresh3, taps, radius, low, high, stg.on_device(h_comp), stream));
+        STAGE_SYNC(st, "shg_stage_limb_points");
+        SHG_REQUIRE(h_comp[0] >= 0 && h_comp[0] <= n, SHG_E_RUNTIME, "shg_stage_limb_points: %lld edge pixels in an image of %lld", (long long)h_comp[0], (long long)n);
+        m = chain.kept(h_comp, n);
+        if (m > 0) break;
+        taps += 2 * radius + 1;                                                               // try again with less blur (:254-256)
+    }
+    const int32_t* idx = h_comp + 1;
+    const int32_t* root = h_comp + 1 + n;
+    SHG_REQUIRE(points_cap >= m, SHG_E_WORKSPACE, "shg_stage_limb_points: %lld edge pixels, room for %lld", (long long)m, (long long)points_cap);
+    int64_t n_sel = 0;
+    STAGE_TRY(shg_host_limb_points(idx, root, m, sh, sw, host_flags, &n_sel));
+    for (int64_t i = 0; i < m; ++i) {
+        host_points[2 * i] = idx[i] / (int32_t)sw;
+        host_points[2 * i + 1] = idx[i] % (int32_t)sw;
+    }
+    host_counts2[0] = m;
+    host_counts2[1] = n_sel;
+    return 0;
+}
 }  // namespace
 
 extern "C" size_t shg_stage_limb_points_workspace_bytes(int64_t h, int64_t w) {
     if (h <= 0 || w <= 0) return 0;
-    const int64_t sh = small_dim(h), sw = small_dim(w);
-    const size_t n = (size_t)sh * (size_t)sw;
-    const int k = (int)((double)sh * 0.01);
-    if (limb_fused(sh, sw, k)) return up(shg_limb_prepare_workspace_bytes(sh, sw, k)) + up(shg_limb_edges_workspace_bytes(sh, sw)) + kAlign;
-    return 4 * up(n * 8) + up(std::max(shg_select_workspace_bytes(4), shg_select_keys_workspace_bytes(4))) + 2 * up(n * 4) + up(4 * 8) + up(3 * 8) + up(20 * 4) + up(256) + up(32 * 8) + 2 * up(n) +
-           up(shg_canny_workspace_bytes(sh, sw)) + up(shg_edge_components_workspace_bytes(sh, sw)) + up((2 * n + 1) * 4) + kAlign;
+    const LimbImage im = limb_image(nullptr, h, w, w);
+    return limb_fused(im.sh, im.sw, im.k) ? FusedLimb(im).bytes() : SeparateLimb(im).bytes();
 }
 
 extern "C" size_t shg_stage_limb_points_host_bytes(int64_t h, int64_t w) {
@@ -331,157 +486,16 @@ extern "C" int shg_stage_limb_points(const uint16_t* disk, int64_t h, int64_t w,
     SHG_REQUIRE(disk && host_gauss_taps && host_points && host_flags && host_counts2 && workspace && host_pinned, SHG_E_ARG,
                 "shg_stage_limb_points: null pointer");
     SHG_REQUIRE(h > 0 && w > 0 && pitch >= w, SHG_E_ARG, "shg_stage_limb_points: bad image size");
-    const int64_t sh = small_dim(h), sw = small_dim(w);
-    const int64_t n = sh * sw;
-    const int k = (int)((double)sh * 0.01);                                                  // cv2.blur kernel, :163
-    if (k <= 0) {
+    const LimbImage im = limb_image(disk, h, w, pitch);
+    if (im.k <= 0) {
         shg::set_error("ellipse fit: the scan needs at least 400 slit rows (cv2.blur kernel int(0.01 * h/4) = 0)");
         return SHG_E_RUNTIME;
     }
-    hipStream_t st = shg::as_stream(stream);
-    if (limb_fused(sh, sw, k)) {
-        Arena dev(workspace, workspace_bytes), pin(host_pinned, host_pinned_bytes);
-        const size_t prep_bytes = shg_limb_prepare_workspace_bytes(sh, sw, k), edge_bytes = shg_limb_edges_workspace_bytes(sh, sw);
-        char* prep_ws = dev.take<char>(prep_bytes);
-        char* edge_ws = dev.take<char>(edge_bytes);
-        double* h_packed = pin.take<double>(32);
-        int32_t* h_comp = pin.take<int32_t>(2 * (size_t)n + 1);
-        SHG_REQUIRE(prep_ws && edge_ws, SHG_E_WORKSPACE, "shg_stage_limb_points: workspace too small");
-        SHG_REQUIRE(h_packed && h_comp, SHG_E_WORKSPACE, "shg_stage_limb_points: pinned staging area too small");
-        Staging stg;
-        STAGE_TRY(map_staging(host_pinned, &stg, "shg_stage_limb_points"));
-        int64_t ranks[4];
-        double gamma99;
-        ranks[0] = (n & 1) ? n / 2 : n / 2 - 1;                                               // np.median(blur 5x5) (:241)
-        ranks[1] = n / 2;
-        STAGE_TRY(shg_host_percentile_plan(n, 99.0, &ranks[2], &ranks[3], &gamma99));          // np.percentile(blurred, 99) (:165)
-        const uint32_t* keys = nullptr;
-        STAGE_TRY(shg_limb_prepare(disk, h, w, pitch, k, ranks, gamma99, stg.on_device(h_packed), &keys, prep_ws, prep_bytes, stream));
-        STAGE_SYNC(st, "shg_stage_limb_points");
-        const double median5 = (n & 1) ? h_packed[0] : (h_packed[0] + h_packed[1]) / 2;
-        const double low = median5 / 10, high = low * 1.5;                                   // :241-243
-        int64_t counts64[20];
-        const uint32_t* hc = reinterpret_cast<const uint32_t*>(h_packed + 8);
-        for (int i = 0; i < 20; ++i) counts64[i] = hc[i];
-        double thresh3;
-        STAGE_TRY(shg_host_flood_threshold(h_packed[4], sh, sw, h_packed[5], h_packed[6], counts64, &thresh3));
-        int64_t m = 0;
-        const double* taps = host_gauss_taps;
-        int32_t* idx = h_comp + 1;
-        int32_t* root = h_comp + 1 + n;
-        for (int rung = 0;; ++rung) {                                                         // sigma = 2, 1.5, 1, 0.5
-            if (rung == 4) { shg::set_error("ellipse fit: could not find any edges of the solar disk"); return SHG_E_RUNTIME; }
-            const double sigma = 2.0 - 0.5 * rung;
-            const int radius = (int)(4.0 * sigma + 0.5);
-            STAGE_TRY(shg_limb_edges(keys, sh, sw, k, thresh3, taps, radius, low, high, stg.on_device(h_comp), edge_ws, edge_bytes, stream));
-            STAGE_SYNC(st, "shg_stage_limb_points");
-            const int64_t m_low = h_comp[0];
-            SHG_REQUIRE(m_low >= 0 && m_low <= n, SHG_E_RUNTIME, "shg_stage_limb_points: %lld edge pixels in an image of %lld", (long long)m_low, (long long)n);
-            m = keep_strong_components(idx, root, m_low, n);
-            if (m > 0) break;
-            taps += 2 * radius + 1;                                                           // try again with less blur (:254-256)
-        }
-        SHG_REQUIRE(points_cap >= m, SHG_E_WORKSPACE, "shg_stage_limb_points: %lld edge pixels, room for %lld", (long long)m, (long long)points_cap);
-        int64_t n_sel = 0;
-        STAGE_TRY(shg_host_limb_points(idx, root, m, sh, sw, host_flags, &n_sel));
-        for (int64_t i = 0; i < m; ++i) {
-            host_points[2 * i] = idx[i] / (int32_t)sw;
-            host_points[2 * i + 1] = idx[i] % (int32_t)sw;
-        }
-        host_counts2[0] = m;
-        host_counts2[1] = n_sel;
-        return 0;
-    }
-    Arena dev(workspace, workspace_bytes), pin(host_pinned, host_pinned_bytes);
-    double* small = dev.take<double>((size_t)n);
-    double* blurred = dev.take<double>((size_t)n);
-    double* blur5 = dev.take<double>((size_t)n);
-    double* tmp = dev.take<double>((size_t)n);
-    const size_t sel_bytes = std::max(shg_select_workspace_bytes(4), shg_select_keys_workspace_bytes(4));
-    char* sel_ws = dev.take<char>(sel_bytes);
-    uint32_t* keys_k = dev.take<uint32_t>((size_t)n);
-    uint32_t* keys_5 = dev.take<uint32_t>((size_t)n);
-    double* packed = dev.take<double>(32);                 // [0..3] order statistics, [4..6] flood stats, [8..17] the 20 counts
-    uint32_t* counts = packed ? reinterpret_cast<uint32_t*>(packed + 8) : nullptr;
-    char* flood_ws = dev.take<char>(256);
-    uint8_t* low_mask = dev.take<uint8_t>((size_t)n);
-    uint8_t* high_mask = dev.take<uint8_t>((size_t)n);
-    const size_t canny_bytes = shg_canny_workspace_bytes(sh, sw), cc_bytes = shg_edge_components_workspace_bytes(sh, sw);
-    char* canny_ws = dev.take<char>(canny_bytes);
-    char* cc_ws = dev.take<char>(cc_bytes);
-    int32_t* comp = dev.take<int32_t>(2 * (size_t)n + 1);  // [count | idx[n] | root[n]]
-    double* h_packed = pin.take<double>(32);
-    int32_t* h_comp = pin.take<int32_t>(2 * (size_t)n + 1);
-    SHG_REQUIRE(small && blurred && blur5 && tmp && sel_ws && keys_k && keys_5 && packed && counts && flood_ws && low_mask && high_mask && canny_ws && cc_ws && comp,
-                SHG_E_WORKSPACE, "shg_stage_limb_points: workspace too small");
-    SHG_REQUIRE(h_packed && h_comp, SHG_E_WORKSPACE, "shg_stage_limb_points: pinned staging area too small");
-    Staging stg;
-    STAGE_TRY(map_staging(host_pinned, &stg, "shg_stage_limb_points"));
-
-    STAGE_TRY(shg_downscale_mean_u16(disk, h, w, pitch, kFactor, small, stream));
-    // np.median(blur 5x5) (:241) and np.percentile(blurred, 99) (:165): their order statistics
-    int64_t ranks[4];
-    double gamma99;
-    ranks[0] = (n & 1) ? n / 2 : n / 2 - 1;
-    ranks[1] = n / 2;
-    STAGE_TRY(shg_host_percentile_plan(n, 99.0, &ranks[2], &ranks[3], &gamma99));
-    if (k <= 63) {
-        // the block means are whole numbers of 2^-20: select on the integer window sums (three passes instead of eight)
-        STAGE_TRY(shg_box_blur_key_f64(small, sh, sw, k, blurred, keys_k, tmp, stream));
-        if (k == 5) {                                    // 2000-2399 slit rows: cv2.blur(img, (k, k)) is the 5 x 5 blur itself
-            blur5 = blurred;
-            keys_5 = keys_k;
-        } else {
-            STAGE_TRY(shg_box_blur_key_f64(small, sh, sw, 5, blur5, keys_5, tmp, stream));
-        }
-        const uint32_t* karr[4] = {keys_5, keys_5, keys_k, keys_k};
-        const int kk[4] = {5, 5, k, k};
-        STAGE_TRY(shg_select_keys_u32(karr, n, ranks, kk, 4, packed, sel_ws, sel_bytes, stream));
-    } else {
-        STAGE_TRY(shg_box_blur_f64(small, sh, sw, k, blurred, tmp, stream));
-        STAGE_TRY(shg_box_blur_f64(small, sh, sw, 5, blur5, tmp, stream));      // (k > 63 here, never 5)
-        const double* arrays[4] = {blur5, blur5, blurred, blurred};
-        STAGE_TRY(shg_select_multi_f64(arrays, n, ranks, 4, packed, sel_ws, sel_bytes, stream));
-    }
-    STAGE_TRY(shg_flood_stats_lerp_f64(small, blurred, n, packed + 2, gamma99, packed + 4, counts, flood_ws, stream));
-    STAGE_TRY(move_words(stg.on_device(h_packed), packed, 8 * 8 + 20 * 4, st));
-    STAGE_SYNC(st, "shg_stage_limb_points");
-    const double median5 = (n & 1) ? h_packed[0] : (h_packed[0] + h_packed[1]) / 2;
-    const double low = median5 / 10, high = low * 1.5;                                       // :241-243
-    int64_t counts64[20];
-    const uint32_t* hc = reinterpret_cast<const uint32_t*>(h_packed + 8);
-    for (int i = 0; i < 20; ++i) counts64[i] = hc[i];
-    double thresh3;
-    STAGE_TRY(shg_host_flood_threshold(h_packed[4], sh, sw, h_packed[5], h_packed[6], counts64, &thresh3));
-
-    int64_t m = 0;
-    const double* taps = host_gauss_taps;
-    for (int rung = 0;; ++rung) {                                                             // sigma = 2, 1.5, 1, 0.5
-        if (rung == 4) { shg::set_error("ellipse fit: could not find any edges of the solar disk"); return SHG_E_RUNTIME; }
-        const double sigma = 2.0 - 0.5 * rung;
-        const int radius = (int)(4.0 * sigma + 0.5);
-        STAGE_TRY(shg_canny_masks_f64(blurred, sh, sw, thresh3, taps, radius, low, high, low_mask, high_mask, canny_ws, canny_bytes, stream));
-        STAGE_TRY(shg_edge_components(low_mask, high_mask, sh, sw, comp + 1, comp + 1 + n, comp, cc_ws, cc_bytes, stream));
-        k_edge_list<<<16, 256, 0, st>>>(comp, n, stg.on_device(h_comp));                      // the device knows how many: one trip
-        STAGE_TRY(shg::check_launch("k_edge_list"));
-        STAGE_SYNC(st, "shg_stage_limb_points");
-        m = h_comp[0];
-        SHG_REQUIRE(m >= 0 && m <= n, SHG_E_RUNTIME, "shg_stage_limb_points: %lld edge pixels in an image of %lld", (long long)m, (long long)n);
-        if (m > 0) break;
-        taps += 2 * radius + 1;                                                               // try again with less blur (:254-256)
-    }
-    const int32_t* idx = h_comp + 1;
-    const int32_t* root = h_comp + 1 + n;
-    SHG_REQUIRE(points_cap >= m, SHG_E_WORKSPACE, "shg_stage_limb_points: %lld edge pixels, room for %lld", (long long)m, (long long)points_cap);
-    int64_t n_sel = 0;
-    STAGE_TRY(shg_host_limb_points(idx, root, m, sh, sw, host_flags, &n_sel));
-    for (int64_t i = 0; i < m; ++i) {
-        host_points[2 * i] = idx[i] / (int32_t)sw;
-        host_points[2 * i + 1] = idx[i] % (int32_t)sw;
-    }
-    host_counts2[0] = m;
-    host_counts2[1] = n_sel;
-    return 0;
+    if (limb_fused(im.sh, im.sw, im.k))
+        return limb_points_with(FusedLimb(im), im, host_gauss_taps, host_points, host_flags, points_cap, host_counts2, workspace, workspace_bytes,
+                                host_pinned, host_pinned_bytes, stream);
+    return limb_points_with(SeparateLimb(im), im, host_gauss_taps, host_points, host_flags, points_cap, host_counts2, workspace, workspace_bytes,
+                            host_pinned, host_pinned_bytes, stream);
 }
 
 // ellipse_to_circle without its warp (ellipse_to_circle.py:294-314): shg_stage_limb_points, then the two-step ellipse

@@ -24,14 +24,8 @@ namespace {
 constexpr int MAXN = SHG_TRANSV_MAX_COLS;   // 19456 keys = 152 KiB of the CU's 160 KiB LDS (plus the static scratch)
 constexpr int NT = 256;
 
-__device__ __forceinline__ uint64_t f64_key(double v) {          // monotone map double -> uint64 (no NaN)
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_f64(uint64_t k) {
-    const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
+using shg::f64_key;
+using shg::key_f64;
 
 constexpr int NB = 512;          // buckets of the bucket select (= the radix select's two 256-bin histograms)
 constexpr int CAP = 128;         // candidates ranked directly

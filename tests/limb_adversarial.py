@@ -108,7 +108,7 @@ def thresholds(reference_magnitude, local_maxima):
 
 def _hypot_glibc(x, y):
     """glibc 2.35's hypot (sysdeps/ieee754/dbl-64/e_hypot.c, the kernel without FMA) for finite inputs in the normal range,
-    in Python floats: what csrc/limb.hip and csrc/limb_fused.hip evaluate."""
+    in Python floats: what both limb chains evaluate (csrc/limb_math.h: hypot_glibc)."""
     x, y = abs(x), abs(y)
     ax, ay = (y, x) if x < y else (x, y)
     if ax >= ay / 2.0 ** -54:
@@ -134,6 +134,18 @@ def gradients(image, sigma):
         return ndi.gaussian_filter(x, sigma, mode='constant', cval=0, truncate=4.0)
     smoothed = fsmooth(np.array(image, dtype=float)) / (fsmooth(np.ones(image.shape)) + np.finfo(float).eps)
     return ndi.sobel(smoothed, axis=0), ndi.sobel(smoothed, axis=1)
+
+
+@functools.lru_cache(maxsize=None)
+def gradient_pairs():
+    """Every distinct (isobel, jsobel) of every scene, shape and sigma -> float64 [n, 2] (read-only)."""
+    pairs = []
+    for shape in SHAPES:
+        for scene in scenes(*shape).values():
+            for sigma in SIGMAS:
+                isobel, jsobel = gradients(flooded(scene), sigma)
+                pairs.append(np.unique(np.stack([isobel.ravel(), jsobel.ravel()], axis=1), axis=0))
+    return _frozen(np.unique(np.concatenate(pairs), axis=0))
 
 
 def suppression_census(image, sigma):

@@ -508,6 +508,76 @@ def test_fast_log_stays_below_one_ulp(tmp_path):
     assert ratio < 1.0 and ratio_differs < 1e-4, (ratio, ratio_differs)
 
 
+def test_limb_math_header_on_the_cpu(tmp_path):
+    """csrc/limb_math.h (with f64_key / key_f64 / np_lerp of csrc/shg_common.h) compiled with the host compiler
+    (tests/c_abi/limb_math_check.cpp): the text both limb chains include gives, on the CPU,
+      * hypot_glibc == np.hypot on every gradient pair test_host_hypot_is_the_kernels_hypot uses;
+      * np_lerp == order_stats.lerp_order_stats' combine, for weights on both sides of 0.5;
+      * key_f64(f64_key(x)) == x bit for bit and key order == value order, over signed zeros, subnormals and infinities;
+      * refl == SciPy's 'reflect' at -1, 0, n - 1, n;
+      * the 20-bin histogram's edges and the bin of every edge value == np.histogram's, the first == last case included."""
+    import shutil
+    import subprocess
+    from tests import limb_adversarial as adv
+    gxx = shutil.which('g++')
+    if gxx is None:
+        pytest.skip('no g++')
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / 'limb_math_check')
+    subprocess.run([gxx, '-O2', '-ffp-contract=off', '-I', os.path.join(here, '..', 'solex_ser_recon_en_amd', 'csrc'),
+                    os.path.join(here, 'c_abi', 'limb_math_check.cpp'), '-o', exe], check=True)
+
+    def run(what, values, dtype=np.float64):
+        src, dst = str(tmp_path / (what + '.in')), str(tmp_path / (what + '.out'))
+        np.ascontiguousarray(values, dtype=np.float64).tofile(src)
+        subprocess.run([exe, what, src, dst], check=True)
+        return np.fromfile(dst, dtype=dtype)
+
+    pairs = adv.gradient_pairs()
+    assert len(pairs) > 100000
+    got = run('hypot', pairs)
+    bad = np.flatnonzero(got != np.hypot(pairs[:, 0], pairs[:, 1]))
+    assert bad.size == 0, [(pairs[i, 0], pairs[i, 1], got[i]) for i in bad[:5]]
+
+    rng = np.random.default_rng(5)
+    cases = []
+    for n, q in [(250000, 99), (4000000, 99.9999), (4000000, 10), (7, 50), (1001, 12.5), (640, 85)]:
+        gamma = order_stats.lerp_gamma(n, q)
+        for a, b in np.sort(rng.random((4, 2)) * 10.0 ** rng.integers(-3, 4, (4, 1)), axis=1):
+            cases.append((a, b, gamma, order_stats.lerp_order_stats(n, q)[2](a, b)))
+    cases = np.array(cases)
+    assert (cases[:, 2] >= 0.5).any() and ((cases[:, 2] > 0) & (cases[:, 2] < 0.5)).any()
+    np.testing.assert_array_equal(run('lerp', cases[:, :3]), cases[:, 3])
+
+    tiny = np.finfo(np.float64).tiny
+    x = np.array([-np.inf, -1e308, -1.5, -tiny, -tiny / 2, -5e-324, -0.0, 0.0, 5e-324, tiny / 2, tiny, 1.0, np.nextafter(1.0, 2.0), 1e308, np.inf])
+    x = np.concatenate([x, rng.standard_normal(1000) * 10.0 ** rng.integers(-300, 300, 1000)])
+    words = run('keys', x, np.uint64).reshape(-1, 2)
+    np.testing.assert_array_equal(words[:, 1], x.view(np.uint64))                 # the round trip, -0.0 and +0.0 apart
+    order = np.argsort(words[:, 0], kind='stable')
+    assert np.all(np.diff(x[order]) >= 0) and len(np.unique(words[:, 0])) == len(np.unique(x.view(np.uint64)))
+    zeros = words[np.flatnonzero(x == 0), 0]
+    assert zeros[0] < zeros[1]                                                     # -0.0 below +0.0
+
+    for n in (1, 2, 3, 64):
+        want = np.pad(np.arange(n), 1, mode='symmetric')[[0, 1, n, n + 1]]        # SciPy 'reflect' = NumPy 'symmetric': a | a b c | c
+        np.testing.assert_array_equal(run('refl', [(-1, n), (0, n), (n - 1, n), (n, n)]), want)
+
+    for mn, mx in [(0.0, 1.0), (0.0123, 0.7391), (3.0517578125e-05, 0.4999847412109375), (0.25, 0.25), (0.0, 0.0)]:
+        data = np.array([mn, mx])
+        ends, edges = np.histogram(data, 20)
+        inside = np.concatenate([edges, np.nextafter(edges, -np.inf)[1:], np.nextafter(edges, np.inf)[:-1]])
+        inside = inside[(inside >= mn) & (inside <= mx)] if mn < mx else np.array([mn])
+        out = run('hist', np.concatenate([[mn, mx], inside]))
+        np.testing.assert_array_equal(out[:21], edges)
+        # (np.histogram needs min and max in the data to keep these edges: count one value at a time beside them)
+        for v, b in zip(inside, out[21:]):
+            counts, e2 = np.histogram(np.array([mn, mx, v]), 20)
+            np.testing.assert_array_equal(e2, edges)
+            counts -= ends
+            assert counts[int(b)] == 1 and counts.sum() == 1, (mn, mx, v, b)
+
+
 def test_ellipse_fit_agrees_with_scikit_images_independent_implementation(golden):
     """lsq-ellipse (the reference's `from ellipse import LsqEllipse`, ellipse_to_circle.py:53-59) is absent from /root/reference
     and from this image, so the fit is a restatement of Halir & Flusser's direct least squares -- which nothing but itself pinned.

@@ -670,22 +670,32 @@ def test_canny_masks_match_skimage_0_18_3(ops, orc, golden):
     np.testing.assert_array_equal(host(high_m).astype(bool), want_high)
 
 
-def test_limb_points_stage_matches_oracle(ops, golden):
+@pytest.mark.parametrize('shape', [None, (6796, 203, 9), (6800, 200, 8), (25600, 800, 7)],
+                         ids=['synth', 'k16_widest_fused_window', 'k17_separate_chain_integer_keys', 'k64_separate_chain_float64_select'])
+def test_limb_points_stage_matches_oracle(ops, golden, shape):
     """shg_stage_limb_points (block mean -> flood image -> canny -> labelling -> region / hull / row selection) on a
-    uint16 disk against the oracle's get_edge_list on the same block mean."""
+    uint16 disk against the oracle's get_edge_list on the same block mean.  Beside the synthetic scan, three _limb_disk
+    images (h, w, seed) at the smallest heights where the stage changes back end (blur window k = int(ceil(h / 4) * 0.01)):
+    k = 16, the widest window the fused chain takes, sides no multiples of 4; k = 17, the first that falls back to the separate
+    chain (integer keys); k = 64, the first whose window sums do not fit 32 bits (the float64 select)."""
     from oracle import limb_oracle as limb
     from solex_ser_recon_en_amd import stages, synth
-    rng = np.random.default_rng(3)
-    frames = synth.synth_frames_numpy(900, 820, 24, 16, seed=2)
-    disk = np.ascontiguousarray(frames[:, 12, :].T)                      # [820 rows, 900 columns]: a limb-darkened disk on sky
-    disk = np.clip(disk.astype(np.int64) + rng.integers(-40, 40, disk.shape), 0, 65535).astype(np.uint16)
+    if shape is None:
+        rng = np.random.default_rng(3)
+        frames = synth.synth_frames_numpy(900, 820, 24, 16, seed=2)
+        disk = np.ascontiguousarray(frames[:, 12, :].T)                  # [820 rows, 900 columns]: a limb-darkened disk on sky
+        disk = np.clip(disk.astype(np.int64) + rng.integers(-40, 40, disk.shape), 0, 65535).astype(np.uint16)
+    else:
+        disk = _limb_disk(*shape)
     X, raw = stages.limb_points(dev(disk))
     small = limb.downscale_local_mean(disk / 65536, 4)
     Xo, rawo = limb.get_edge_list(small.copy())
+    assert len(Xo) > 0
     np.testing.assert_array_equal(X, Xo * 4)
     np.testing.assert_array_equal(raw, rawo * 4)
-    with pytest.raises(RuntimeError, match='at least 400 slit rows'):
-        stages.limb_points(dev(disk[:300]))
+    if shape is None:
+        with pytest.raises(RuntimeError, match='at least 400 slit rows'):
+            stages.limb_points(dev(disk[:300]))
 
 
 @pytest.mark.parametrize('h,w,k', [(203, 230, 2), (500, 525, 5), (97, 131, 7), (640, 1000, 6), (30, 40, 63)])

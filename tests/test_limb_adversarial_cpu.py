@@ -86,15 +86,9 @@ def test_labelling_scenes_have_many_components_and_long_ones():
 
 
 def test_host_hypot_is_the_kernels_hypot():
-    """np.hypot on this host == the glibc 2.35 algorithm the kernels evaluate (csrc/limb.hip: hypot_glibc), on every
+    """np.hypot on this host == the glibc 2.35 algorithm the kernels evaluate (csrc/limb_math.h: hypot_glibc), on every
     gradient pair of every scene: a host whose libm differs shows up here, and not as a mask that differs on the GPU."""
-    pairs = []
-    for shape in adv.SHAPES:
-        for scene in adv.scenes(*shape).values():
-            for sigma in adv.SIGMAS:
-                isobel, jsobel = adv.gradients(adv.flooded(scene), sigma)
-                pairs.append(np.unique(np.stack([isobel.ravel(), jsobel.ravel()], axis=1), axis=0))
-    pairs = np.unique(np.concatenate(pairs), axis=0)
+    pairs = adv.gradient_pairs()
     print('HYPOT %d distinct gradient pairs' % len(pairs))
     assert len(pairs) > 100000
     got = np.hypot(pairs[:, 0], pairs[:, 1])
