@@ -391,6 +391,46 @@ int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_
 int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w, int S,
                       const double* circle3, uint64_t* ssd, shg_stream_t stream);
 
+/* ---- sharpening a disk: the undecimated B3-spline ("a trous") wavelet layers of a 16-bit image, one gain a layer and a soft
+ * noise gate a layer (not a reference stage; tests/sharpen_ref.py restates all of it in NumPy, bit for bit).  Everything is an
+ * integer: the result depends neither on the launch grid, nor on how levels are fused, nor on the order of anything.
+ * The reflection R(i, n), whole-sample symmetric and repeated (NumPy's 'reflect'): 0 when n = 1; else with p = 2 (n - 1),
+ *   i <- i mod p (non-negative), and R = i when i < n, p - i otherwise.  An image narrower than twice a hole reflects more than once.
+ * The decomposition into 1 <= levels = L <= 6 layers, in Q6 fixed point:
+ *   c_0[r][c] = 64 * img[r][c]                                                   (below 2^22);
+ *   for j = 1 .. L, with the hole d = 2^(j - 1) and K = (1, 4, 6, 4, 1):
+ *     S[r][c] = sum over k, l = 0 .. 4 of K[k] * K[l] * c_(j-1)[R(r + (k - 2) d, h)][R(c + (l - 2) d, w)]
+ *               (below 2^30: an image of all 65535 gives 1 073 725 440; exact however it is split into a row and a column pass,
+ *               nothing is rounded between the two);
+ *     c_j = (S + 128) >> 8;      w_j = c_(j-1) - c_j   (int32, |w_j| < 2^22).
+ *   c_0 = w_1 + ... + w_L + c_L exactly.
+ * The recombination.  host_gain_q8[j - 1] in [0, 4096] is the gain of layer j, 256 standing for 1; host_threshold_q6[j - 1] in
+ * [0, 2^22] is its gate, in the units of w_j (64 a count):
+ *   s_j = sign(w_j) * max(|w_j| - threshold_j, 0)                                (the soft threshold; a threshold of 0 is the identity);
+ *   acc = 256 * c_L + sum over j of gain_j * s_j                                 (int64, |acc| < 2^37);
+ *   out[r * out_pitch + c] = (uint16)clip((acc + 8192) >> 14, 0, 65535)          (the shift is arithmetic: a floor towards -infinity).
+ *   Every gain 256 and every threshold 0 give out = img.
+ * shg_wavelet_sharpen_u16: planes is NULL or device int32 memory of [L + 1][h][w] (dense): w_1 .. w_L, then c_L.  Without planes no
+ *   wavelet plane reaches memory: only what the launches hand each other -- c_3 and its successors and acc, beyond three levels --
+ *   goes through the workspace.  workspace: shg_wavelet_workspace_bytes(h, w, levels), which is 0 for arguments out of range and
+ *   needs no GPU.
+ * shg_wavelet_noise_u16: the pixel set is every pixel ON THE DISK by the test of the flatten section above (circle3 on the host, the
+ *   radius already multiplied by the caller's region; NULL or (-1, -1, -1): every pixel).  With n the size of the set,
+ *   out2[0] = the lower median of |w_1| over the set -- the (n - 1) / 2-th smallest, 0-based, an exact integer in Q6 --, out2[1] = n;
+ *   n = 0 gives 0 and 0.  out2 is device memory of two uint64.  An exact two-level radix select over the 22-bit values (high 11
+ *   bits, then low 11 bits) in the manner of shg_ring_medians_u16: integer counts only, and the call includes its own clearing pass.
+ *   workspace: at least shg_wavelet_workspace_bytes(h, w, 1) (the query for any level count is enough).
+ * 1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG for a null pointer (planes excepted), a pitch below the width, levels outside
+ * [1, 6], a gain or threshold out of range, a circle that is not finite, a workspace that is too small, and an out or planes that
+ * overlaps img or the other (a stencil cannot run in place).  On any error nothing is written.  No call allocates, waits for the
+ * device or copies from it.  Elements between w and a pitch are never touched. */
+size_t shg_wavelet_workspace_bytes(int64_t h, int64_t w, int levels);
+int shg_wavelet_sharpen_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, int levels, const int32_t* host_gain_q8,
+                            const int32_t* host_threshold_q6, uint16_t* out, int64_t out_pitch, int32_t* planes, void* workspace,
+                            size_t workspace_bytes, shg_stream_t stream);
+int shg_wavelet_noise_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, uint64_t* out2,
+                          void* workspace, size_t workspace_bytes, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

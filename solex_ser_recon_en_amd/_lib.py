@@ -106,6 +106,9 @@ SIGNATURES = {
     'shg_ring_flatten_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
     'shg_stack_combine_u16': (c_int, [P, P, P, c_int, c_int, c_double, c_int, P, c_int64, c_int64, c_int64, P, c_int64, P]),
     'shg_shift_ssd_u16': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, c_int, P, P, P]),
+    'shg_wavelet_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int]),
+    'shg_wavelet_sharpen_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, P, P, P, c_int64, P, P, c_size_t, P]),
+    'shg_wavelet_noise_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, c_size_t, P]),
     'shg_blur_fits_fused': (c_int, [c_int64, c_int]),
     'shg_blur_row_mean_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, P, P]),
     'shg_blur_argmin_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int64, c_int64, P, P, P]),

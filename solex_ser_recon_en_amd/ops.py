@@ -1085,3 +1085,51 @@ def shift_ssd_u16(ref, img, search, circle=None, out=None):
         raise ValueError('out must be a contiguous int64 [%d] tensor' % words)
     _lib.check(lib.shg_shift_ssd_u16(rptr, rpitch, iptr, ipitch, h, w, s, _host_ptr(c3), out.data_ptr(), _stream()), 'shg_shift_ssd_u16')
     return out
+
+
+# ---- sharpening a disk: the a-trous wavelet layers with gains and gates, and the noise they are gated by ----
+def wavelet_sharpen_u16(img, gain_q8, threshold_q6=None, out=None, want_planes=False, workspace=None):
+    """shg_wavelet_sharpen_u16: the uint16 image split into L = len(gain_q8) B3-spline a-trous layers (1 to 6) and put together again,
+    layer j times gain_q8[j] / 256 (integers in [0, 4096]) after a soft threshold of threshold_q6[j] (integers in [0, 2^22], 64 a
+    count; None: zeros) -> (out uint16 [h, w], planes int32 [L + 1, h, w] or None: w_1 .. w_L, then c_L).  out: the caller's view,
+    which must not overlap the image.  workspace: the caller's uint8 tensor of at least wavelet_workspace_bytes(h, w, L)."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    g = np.ascontiguousarray(gain_q8, dtype=np.int64).reshape(-1)
+    levels = int(g.size)
+    t = np.zeros(levels, np.int64) if threshold_q6 is None else np.ascontiguousarray(threshold_q6, dtype=np.int64).reshape(-1)
+    if not 1 <= levels <= 6 or t.size != levels:
+        raise ValueError('1 to 6 gains and as many thresholds, got %d and %d' % (levels, t.size))
+    if g.min() < 0 or g.max() > 4096 or t.min() < 0 or t.max() > 1 << 22:
+        raise ValueError('gain_q8 lies in [0, 4096] and threshold_q6 in [0, 2^22]')
+    g, t = g.astype(np.int32), t.astype(np.int32)
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.uint16, device=img.device)
+    optr, oh, ow, opitch = _img(out, 'out', torch.uint16)
+    if (oh, ow) != (h, w):
+        raise ValueError('out must be a uint16 [%d, %d] view' % (h, w))
+    planes = torch.empty((levels + 1, h, w), dtype=torch.int32, device=img.device) if want_planes else None
+    need = lib.shg_wavelet_workspace_bytes(h, w, levels)
+    ws = torch.empty(need, dtype=torch.uint8, device=img.device) if workspace is None else _dev(workspace, 'workspace')
+    _lib.check(lib.shg_wavelet_sharpen_u16(ptr, h, w, pitch, levels, _host_ptr(g), _host_ptr(t), optr, opitch,
+                                           None if planes is None else planes.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                           _stream()), 'shg_wavelet_sharpen_u16')
+    return out, planes
+
+
+def wavelet_noise_u16(img, circle=None, out=None, workspace=None):
+    """shg_wavelet_noise_u16: over the pixels of the uint16 image on the disk `circle` (cx, cy, r; None or (-1, -1, -1): every
+    pixel) -> int64 [2] on the image's device: the lower median of |w_1|, the finest wavelet layer, in Q6 (64 a count), and the
+    number of pixels (0 and 0 for an empty set).  out: the caller's, overwritten."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    if c3 is not None and c3.size != 3:
+        raise ValueError('circle is (cx, cy, r)')
+    if out is None:
+        out = torch.empty(2, dtype=torch.int64, device=img.device)
+    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (2,) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int64 [2] tensor')
+    need = lib.shg_wavelet_workspace_bytes(h, w, 1)
+    ws = torch.empty(need, dtype=torch.uint8, device=img.device) if workspace is None else _dev(workspace, 'workspace')
+    _lib.check(lib.shg_wavelet_noise_u16(ptr, h, w, pitch, _host_ptr(c3), out.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                         _stream()), 'shg_wavelet_noise_u16')
+    return out
