@@ -501,6 +501,15 @@ int shg_warp_rows_minmax_u16(const uint16_t* src, int64_t h, int64_t w, int64_t 
                              uint16_t* dst, int64_t out_h, int64_t out_w, int64_t dst_pitch,
                              const uint32_t* minmax2, shg_stream_t stream);
 
+/* Which kernel the two entry points above take for this image: 1 where the eight-pixels-a-lane k_warp_rows8 serves it (both
+ * pitches multiples of 8, both images 16-byte aligned, at least 8 source columns and two 8-column vectors of output, 32-bit
+ * offsets, 0 <= h00 <= 1.75, h01 and h02 below 1e300), 0 where k_warp_rows does.  A pure host function: the pointers are only
+ * looked at as numbers, no GPU is touched.  (SHG_WARP_WIDE=0 in the environment sends every image to k_warp_rows whatever this
+ * says: the A / B switch is the launcher's.)  A stack goes wide when every one of its disks fits. */
+int shg_warp_rows_wide_fits(const uint16_t* src, int64_t h, int64_t w, int64_t src_pitch,
+                            double h00, double h01, double h02,
+                            const uint16_t* dst, int64_t out_h, int64_t out_w, int64_t dst_pitch);
+
 /* ---- transversalium ---------------------------- solex_util.py:383-395, 76-86
  * Per row y in (y1, y2): the mean of the 2-MAD inliers of log(img[y][a:b] / img[y-1][a:b])
  * with a, b the chord of `circle` clipped to `borders` (float64).  out[y2 - y1]
@@ -531,6 +540,9 @@ int shg_correlate1d_rows_f64(const double* src, int64_t k, int64_t n, const doub
 /* ret = min(img * c[y], 65535) truncated to uint16 (solex_util.py:489, 515-516). */
 int shg_scale_rows_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* c,
                        const double* row_factor, uint16_t* dst, int64_t dst_pitch, shg_stream_t stream);
+/* 1 where shg_scale_rows_u16 takes k_scale_rows8 for this image (16-byte loads and stores: both images 16-byte aligned, both
+ * pitches multiples of 8), 0 where it takes k_scale_rows.  A pure host function, as shg_warp_rows_wide_fits. */
+int shg_scale_rows_vec_fits(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const uint16_t* dst, int64_t dst_pitch);
 
 /* ---- f4: "stubborn" transversalium, the line filter of apply_lin_filter + fix_edge_effect ----
  * Replaces the three cv2.filter2D calls on log(img) (solex_util.py:277-353) and the limb clean-up
@@ -695,6 +707,12 @@ int shg_contrast_products_u16(const uint16_t* frame, int64_t frame_pitch, const 
                               int64_t h, int64_t w, const double* lo_hi6, uint16_t* high_contrast,
                               uint16_t* protus, uint16_t* cc, int64_t dst_pitch, int64_t disc_x0,
                               int64_t disc_y0, int64_t disc_r, shg_stream_t stream);
+/* 1 where shg_contrast_products_u16 takes k_products8 for these five images (all 16-byte aligned, the three pitches multiples
+ * of 8, at least 9 columns -- two vectors a row --, 32-bit offsets), 0 where it takes k_products.  A pure host function, as
+ * shg_warp_rows_wide_fits. */
+int shg_contrast_products_vec_fits(const uint16_t* frame, int64_t frame_pitch, const uint16_t* cl1, int64_t cl1_pitch,
+                                   int64_t h, int64_t w, const uint16_t* high_contrast, const uint16_t* protus,
+                                   const uint16_t* cc, int64_t dst_pitch);
 
 /* ---- the limb stage's kernels fused through LDS tiles ------ ellipse_to_circle.py:148-291, 299-302 (csrc/limb_fused.hip)
  * The same arithmetic as shg_downscale_mean_u16 / shg_box_blur_key_f64 / shg_select_keys_u32 / shg_flood_stats_lerp_f64 and

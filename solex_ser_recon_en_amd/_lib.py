@@ -123,10 +123,12 @@ SIGNATURES = {
                                          c_int64, P, P]),
     'shg_warp_rows_u16': (c_int, [P, c_int64, c_int64, c_int64, c_double, c_double, c_double, P, c_int64, c_int64,
                                   c_int64, P, P]),
+    'shg_warp_rows_wide_fits': (c_int, [P, c_int64, c_int64, c_int64, c_double, c_double, c_double, P, c_int64, c_int64, c_int64]),
     'shg_rowpair_logratio_stats': (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_int64, P, P, P, P, P]),
     'shg_rowpair_logratio_stats_mirrored': (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_int64, P, P, P, P, P, P]),
     'shg_line_order_stats_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, P, P, P]),
     'shg_scale_rows_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, c_int64, P]),
+    'shg_scale_rows_vec_fits': (c_int, [P, c_int64, c_int64, c_int64, P, c_int64]),
     'shg_correlate1d_rows_f64': (c_int, [P, c_int64, c_int64, P, c_int, c_int, P, P]),
     'shg_lin_filter_row_sums': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P, P, c_int, P, P, P]),
     'shg_lin_filter_apply': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, c_int, c_int, P, P, P, P, c_int, P, c_int64, P]),
@@ -144,6 +146,7 @@ SIGNATURES = {
     'shg_contrast_stats_workspace_bytes_for': (c_size_t, [c_int64, c_int64, c_int]),
     'shg_contrast_stats_u16': (c_int, [P, c_int64, c_int64, c_int64, c_double, c_int, P, c_int64, P, P, P, P, c_size_t, P]),
     'shg_contrast_products_u16': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
+    'shg_contrast_products_vec_fits': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, P, P, c_int64]),
     'shg_fill_disc_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_uint16, P, P]),
     'shg_downscale_mean_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, P, P]),
     'shg_box_blur_f64': (c_int, [P, c_int64, c_int64, c_int, P, P, P]),

@@ -399,6 +399,20 @@ extern "C" int shg_contrast_products_u16(const uint16_t* frame, int64_t frame_pi
                                         disc_y0, disc_r, stream);
 }
 
+// Whether k_products8 serves these five images: 16-byte loads and stores (aligned images, pitches in whole vectors), and the vector
+// kernel's 32-bit offsets and multiply-high: every image below 4 GiB, pitches in 24 bits, at least two vectors a row.  The one
+// statement of the gate: the launcher below asks it for every disk.
+extern "C" int shg_contrast_products_vec_fits(const uint16_t* frame, int64_t frame_pitch, const uint16_t* cl1, int64_t cl1_pitch, int64_t h,
+                                              int64_t w, const uint16_t* high_contrast, const uint16_t* protus, const uint16_t* cc,
+                                              int64_t dst_pitch) {
+    if (h <= 0 || w <= 0 || frame_pitch < w || cl1_pitch < w || dst_pitch < w || h >= 65536) return 0;      // (nothing the launcher takes)
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(frame) | reinterpret_cast<uintptr_t>(cl1) | reinterpret_cast<uintptr_t>(high_contrast) |
+                           reinterpret_cast<uintptr_t>(protus) | reinterpret_cast<uintptr_t>(cc);
+    const int64_t widest = std::max(frame_pitch, std::max(cl1_pitch, dst_pitch));
+    return (ptrs & 15) == 0 && frame_pitch % 8 == 0 && cl1_pitch % 8 == 0 && dst_pitch % 8 == 0 && w >= 9 && w < (1ll << 30) &&
+           widest < (1ll << 24) && h * widest < (1ll << 31) && ((w + 7) / 8) * h < (1ll << 31);
+}
+
 // k disks of one shape in one launch (per kProductsBatch): host_lo_hi6 is [k][6] -- or NULL, and the bounds are formed on the
 // device from stats5 [k][5] (device; the order statistics shg_contrast_stats_u16 leaves) with the _lerp weights g_bright /
 // g_dark; mirror5 (may be NULL, e.g. GPU-mapped host memory): where the kernel also leaves those statistics for the host.
@@ -410,21 +424,16 @@ int shg::contrast_products_batch(const uint16_t* const* host_frames, int64_t fra
     SHG_REQUIRE(h > 0 && w > 0 && frame_pitch >= w && cl1_pitch >= w && dst_pitch >= w, SHG_E_ARG, "shg_contrast_products_u16: bad image size");
     SHG_REQUIRE(h < 65536, SHG_E_UNSUPPORTED, "shg_contrast_products_u16: more than 65535 rows");
     SHG_REQUIRE(disc_r < 32768, SHG_E_UNSUPPORTED, "shg_contrast_products_u16: radius %lld out of range", (long long)disc_r);
-    uintptr_t ptrs = 0;
+    bool vec = true;                                     // (every disk of the call has to fit: one kernel serves them all)
     for (int64_t d = 0; d < k; ++d) {
         SHG_REQUIRE(host_frames[d] && host_cl1[d] && host_hc[d] && host_protus[d] && host_cc[d], SHG_E_ARG, "shg_contrast_products_u16: null image");
-        ptrs |= reinterpret_cast<uintptr_t>(host_frames[d]) | reinterpret_cast<uintptr_t>(host_cl1[d]) | reinterpret_cast<uintptr_t>(host_hc[d]) |
-                reinterpret_cast<uintptr_t>(host_protus[d]) | reinterpret_cast<uintptr_t>(host_cc[d]);
+        vec = vec && shg_contrast_products_vec_fits(host_frames[d], frame_pitch, host_cl1[d], cl1_pitch, h, w, host_hc[d], host_protus[d], host_cc[d], dst_pitch) != 0;
         for (int i = 0; i < 3 && host_lo_hi6; ++i) {
             const double lo = host_lo_hi6[6 * d + 2 * i], hi = host_lo_hi6[6 * d + 2 * i + 1];
             SHG_REQUIRE(65535.0 >= hi && hi > lo, SHG_E_ARG, "shg_contrast_products_u16: need sat >= hi > lo (got lo=%g hi=%g)", lo, hi);   // assert, solex_util.py:521
         }
     }
     hipStream_t st = shg::as_stream(stream);
-    // (the vector kernel's 32-bit offsets and multiply-high: every image below 4 GiB, pitches in 24 bits, at least two vectors a row)
-    const bool vec = (ptrs & 15) == 0 && frame_pitch % 8 == 0 && cl1_pitch % 8 == 0 && dst_pitch % 8 == 0 && w >= 9 && w < (1ll << 30) &&
-                     std::max(frame_pitch, std::max(cl1_pitch, dst_pitch)) < (1ll << 24) && h * std::max(frame_pitch, std::max(cl1_pitch, dst_pitch)) < (1ll << 31) &&
-                     ((w + 7) / 8) * h < (1ll << 31);
     SHG_PROF("products", st);
     for (int64_t i0 = 0; i0 < k; i0 += kProductsBatch) {
         const int m = (int)std::min<int64_t>(kProductsBatch, k - i0);

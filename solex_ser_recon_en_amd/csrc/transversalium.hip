@@ -797,6 +797,13 @@ extern "C" int shg_scale_rows_u16(const uint16_t* img, int64_t h, int64_t w, int
     return shg::scale_rows_batch(&img, 1, h, w, pitch, c, row_factor, &dst, dst_pitch, stream);
 }
 
+// Whether k_scale_rows8 serves this image: 16-byte loads and stores need aligned images and pitches in whole vectors (a row's last,
+// partial vector goes pixel by pixel: any width).  The one statement of the gate: the launcher below asks it for every image.
+extern "C" int shg_scale_rows_vec_fits(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const uint16_t* dst, int64_t dst_pitch) {
+    if (h <= 0 || w <= 0 || pitch < w || dst_pitch < w || h >= 65536) return 0;                              // (nothing the launcher takes)
+    return ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && pitch % 8 == 0 && dst_pitch % 8 == 0;
+}
+
 // k images in one launch: c is [k][h] (row_factor, if given, applies to all of them)
 int shg::scale_rows_batch(const uint16_t* const* host_imgs, int64_t k, int64_t h, int64_t w, int64_t pitch, const double* c,
                           const double* row_factor, uint16_t* const* host_dsts, int64_t dst_pitch, shg_stream_t stream) {
@@ -804,12 +811,11 @@ int shg::scale_rows_batch(const uint16_t* const* host_imgs, int64_t k, int64_t h
     SHG_REQUIRE(h > 0 && w > 0 && pitch >= w && dst_pitch >= w, SHG_E_ARG, "shg_scale_rows_u16: bad image size");
     SHG_REQUIRE(h < 65536, SHG_E_UNSUPPORTED, "shg_scale_rows_u16: more than 65535 rows");
     hipStream_t st = shg::as_stream(stream);
-    uintptr_t bits = 0;
+    bool vec = true;                                     // (every image of the call has to fit: one kernel serves them all)
     for (int64_t i = 0; i < k; ++i) {
         SHG_REQUIRE(host_imgs[i] && host_dsts[i], SHG_E_ARG, "shg_scale_rows_u16: null image");
-        bits |= reinterpret_cast<uintptr_t>(host_imgs[i]) | reinterpret_cast<uintptr_t>(host_dsts[i]);
+        vec = vec && shg_scale_rows_vec_fits(host_imgs[i], h, w, pitch, host_dsts[i], dst_pitch) != 0;
     }
-    const bool vec = (bits & 15) == 0 && pitch % 8 == 0 && dst_pitch % 8 == 0;
     SHG_PROF("scale_rows", st);
     for (int64_t i0 = 0; i0 < k; i0 += shg::kMaxBatch) {
         const int m = (int)std::min<int64_t>(shg::kMaxBatch, k - i0);

@@ -285,6 +285,21 @@ int warp_rows_forced() {                           // SHG_WARP_ROWS=4|8|16: the 
 
 }  // namespace
 
+// Whether k_warp_rows8 serves this image: its pieces are 16-byte loads and stores (pitches in whole vectors, aligned images, a source
+// row that holds a piece), flat / nv is a multiply-high (at least two vectors a row, fewer than 2^31 in all), its byte offsets are 32
+// bits off the image bases (pitches in 24 bits, both images below 4 GiB) and its 24-pixel window holds a lane's samples (a column
+// step in [0, 1.75], a finite transform).  The one statement of the gate: the launcher below asks it for every disk.
+extern "C" int shg_warp_rows_wide_fits(const uint16_t* src, int64_t h, int64_t w, int64_t src_pitch, double h00, double h01, double h02,
+                                       const uint16_t* dst, int64_t out_h, int64_t out_w, int64_t dst_pitch) {
+    if (h <= 0 || w <= 0 || out_h <= 0 || out_w <= 0 || src_pitch < w || dst_pitch < out_w) return 0;       // (nothing the launcher takes)
+    if (out_h >= 65536 || out_w >= (1ll << 30) || w >= (1ll << 30) || h >= (1ll << 30)) return 0;
+    const int64_t nv = (out_w + 7) / 8;
+    return src_pitch % 8 == 0 && dst_pitch % 8 == 0 && w >= 8 && src_pitch >= 8 && nv >= 2 && out_h * nv < (1ll << 31) &&
+           src_pitch < (1ll << 24) && dst_pitch < (1ll << 24) && h * src_pitch < (1ll << 31) && out_h * dst_pitch < (1ll << 31) &&
+           h00 >= 0.0 && h00 <= 1.75 && std::fabs(h01) < 1e300 && std::fabs(h02) < 1e300 &&
+           (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+}
+
 extern "C" int shg_warp_rows_u16(const uint16_t* src, int64_t h, int64_t w, int64_t src_pitch, double h00, double h01,
                                  double h02, uint16_t* dst, int64_t out_h, int64_t out_w, int64_t dst_pitch,
                                  uint32_t* minmax, shg_stream_t stream) {
@@ -336,13 +351,9 @@ int shg::warp_rows_batch(const uint16_t* const* host_srcs, int64_t k, int64_t h,
                             out_h, out_w, dst_pitch, shg::make_batch_n<kWarpBatch>(host_minmax2, (int)i0, m), nv_magic, nv_shift};
         // eight pixels a lane where the pieces can be 16-byte loads and stores and the window holds a lane's samples (SHG_WARP_WIDE=0: never)
         const bool wide_ok = [] { const char* e = getenv("SHG_WARP_WIDE"); return !e || atoi(e) != 0; }();     // (read per call: the parity test switches it)
-        bool wide = wide_ok && src_pitch % 8 == 0 && dst_pitch % 8 == 0 && w >= 8 && src_pitch >= 8 && nv >= 2 && out_h * ((out_w + 7) / 8) < (1ll << 31) &&
-                    src_pitch < (1ll << 24) && dst_pitch < (1ll << 24) && h * src_pitch < (1ll << 31) && out_h * dst_pitch < (1ll << 31);
-        for (int d = 0; d < m && wide; ++d) {
-            const double a00 = rows.h[d][0], a01 = rows.h[d][1], a02 = rows.h[d][2];
-            wide = a00 >= 0.0 && a00 <= 1.75 && std::fabs(a01) < 1e300 && std::fabs(a02) < 1e300 &&
-                   (reinterpret_cast<uintptr_t>(host_srcs[i0 + d]) & 15) == 0 && (reinterpret_cast<uintptr_t>(host_dsts[i0 + d]) & 15) == 0;
-        }
+        bool wide = wide_ok;
+        for (int d = 0; d < m && wide; ++d)
+            wide = shg_warp_rows_wide_fits(host_srcs[i0 + d], h, w, src_pitch, rows.h[d][0], rows.h[d][1], rows.h[d][2], host_dsts[i0 + d], out_h, out_w, dst_pitch) != 0;
         if (wide) {
             // ITER vectors a thread (the next one's pieces asked for while the current one is blended) -- as long as that still
             // leaves every CU a few workgroups: a single 2000 x 2096 disk is 512 workgroups of 4 vectors a thread

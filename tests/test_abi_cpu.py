@@ -119,6 +119,82 @@ def test_argument_errors_are_reported_not_thrown():
         _lib.check(-1, 'unit test')
 
 
+def test_warp_route_predicate_truth_table():
+    """shg_warp_rows_wide_fits is the launcher's own gate for k_warp_rows8 (csrc/warp.hip): from a layout that fits, each row
+    flips one condition."""
+    from solex_ser_recon_en_amd._lib import lib
+    A = 1 << 20                                                  # any 16-byte aligned address: the pointers are only looked at
+    good = dict(src=A, h=60, w=84, src_pitch=128, h00=1.0, h01=0.01, h02=-3.5, dst=A + 4096, out_h=60, out_w=96, dst_pitch=128)
+
+    def fits(**change):
+        a = dict(good, **change)
+        return lib.shg_warp_rows_wide_fits(a['src'], a['h'], a['w'], a['src_pitch'], a['h00'], a['h01'], a['h02'], a['dst'], a['out_h'],
+                                           a['out_w'], a['dst_pitch'])
+    assert fits() == 1
+    table = [
+        (dict(src_pitch=84), 0), (dict(src_pitch=132), 0), (dict(src_pitch=136), 1),                  # pitch % 8
+        (dict(dst_pitch=100), 0), (dict(dst_pitch=96), 1),
+        (dict(src=A + 2), 0), (dict(src=A + 8), 0), (dict(src=A + 16), 1),                            # pointer & 15
+        (dict(dst=A + 4096 + 2), 0), (dict(dst=A + 4096 + 8), 0),
+        (dict(w=8, src_pitch=8), 1), (dict(w=7, src_pitch=8), 0), (dict(w=7), 0), (dict(w=8), 1),     # w < 8
+        (dict(out_w=9), 1), (dict(out_w=8), 0), (dict(out_w=1), 0), (dict(out_w=16), 1),              # nv < 2
+        (dict(h00=-0.1), 0), (dict(h00=0.0), 1), (dict(h00=1.75), 1), (dict(h00=1.76), 0),            # the window's column step
+        (dict(h00=float('nan')), 0), (dict(h01=1e300), 0), (dict(h02=-1e300), 0), (dict(h01=float('inf')), 0), (dict(h02=float('nan')), 0),
+        (dict(h01=9.9e299), 1),
+        (dict(src_pitch=1 << 24, h=64), 0), (dict(src_pitch=(1 << 24) - 8, h=64), 1),                 # pitches in 24 bits
+        (dict(src_pitch=1 << 16, w=1 << 16, h=1 << 15), 0), (dict(src_pitch=1 << 16, w=1 << 16, h=(1 << 15) - 1), 1),    # 32-bit offsets
+        (dict(dst_pitch=1 << 16, out_h=1 << 15), 0), (dict(dst_pitch=1 << 16, out_h=(1 << 15) - 1), 1),
+        (dict(out_h=65536), 0), (dict(h=0), 0), (dict(out_w=0), 0), (dict(src_pitch=80), 0), (dict(dst_pitch=88), 0),   # nothing the launcher takes
+    ]
+    for change, want in table:
+        assert fits(**change) == want, change
+
+
+def test_scale_rows_route_predicate_truth_table():
+    """shg_scale_rows_vec_fits: the launcher's gate for k_scale_rows8 (csrc/transversalium.hip)."""
+    from solex_ser_recon_en_amd._lib import lib
+    A = 1 << 20
+    good = dict(img=A, h=5, w=17, pitch=64, dst=A + 4096, dst_pitch=64)
+
+    def fits(**change):
+        a = dict(good, **change)
+        return lib.shg_scale_rows_vec_fits(a['img'], a['h'], a['w'], a['pitch'], a['dst'], a['dst_pitch'])
+    assert fits() == 1
+    table = [
+        (dict(pitch=17), 0), (dict(pitch=20), 0), (dict(pitch=24), 1), (dict(dst_pitch=17), 0), (dict(dst_pitch=28), 0), (dict(dst_pitch=24), 1),
+        (dict(img=A + 2), 0), (dict(img=A + 8), 0), (dict(img=A + 16), 1), (dict(dst=A + 4098), 0), (dict(dst=A + 4104), 0),
+        (dict(w=1, pitch=8, dst_pitch=8), 1), (dict(w=8, pitch=8, dst_pitch=8), 1), (dict(h=1), 1),    # any width, any height: the tail goes pixel by pixel
+        (dict(h=0), 0), (dict(w=0), 0), (dict(pitch=16), 0), (dict(h=65536), 0),                      # nothing the launcher takes
+    ]
+    for change, want in table:
+        assert fits(**change) == want, change
+
+
+def test_products_route_predicate_truth_table():
+    """shg_contrast_products_vec_fits: the launcher's gate for k_products8 (csrc/post.hip)."""
+    from solex_ser_recon_en_amd._lib import lib
+    A = 1 << 20
+    good = dict(frame=A, frame_pitch=64, cl1=A + 4096, cl1_pitch=128, h=7, w=17, hc=A + 8192, protus=A + 12288, cc=A + 16384, dst_pitch=192)
+
+    def fits(**change):
+        a = dict(good, **change)
+        return lib.shg_contrast_products_vec_fits(a['frame'], a['frame_pitch'], a['cl1'], a['cl1_pitch'], a['h'], a['w'], a['hc'], a['protus'],
+                                                  a['cc'], a['dst_pitch'])
+    assert fits() == 1
+    table = [
+        (dict(frame_pitch=17), 0), (dict(frame_pitch=60), 0), (dict(cl1_pitch=17), 0), (dict(cl1_pitch=100), 0), (dict(dst_pitch=17), 0),
+        (dict(dst_pitch=196), 0), (dict(frame_pitch=24, cl1_pitch=24, dst_pitch=24), 1),                             # pitch % 8
+        (dict(frame=A + 2), 0), (dict(cl1=A + 4096 + 8), 0), (dict(hc=A + 8192 + 4), 0), (dict(protus=A + 12288 + 8), 0), (dict(cc=A + 16384 + 2), 0),
+        (dict(frame=A + 16), 1),                                                                                     # pointer & 15
+        (dict(w=9), 1), (dict(w=8), 0), (dict(w=1), 0), (dict(w=16), 1),                                             # w < 9: two vectors a row
+        (dict(dst_pitch=1 << 24), 0), (dict(dst_pitch=(1 << 24) - 8), 1),                                            # pitches in 24 bits
+        (dict(frame_pitch=1 << 16, h=1 << 15), 0), (dict(frame_pitch=1 << 16, h=(1 << 15) - 1), 1),                  # 32-bit offsets
+        (dict(h=0), 0), (dict(w=0), 0), (dict(frame_pitch=16), 0), (dict(h=65536), 0),                               # nothing the launcher takes
+    ]
+    for change, want in table:
+        assert fits(**change) == want, change
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from solex_ser_recon_en_amd import ops

@@ -240,6 +240,38 @@ def test_band_kernel_into_rows_that_are_not_16_byte_aligned(ops, monkeypatch, sh
     assert (outs[1][:, :, n:] == 0x5a5a).all()
 
 
+@pytest.mark.parametrize('h,w', [(300, 40), (40, 300)])
+def test_dense_entry_point_into_rows_that_are_not_16_byte_aligned(ops, h, w):
+    """shg_extract_columns_dense has a write-out gate of its own (16-byte stores: aligned disks, row pitch and plane stride multiples
+    of 8) and ops.extract_columns_dense always hands it a buffer that passes.  Here the caller's buffer has an odd row pitch: the
+    un-rotated file's k_extract_dense and the rotated file's band kernel write pixel by pixel -- same disks and extrema as the
+    general kernel's, the buffer's padding columns untouched."""
+    from solex_ser_recon_en_amd import _lib, hostmath
+    rng = np.random.default_rng(h)
+    n, shifts = 150, np.array([2, 0, 1, -1, -2], np.int32)
+    frames = rng.integers(0, 65536, (n, h, w)).astype(np.uint16)
+    ih, iw = (w, h) if w > h else (h, w)
+    y = np.arange(ih)
+    curve = iw / 2 + 0.004 * (y - ih / 2)
+    fit = np.stack([np.floor(curve), curve - np.floor(curve), y.astype(float), curve], axis=1)
+    ind_l, lw, rw = hostmath.column_plan(fit, shifts, ih, iw)
+    stack = dev(frames)
+    want = host(ops.extract_columns(stack, ind_l, lw, rw))
+    base = (fit[:, 0] + 1.0 * float(shifts.min())).astype(np.int64).astype(np.int32)
+    s, pitch = len(shifts), n + 3
+    buf = torch.full((s, ih, pitch), 0x5a5a, dtype=torch.int32, device='cuda').to(torch.uint16)
+    assert pitch % 8 != 0 and buf.data_ptr() % 16 == 0
+    mm = torch.empty(s * 130, dtype=torch.int32, device='cuda')
+    ind_d, base_d, w_d = dev(ind_l), dev(base), dev(np.stack([lw, rw]))
+    _lib.check(_lib.lib.shg_extract_columns_dense(stack.data_ptr(), n, h, w, 2, h * w, ind_d.data_ptr(), base_d.data_ptr(), w_d[0].data_ptr(),
+                                                  w_d[1].data_ptr(), shifts.ctypes.data, s, buf.data_ptr(), buf.stride(1), buf.stride(0), n, 0, 0,
+                                                  mm.data_ptr(), torch.cuda.current_stream().cuda_stream), 'shg_extract_columns_dense')
+    got = host(buf)
+    np.testing.assert_array_equal(got[:, :, :n], want)
+    assert (got[:, :, n:] == 0x5a5a).all()
+    assert [tuple(e) for e in mm[s * 128:].view(s, 2).cpu().numpy().astype(np.int64)] == [(int(p.min()), int(p.max())) for p in want]
+
+
 def test_pass_a_in_the_lane_waits_for_the_stack_its_caller_is_still_writing(ops):
     """With a frame-pass lane set, pass A runs on another stream than its caller's: it must still see a stack that the caller's
     stream has only queued the writing of (no synchronisation in between)."""
@@ -484,15 +516,26 @@ def test_warp_golden_bit_exact(ops, golden):
 def test_warp_eight_pixels_a_lane_equals_one_pixel_a_lane(ops, monkeypatch, h, w, oh, ow, h00, h01, h02):
     """k_warp_rows8 (round 6: three 16-byte pieces of the source row per lane, LDS window, one 16-byte store) against k_warp_rows
     (two 2-byte gathers per pixel), which g3 pins to scikit-image: same pixels on transforms that run off either edge, land on
-    whole positions, squeeze and stretch."""
+    whole positions, squeeze and stretch.  The source lies in a pitched store, as production's disks do: handed over dense (pitch =
+    width) every width that is not a multiple of 8 goes to k_warp_rows in both calls.  The route predicate is asserted for each case."""
+    from solex_ser_recon_en_amd._lib import lib
+    from tests.pitched_util import POISON, padding_untouched, pitched
     rng = np.random.default_rng(h * 31 + w + ow)
     img = rng.integers(0, 65536, (h, w)).astype(np.uint16)
     img[:, :3] = 65535                                                # saturated columns at the edge: the clip's upper bound in play
+    store, src = pitched(img)
+
+    def warp():
+        out = ops.warp_rows_u16(src, h00, h01, h02, oh, ow)
+        fits = lib.shg_warp_rows_wide_fits(src.data_ptr(), h, w, src.stride(0), h00, h01, h02, out.data_ptr(), oh, ow, out.stride(0))
+        assert fits == (0 if h00 == 1.76 else 1)                      # (what the launcher asks once SHG_WARP_WIDE lets it)
+        return host(out)
     monkeypatch.setenv('SHG_WARP_WIDE', '0')
-    want = host(ops.warp_rows_u16(dev(img), h00, h01, h02, oh, ow))
+    want = warp()
     monkeypatch.delenv('SHG_WARP_WIDE')
-    got = host(ops.warp_rows_u16(dev(img), h00, h01, h02, oh, ow))
+    got = warp()
     np.testing.assert_array_equal(got, want)
+    assert padding_untouched(store, src, POISON)
 
 
 # ---- transversalium -------------------------------------------------------------
@@ -808,13 +851,15 @@ def test_row_factor_paths_match_float_image(ops, orc, golden):
 def test_row_kernels_on_widths_around_their_vector_and_workgroup_sizes(ops, h, w):
     """k_scale_rows8, k_products8 and the CLAHE blend deal their lanes from one flat (row, vector) sequence: widths below a vector,
     just past a multiple of a workgroup's span (2049, 2096, 4100), one short of it (1023), row counts that are not multiples of
-    the rows a lane takes -- against plain NumPy, pixel for pixel, padding columns untouched."""
+    the rows a lane takes -- against plain NumPy, pixel for pixel, padding columns untouched.  Each shape in both layouts: dense
+    (pitch = width: k_scale_rows and k_products unless the width is a multiple of 8) and pitched as production's images are (the
+    eight-pixel kernels, their partial last vector included); which kernel a layout gets is asserted with the route predicates."""
+    from solex_ser_recon_en_amd._lib import lib
+    from tests.pitched_util import POISON, padding_untouched, pitched
     rng = np.random.default_rng(h * 10007 + w)
     img = rng.integers(0, 65536, (h, w)).astype(np.uint16)
     c = 0.5 + rng.random(h)
     want = np.minimum(img.astype(np.float64) * c[:, None], 65535.0).astype(np.uint16)       # (img.T * c).T, saturate, truncate
-    np.testing.assert_array_equal(host(ops.scale_rows_u16(dev(img), c)), want)
-
     cl1 = rng.integers(0, 65536, (h, w)).astype(np.uint16)
     lo_hi6 = [9000.0, 61000.0, 0.0, 11000.0, 3000.5, 64000.0]
 
@@ -822,16 +867,33 @@ def test_row_kernels_on_widths_around_their_vector_and_workgroup_sizes(ops, h, w
         v = 65535.0 * (a.astype(np.float64) - lo) / (hi - lo)
         return np.clip(v, 0, 65535).astype(np.uint16)
     disc = (w // 2, h // 2, max(1, min(h, w) // 3))
-    hc, protus, cc = (host(t) for t in ops.contrast_products_u16(dev(img), dev(cl1), lo_hi6, disc))
-    np.testing.assert_array_equal(hc, rescale(img, lo_hi6[0], lo_hi6[1]))
-    np.testing.assert_array_equal(cc, rescale(cl1, lo_hi6[4], lo_hi6[5]))
     want_p = rescale(img, lo_hi6[2], lo_hi6[3])
     yy, xx = np.mgrid[0:h, 0:w]
     ady = np.abs(yy - disc[1])
     half = np.floor(np.sqrt(np.maximum(disc[2] ** 2 - ady.astype(np.float64) ** 2, 0)) + 1e-9).astype(np.int64)
     inside = (ady <= disc[2]) & (np.abs(xx - disc[0]) <= half)
     want_p[inside] = 80                                          # cv2.circle(frame_protus, centre, r, 80, -1)
-    np.testing.assert_array_equal(protus, want_p)
+
+    for layout in ('dense', 'pitched'):
+        if layout == 'dense':
+            stores, (src, csrc) = [], (dev(img), dev(cl1))
+        else:
+            stores = [pitched(img), pitched(cl1)]
+            src, csrc = stores[0][1], stores[1][1]
+        vector = layout == 'pitched' or w % 8 == 0
+        out = ops.scale_rows_u16(src, c)
+        assert lib.shg_scale_rows_vec_fits(src.data_ptr(), h, w, src.stride(0), out.data_ptr(), out.stride(0)) == (1 if vector else 0), layout
+        np.testing.assert_array_equal(host(out), want, err_msg=layout)
+
+        hc, protus, cc = ops.contrast_products_u16(src, csrc, lo_hi6, disc)
+        fits = lib.shg_contrast_products_vec_fits(src.data_ptr(), src.stride(0), csrc.data_ptr(), csrc.stride(0), h, w, hc.data_ptr(), protus.data_ptr(),
+                                                  cc.data_ptr(), hc.stride(0))
+        assert fits == (1 if vector and w >= 9 else 0), layout
+        np.testing.assert_array_equal(host(hc), rescale(img, lo_hi6[0], lo_hi6[1]), err_msg=layout)
+        np.testing.assert_array_equal(host(cc), rescale(cl1, lo_hi6[4], lo_hi6[5]), err_msg=layout)
+        np.testing.assert_array_equal(host(protus), want_p, err_msg=layout)
+        for store, view in stores:
+            assert padding_untouched(store, view, POISON), layout
 
 
 @pytest.mark.parametrize('bounds', [
