@@ -1,6 +1,8 @@
 """Command-line flags of SHG_MAIN (reference CLI_handler.py:10-114): same flags, same
 option keys, same parsing order.  One addition: the value of -w / -r may also be given
 detached (`-w -10:10:1`), which the reference's parser rejects with int('') errors."""
+import contextlib
+import os
 import re
 import sys
 
@@ -129,3 +131,26 @@ def handle_CLI(options, argv=None):
         raise ValueError('flag -%s needs a value' % pending)
     print('theses files are going to be processed : ', serfiles)
     return serfiles
+
+
+def options_and_files(p, rest, need='exactly one SER or AVI file is needed', least=1, most=1, extra=(), checks=None):
+    """For the command lines that take the SHG_MAIN flags beside their own (the line maps, the disk products): what argparse
+    parser `p` left in `rest` -> (the options, the files: the scans among `rest`, then `extra`).  Refuses through p.error, with
+    `need`, fewer than `least` or more than `most` (None: any number) files or an argument that is neither; then checks(files)
+    may refuse; then a file that does not exist."""
+    from . import SHG_MAIN
+    opts = SHG_MAIN.default_options()
+    try:
+        with contextlib.redirect_stdout(sys.stderr):            # the SHG_MAIN parser reports on stdout: keep it for the JSON line
+            files = handle_CLI(opts, rest) + list(extra)
+    except ValueError as e:
+        p.error(str(e))
+    unknown = [a for a in rest if not a.startswith('-') and a not in files and not a.isdigit()]
+    if len(files) < least or (most is not None and len(files) > most) or unknown:
+        p.error('%s (got %s)' % (need, files + unknown))
+    if checks is not None:
+        checks(files)
+    for path in files:
+        if not os.path.isfile(path):
+            p.error('no such file: %s' % path)
+    return opts, files

@@ -1,7 +1,7 @@
 // Removing a fitted plane from a finished line map (shg_map_plane_moments, shg_map_detrend).  Not a reference stage: the arithmetic is
 // the one include/shg_hip.h states, restated in NumPy by tests/detrend_ref.py.  The fit itself is the host's (linemaps.py): the GPU
 // gathers the ten integer moments of the used pixels in one streaming read, and subtracts the plane in one read and two writes.
-#include "shg_common.h"
+#include "image_args.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -201,10 +201,6 @@ int check_map(const char* fn, const void* map, int64_t h, int64_t w, int64_t pit
     return 0;
 }
 
-bool rows_on_16_bytes(const void* p, int64_t pitch, size_t element) {
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (pitch * (int64_t)element) % 16 == 0;
-}
-
 int round_up(int64_t v, int to) { return (int)((v + to - 1) / to * to); }
 
 }  // namespace
@@ -230,12 +226,9 @@ extern "C" int shg_map_plane_moments(const float* map, int64_t h, int64_t w, int
     a.band = (int)(band > kMaxBandRows ? kMaxBandRows : band);
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("map_plane_moments", st);
-    if (hipError_t e = hipMemsetAsync(moments10, 0, 10 * sizeof(int64_t), st)) {
-        shg::set_error("shg_map_plane_moments: %s", hipGetErrorString(e));
-        return (int)e;
-    }
+    if (const int e = shg::zero_async("shg_map_plane_moments", moments10, 10 * sizeof(int64_t), st)) return e;
     const dim3 grid((unsigned)gx, (unsigned)((h + a.band - 1) / a.band));
-    return shg::launch(rows_on_16_bytes(map, pitch, sizeof(float)) ? k_plane_moments<true> : k_plane_moments<false>, grid, dim3(kThreads), 0,
+    return shg::launch(shg::rows_aligned(map, pitch, sizeof(float), 16) ? k_plane_moments<true> : k_plane_moments<false>, grid, dim3(kThreads), 0,
                        st, a, "k_plane_moments");
 }
 
@@ -251,7 +244,7 @@ extern "C" int shg_map_detrend(const float* map, int64_t h, int64_t w, int64_t p
     constexpr int kRows = 4;
     DetrendArgs a{map, (int)h, (int)w, pitch, plane3[0], plane3[1], plane3[2], out, out_pitch, png, png_pitch,
                   png ? 32767.0 / display_range : 0.0, kRows};
-    const bool vec = rows_on_16_bytes(map, pitch, sizeof(float)) && rows_on_16_bytes(out, out_pitch, sizeof(float)) &&
+    const bool vec = shg::rows_aligned(map, pitch, sizeof(float), 16) && shg::rows_aligned(out, out_pitch, sizeof(float), 16) &&
                      (!png || (reinterpret_cast<uintptr_t>(png) % 8 == 0 && png_pitch % 4 == 0));
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("map_detrend", st);

@@ -24,7 +24,7 @@
 // host arrays; 4 KB of arguments hold 449 doubles, so a call is cut into launches that each own 448 consecutive table intervals
 // (one launch up to K = 448, three for a 2000 x 2000 product).  A launch skips, before it loads anything, the thread rows whose
 // pixels all lie clear of its annulus.  A pixel is written by one launch only, and by the thread that read it: in place is safe.
-#include "shg_common.h"
+#include "image_args.h"
 
 #include <limits.h>
 #include <math.h>
@@ -32,11 +32,9 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxDim = 16384;
 constexpr int kMaxRings = 16384;
 constexpr size_t kTableBytes = 256 * sizeof(uint32_t);        // one ring's 256 counts
 constexpr size_t kStateBytes = 4 * sizeof(uint32_t);          // one ring's {high byte, rank left} x {lower, upper}
-constexpr size_t kAlign = 256;
 constexpr uint32_t kNoByte = 0xFFFF;                          // the "high byte" of a ring without pixels: no sample has it
 
 // The ring of a pixel: the largest k with (double)k * (double)k <= d2.  sqrt is within an ulp, so its truncation is within one of k.
@@ -310,14 +308,6 @@ __global__ __launch_bounds__(kThreads) void k_ring_flatten(const FlattenArgs a) 
     }
 }
 
-int check_image(const char* fn, const void* img, int64_t h, int64_t w, int64_t pitch) {
-    SHG_REQUIRE(img, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(h >= 1 && h <= kMaxDim && w >= 1 && w <= kMaxDim, SHG_E_UNSUPPORTED, "%s: an image of %lld x %lld (1 to %d either way)", fn,
-                (long long)h, (long long)w, kMaxDim);
-    SHG_REQUIRE(pitch >= w, SHG_E_ARG, "%s: pitch < w", fn);
-    return 0;
-}
-
 int check_circle(const char* fn, const double* circle3, int64_t n_rings) {
     SHG_REQUIRE(circle3, SHG_E_ARG, "%s: null pointer", fn);
     const double cx = circle3[0], cy = circle3[1], rad = circle3[2];
@@ -329,11 +319,7 @@ int check_circle(const char* fn, const double* circle3, int64_t n_rings) {
     return 0;
 }
 
-bool rows_on_16_bytes(const void* p, int64_t pitch) {
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (pitch * (int64_t)sizeof(uint16_t)) % 16 == 0;
-}
-
-size_t medians_bytes(int64_t n_rings) { return (size_t)n_rings * (3 * kTableBytes + kStateBytes) + kAlign; }
+size_t medians_bytes(int64_t n_rings) { return (size_t)n_rings * (3 * kTableBytes + kStateBytes) + shg::kWorkspaceAlign; }
 
 }  // namespace
 
@@ -345,20 +331,17 @@ extern "C" int shg_ring_medians_u16(const uint16_t* img, int64_t h, int64_t w, i
                                     uint32_t* count, uint16_t* lo, uint16_t* hi, void* workspace, size_t workspace_bytes,
                                     shg_stream_t stream) {
     const char* fn = "shg_ring_medians_u16";
-    if (const int e = check_image(fn, img, h, w, pitch)) return e;
+    if (const int e = shg::check_image(fn, img, h, w, pitch)) return e;
     SHG_REQUIRE(count && lo && hi && workspace, SHG_E_ARG, "%s: null pointer", fn);
     if (const int e = check_circle(fn, circle3, n_rings)) return e;
     SHG_REQUIRE(workspace_bytes >= medians_bytes(n_rings), SHG_E_ARG, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
                 medians_bytes(n_rings));
     const int K = (int)n_rings;
-    uint32_t* tables = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + kAlign - 1) / kAlign * kAlign);
+    uint32_t* tables = reinterpret_cast<uint32_t*>(shg::align_up(workspace, shg::kWorkspaceAlign));
     uint32_t* state = tables + 3 * (size_t)K * 256;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("ring_medians", st);
-    if (hipError_t e = hipMemsetAsync(tables, 0, 3 * (size_t)K * kTableBytes, st)) {
-        shg::set_error("%s: %s", fn, hipGetErrorString(e));
-        return (int)e;
-    }
+    if (const int e = shg::zero_async(fn, tables, 3 * (size_t)K * kTableBytes, st)) return e;
     HistArgs ha{img, (int)h, (int)w, pitch, circle3[0], circle3[1], circle3[2] * circle3[2], K, tables, nullptr};
     const PickArgs pa{tables, state, K, count, lo, hi};
     const dim3 picks((unsigned)((K + 3) / 4));
@@ -377,7 +360,7 @@ extern "C" int shg_ring_medians_u16(const uint16_t* img, int64_t h, int64_t w, i
 extern "C" int shg_ring_flatten_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, const double* gain,
                                     int64_t n_rings, uint16_t* out, int64_t out_pitch, shg_stream_t stream) {
     const char* fn = "shg_ring_flatten_u16";
-    if (const int e = check_image(fn, img, h, w, pitch)) return e;
+    if (const int e = shg::check_image(fn, img, h, w, pitch)) return e;
     SHG_REQUIRE(gain && out, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(out_pitch >= w, SHG_E_ARG, "%s: output pitch < w", fn);
     if (const int e = check_circle(fn, circle3, n_rings)) return e;
@@ -399,7 +382,7 @@ extern "C" int shg_ring_flatten_u16(const uint16_t* img, int64_t h, int64_t w, i
         a.j0 = j0, a.j1 = j0 + kWindow < K ? j0 + kWindow : K;
         const int last = a.j1 < K ? a.j1 : K - 1;                    // the interval [j1 - 1, j1) reads gain[j1] too
         for (int j = j0; j <= last; ++j) a.gain[j - j0] = gain[j];
-        const bool vec = rows_on_16_bytes(a.src, a.pitch) && rows_on_16_bytes(out, out_pitch);
+        const bool vec = shg::rows_aligned(a.src, a.pitch, sizeof(uint16_t), 16) && shg::rows_aligned(out, out_pitch, sizeof(uint16_t), 16);
         if (const int e = shg::launch(vec ? k_ring_flatten<true> : k_ring_flatten<false>, grid, dim3(kThreads), 0, st, a, "k_ring_flatten"))
             return e;
     }

@@ -19,7 +19,7 @@
 // 64-bit), folds the wave with DPP and adds the wave's total to a table in LDS; at its end it adds the table's non-zero entries
 // to the output with 64-bit integer atomics.  Everything accumulated is an integer: neither the grid nor the order of the atomics
 // can change a bit.  A tile without a pixel of the set is skipped before its border is loaded.
-#include "shg_common.h"
+#include "image_args.h"
 
 #include <math.h>
 #include <utility>
@@ -27,7 +27,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxDim = 16384;
 constexpr int kMaxSources = 32;
 
 // ---- combine ----
@@ -216,15 +215,9 @@ int launch_combine(int mode, dim3 grid, hipStream_t st, const CombineArgs& a) {
     return shg::launch(k_stack_combine<CAP, SHG_STACK_SIGMA>, grid, dim3(kThreads), 0, st, a, what);
 }
 
-// [p, p + ((h - 1) pitch + w) item) of an image
-struct Span {
-    uintptr_t lo, hi;
-};
-Span span_of(const void* p, int64_t h, int64_t w, int64_t pitch, size_t item) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return {lo, lo + (uintptr_t)((h - 1) * pitch + w) * item};
-}
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+using shg::overlap;
+using shg::Span;
+using shg::span_of;
 
 // ---- SSD ----
 constexpr int kTW = 64, kTH = 16;                 // the tile; a thread owns column threadIdx.x % 64 of rows threadIdx.x / 64 + 4 i
@@ -309,8 +302,8 @@ extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int
     const char* fn = "shg_stack_combine_u16";
     SHG_REQUIRE(host_srcs && host_dims3 && host_xform4 && out, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(n >= 1 && n <= kMaxSources, SHG_E_ARG, "%s: %d sources (1 to %d)", fn, n, kMaxSources);
-    SHG_REQUIRE(oh >= 1 && oh <= kMaxDim && ow >= 1 && ow <= kMaxDim, SHG_E_UNSUPPORTED, "%s: an output of %lld x %lld (1 to %d either way)",
-                fn, (long long)oh, (long long)ow, kMaxDim);
+    SHG_REQUIRE(shg::image_dims_ok(oh, ow), SHG_E_UNSUPPORTED, "%s: an output of %lld x %lld (1 to %d either way)", fn, (long long)oh,
+                (long long)ow, shg::kMaxImageDim);
     SHG_REQUIRE(out_pitch >= ow, SHG_E_ARG, "%s: output pitch < ow", fn);
     SHG_REQUIRE(!count || count_pitch >= ow, SHG_E_ARG, "%s: count pitch < ow", fn);
     SHG_REQUIRE(mode == SHG_STACK_MEAN || mode == SHG_STACK_MEDIAN || mode == SHG_STACK_SIGMA, SHG_E_ARG, "%s: unknown mode %d", fn, mode);
@@ -324,8 +317,8 @@ extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int
         const int64_t h = host_dims3[3 * j], w = host_dims3[3 * j + 1], pitch = host_dims3[3 * j + 2];
         const double s = host_xform4[4 * j], tx = host_xform4[4 * j + 1], ty = host_xform4[4 * j + 2], gain = host_xform4[4 * j + 3];
         SHG_REQUIRE(host_srcs[j], SHG_E_ARG, "%s: source %d is a null pointer", fn, j);
-        SHG_REQUIRE(h >= 1 && h <= kMaxDim && w >= 1 && w <= kMaxDim, SHG_E_UNSUPPORTED, "%s: source %d of %lld x %lld (1 to %d either way)", fn,
-                    j, (long long)h, (long long)w, kMaxDim);
+        SHG_REQUIRE(shg::image_dims_ok(h, w), SHG_E_UNSUPPORTED, "%s: source %d of %lld x %lld (1 to %d either way)", fn, j, (long long)h,
+                    (long long)w, shg::kMaxImageDim);
         SHG_REQUIRE(pitch >= w, SHG_E_ARG, "%s: source %d: pitch < w", fn, j);
         SHG_REQUIRE(isfinite(s) && s > 0.0, SHG_E_ARG, "%s: source %d: scale %g is not finite and > 0", fn, j, s);
         SHG_REQUIRE(isfinite(tx) && isfinite(ty), SHG_E_ARG, "%s: source %d: translation (%g, %g) is not finite", fn, j, tx, ty);
@@ -337,8 +330,8 @@ extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int
     }
     a.out = out, a.count = count, a.oh = (int)oh, a.ow = (int)ow, a.out_pitch = out_pitch, a.count_pitch = count ? count_pitch : 0;
     a.n = n, a.iterations = iterations, a.kappa = kappa;
-    a.vec_out = reinterpret_cast<uintptr_t>(out) % 16 == 0 && (out_pitch * (int64_t)sizeof(uint16_t)) % 16 == 0;
-    a.vec_count = count && reinterpret_cast<uintptr_t>(count) % 8 == 0 && count_pitch % 8 == 0;
+    a.vec_out = shg::rows_aligned(out, out_pitch, sizeof(uint16_t), 16);
+    a.vec_count = count && shg::rows_aligned(count, count_pitch, sizeof(uint8_t), 8);
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("stack_combine", st);
     const dim3 grid((unsigned)((ow + kLanesX * kOct - 1) / (kLanesX * kOct)), (unsigned)((oh + kRows - 1) / kRows));
@@ -352,17 +345,12 @@ extern "C" int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const u
                                  const double* circle3, uint64_t* ssd, shg_stream_t stream) {
     const char* fn = "shg_shift_ssd_u16";
     SHG_REQUIRE(ref && img && ssd, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(h >= 1 && h <= kMaxDim && w >= 1 && w <= kMaxDim, SHG_E_UNSUPPORTED, "%s: images of %lld x %lld (1 to %d either way)", fn,
-                (long long)h, (long long)w, kMaxDim);
+    SHG_REQUIRE(shg::image_dims_ok(h, w), SHG_E_UNSUPPORTED, "%s: images of %lld x %lld (1 to %d either way)", fn, (long long)h,
+                (long long)w, shg::kMaxImageDim);
     SHG_REQUIRE(ref_pitch >= w && img_pitch >= w, SHG_E_ARG, "%s: pitch < w", fn);
     SHG_REQUIRE(S >= 0 && S <= kMaxS, SHG_E_ARG, "%s: a search of %d pixels (0 to %d)", fn, S, kMaxS);
     SsdArgs a{};
-    a.masked = circle3 && !(circle3[0] == -1.0 && circle3[1] == -1.0 && circle3[2] == -1.0);
-    if (a.masked) {
-        SHG_REQUIRE(isfinite(circle3[0]) && isfinite(circle3[1]) && isfinite(circle3[2]), SHG_E_ARG, "%s: the circle (%g, %g, %g) is not finite",
-                    fn, circle3[0], circle3[1], circle3[2]);
-        a.cx = circle3[0], a.cy = circle3[1], a.rad2 = circle3[2] * circle3[2];
-    }
+    if (const int e = shg::parse_disk_mask(fn, circle3, &a.masked, &a.cx, &a.cy, &a.rad2)) return e;
     a.ref = ref, a.img = img, a.ref_pitch = ref_pitch, a.img_pitch = img_pitch, a.h = (int)h, a.w = (int)w, a.S = S;
     a.ssd = reinterpret_cast<unsigned long long*>(ssd);
     a.tiles_x = (int)((w + kTW - 1) / kTW);
@@ -370,10 +358,7 @@ extern "C" int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const u
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("shift_ssd", st);
     const size_t words = (size_t)(2 * S + 1) * (2 * S + 1) + 1;
-    if (hipError_t e = hipMemsetAsync(ssd, 0, words * sizeof(uint64_t), st)) {
-        shg::set_error("%s: %s", fn, hipGetErrorString(e));
-        return (int)e;
-    }
+    if (const int e = shg::zero_async(fn, ssd, words * sizeof(uint64_t), st)) return e;
     if (w < 2 * S + 1 || h < 2 * S + 1) return 0;                        // the set is empty: the zeros are the result
     return shg::launch(k_shift_ssd, dim3((unsigned)(a.tiles < kSsdBlocks ? a.tiles : kSsdBlocks)), dim3(kThreads), 0, st, a, "k_shift_ssd");
 }

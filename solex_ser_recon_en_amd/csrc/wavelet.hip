@@ -26,14 +26,13 @@
 //   k_noise_hist<true>      T1[|w_1| & 2047] += 1 where |w_1| >> 11 is that bin
 //   k_noise_pick<true>      the median and n
 // Everything accumulated is an integer count: neither the grid nor the order of the atomics can change a bit.
-#include "shg_common.h"
+#include "image_args.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxDim = 16384;
 constexpr int kMaxLevels = 6;
 constexpr int kFusedLevels = 3;
 constexpr int kMaxGain = 4096;
@@ -41,7 +40,6 @@ constexpr int kMaxThreshold = 1 << 22;
 constexpr int kTW = 64, kTH = 32;                 // the fused kernel's tile; a thread owns column threadIdx.x % 64 of rows threadIdx.x / 64 + 4 i
 constexpr int kOwned = kTW * kTH / kThreads;
 constexpr int kRowStep = kThreads / kTW;
-constexpr size_t kAlign = 256;
 constexpr int kBins = 2048;                       // 11 bits a level of the select
 constexpr size_t kNoiseBytes = 2 * kBins * sizeof(uint32_t) + 256;       // T0 | T1 | the state {bin, rank left, n}
 constexpr uint32_t kNoBin = 0xFFFFFFFFu;          // the "bin" of an empty set: no value has it
@@ -329,12 +327,9 @@ __global__ __launch_bounds__(kThreads) void k_noise_pick(const PickArgs a) {
 }
 
 // ---- host ----
-struct Span {
-    uintptr_t lo, hi;
-};
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-bool dims_ok(int64_t h, int64_t w) { return h >= 1 && h <= kMaxDim && w >= 1 && w <= kMaxDim; }
+using shg::overlap;
+using shg::Span;
+using shg::span_of;
 
 // the planes the launches of an L-level call hand each other: the 64-bit sum and one or two c planes, beyond three levels
 size_t carried_bytes(int64_t h, int64_t w, int levels) {
@@ -343,30 +338,19 @@ size_t carried_bytes(int64_t h, int64_t w, int levels) {
     return px * sizeof(long long) + px * sizeof(int32_t) * (levels == kFusedLevels + 1 ? 1 : 2);
 }
 
-size_t workspace_bytes(int64_t h, int64_t w, int levels) { return kAlign + kNoiseBytes + carried_bytes(h, w, levels); }
-
-uint8_t* aligned(void* workspace) {
-    return reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(workspace) + kAlign - 1) / kAlign * kAlign);
-}
-
-int check_image(const char* fn, const void* img, int64_t h, int64_t w, int64_t pitch) {
-    SHG_REQUIRE(img, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(dims_ok(h, w), SHG_E_UNSUPPORTED, "%s: an image of %lld x %lld (1 to %d either way)", fn, (long long)h, (long long)w, kMaxDim);
-    SHG_REQUIRE(pitch >= w, SHG_E_ARG, "%s: pitch < w", fn);
-    return 0;
-}
+size_t workspace_bytes(int64_t h, int64_t w, int levels) { return shg::kWorkspaceAlign + kNoiseBytes + carried_bytes(h, w, levels); }
 
 }  // namespace
 
 extern "C" size_t shg_wavelet_workspace_bytes(int64_t h, int64_t w, int levels) {
-    return dims_ok(h, w) && levels >= 1 && levels <= kMaxLevels ? workspace_bytes(h, w, levels) : 0;
+    return shg::image_dims_ok(h, w) && levels >= 1 && levels <= kMaxLevels ? workspace_bytes(h, w, levels) : 0;
 }
 
 extern "C" int shg_wavelet_sharpen_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, int levels, const int32_t* host_gain_q8,
                                        const int32_t* host_threshold_q6, uint16_t* out, int64_t out_pitch, int32_t* planes, void* workspace,
                                        size_t workspace_bytes_given, shg_stream_t stream) {
     const char* fn = "shg_wavelet_sharpen_u16";
-    if (const int e = check_image(fn, img, h, w, pitch)) return e;
+    if (const int e = shg::check_image(fn, img, h, w, pitch)) return e;
     SHG_REQUIRE(host_gain_q8 && host_threshold_q6 && out && workspace, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(out_pitch >= w, SHG_E_ARG, "%s: output pitch < w", fn);
     SHG_REQUIRE(levels >= 1 && levels <= kMaxLevels, SHG_E_ARG, "%s: %d levels (1 to %d)", fn, levels, kMaxLevels);
@@ -378,9 +362,7 @@ extern "C" int shg_wavelet_sharpen_u16(const uint16_t* img, int64_t h, int64_t w
     }
     SHG_REQUIRE(workspace_bytes_given >= workspace_bytes(h, w, levels), SHG_E_ARG, "%s: workspace of %zu bytes, %zu needed", fn,
                 workspace_bytes_given, workspace_bytes(h, w, levels));
-    const uintptr_t img_lo = reinterpret_cast<uintptr_t>(img), out_lo = reinterpret_cast<uintptr_t>(out);
-    const Span img_span{img_lo, img_lo + (uintptr_t)((h - 1) * pitch + w) * sizeof(uint16_t)};
-    const Span out_span{out_lo, out_lo + (uintptr_t)((h - 1) * out_pitch + w) * sizeof(uint16_t)};
+    const Span img_span = span_of(img, h, w, pitch, sizeof(uint16_t)), out_span = span_of(out, h, w, out_pitch, sizeof(uint16_t));
     SHG_REQUIRE(!overlap(out_span, img_span), SHG_E_ARG, "%s: the output overlaps the image (a stencil cannot run in place)", fn);
     if (planes) {
         const uintptr_t lo = reinterpret_cast<uintptr_t>(planes);
@@ -391,7 +373,7 @@ extern "C" int shg_wavelet_sharpen_u16(const uint16_t* img, int64_t h, int64_t w
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("wavelet_sharpen", st);
     const size_t px = (size_t)h * (size_t)w;
-    long long* acc = reinterpret_cast<long long*>(aligned(workspace) + kNoiseBytes);
+    long long* acc = reinterpret_cast<long long*>(shg::align_up(workspace, shg::kWorkspaceAlign) + kNoiseBytes);
     int32_t* c_plane[2] = {reinterpret_cast<int32_t*>(acc + px), reinterpret_cast<int32_t*>(acc + px) + px};
     FusedArgs fa{};
     fa.img = img, fa.h = (int)h, fa.w = (int)w, fa.pitch = pitch, fa.levels = levels;
@@ -421,25 +403,17 @@ extern "C" int shg_wavelet_sharpen_u16(const uint16_t* img, int64_t h, int64_t w
 extern "C" int shg_wavelet_noise_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, uint64_t* out2,
                                      void* workspace, size_t workspace_bytes_given, shg_stream_t stream) {
     const char* fn = "shg_wavelet_noise_u16";
-    if (const int e = check_image(fn, img, h, w, pitch)) return e;
+    if (const int e = shg::check_image(fn, img, h, w, pitch)) return e;
     SHG_REQUIRE(out2 && workspace, SHG_E_ARG, "%s: null pointer", fn);
     NoiseArgs na{};
-    na.masked = circle3 && !(circle3[0] == -1.0 && circle3[1] == -1.0 && circle3[2] == -1.0);
-    if (na.masked) {
-        SHG_REQUIRE(isfinite(circle3[0]) && isfinite(circle3[1]) && isfinite(circle3[2]), SHG_E_ARG, "%s: the circle (%g, %g, %g) is not finite",
-                    fn, circle3[0], circle3[1], circle3[2]);
-        na.cx = circle3[0], na.cy = circle3[1], na.rad2 = circle3[2] * circle3[2];
-    }
+    if (const int e = shg::parse_disk_mask(fn, circle3, &na.masked, &na.cx, &na.cy, &na.rad2)) return e;
     SHG_REQUIRE(workspace_bytes_given >= workspace_bytes(h, w, 1), SHG_E_ARG, "%s: workspace of %zu bytes, %zu needed", fn,
                 workspace_bytes_given, workspace_bytes(h, w, 1));
-    uint32_t* tables = reinterpret_cast<uint32_t*>(aligned(workspace));
+    uint32_t* tables = reinterpret_cast<uint32_t*>(shg::align_up(workspace, shg::kWorkspaceAlign));
     uint32_t* state = tables + 2 * kBins;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("wavelet_noise", st);
-    if (hipError_t e = hipMemsetAsync(tables, 0, 2 * kBins * sizeof(uint32_t), st)) {
-        shg::set_error("%s: %s", fn, hipGetErrorString(e));
-        return (int)e;
-    }
+    if (const int e = shg::zero_async(fn, tables, 2 * kBins * sizeof(uint32_t), st)) return e;
     na.img = img, na.h = (int)h, na.w = (int)w, na.pitch = pitch, na.table = tables, na.state = nullptr;
     const PickArgs pa{tables, state, reinterpret_cast<unsigned long long*>(out2)};
     na.tiles_x = (int)((w + kNW - 1) / kNW);

@@ -6,20 +6,13 @@ step by step so that tests/flatten_ref.py restates it bit for bit.
     python -m solex_ser_recon_en_amd.flatten scan.ser [--shift S] [--smooth N] [--max-gain G] [--contrast] [SHG_MAIN flags]
 """
 import argparse
-import contextlib
-import io
 import math
 import os
 import sys
 
 import numpy as np
 
-
-def _host_u(t, dtype):
-    """A uint16 / uint32 device tensor as a NumPy array of that type (through the signed type of the same width)."""
-    import torch
-    signed = {torch.uint16: torch.int16, torch.uint32: torch.int32}[t.dtype]
-    return t.view(signed).cpu().numpy().view(dtype)
+from . import disk
 
 
 def ring_profile(image, circle):
@@ -28,7 +21,7 @@ def ring_profile(image, circle):
     from . import ops
     from .device import to_device_u16
     count, lo, hi = ops.ring_medians_u16(to_device_u16(image), circle)
-    count, lo, hi = _host_u(count, np.uint32), _host_u(lo, np.uint16), _host_u(hi, np.uint16)
+    count, lo, hi = disk.host_u(count, np.uint32), disk.host_u(lo, np.uint16), disk.host_u(hi, np.uint16)
     return {'count': count, 'lo': lo, 'hi': hi, 'median': (lo.astype(np.float64) + hi.astype(np.float64)) / 2.0,
             'radius': np.arange(count.shape[0], dtype=np.float64) + 0.5}
 
@@ -90,67 +83,21 @@ def flatten_disk(image, circle, smooth=1, level=None, max_gain=8.0):
     return ops.ring_flatten_u16(t, circle, gain), profile, gain
 
 
-def scan_disk_and_circle(file_or_reader, options=None, shift=0, what=('flattening', 'flattening needs', 'flattening takes')):
-    """A scan's disk at `shift`: the image _uncontrasted.png shows for that shift before img_rotate -- through the package's own
-    stages as Solex_recon.solex_process composes them: line fit, the disks of the ellipse-fit shift and of `shift`, the limb fit,
-    the ellipse -> circle warp, transversalium, crop -- and its circle.  -> {'image' (a uint16 device tensor), 'circle' (of the
-    image), 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe / slant_fix (no limb fit, hence no circle), de-vignette (a
-    float64 frame) and a frame-sharded reader; `what` words the messages for the caller (flatten_scan, stack.scan_disk)."""
-    from . import SHG_MAIN, dist
-    from .device import DeviceImage, to_device_u16
-    from .ellipse_to_circle import correct_image, ellipse_to_circle
-    from .fits_io import make_header
-    from .Solex_recon import crop_plan, crop_to_width
-    from .solex_util import compute_mean_return_fit, correct_transversalium2, extract_disks
-    from .video_reader import video_reader
-    opts = SHG_MAIN.default_options() if options is None else dict(options)
-    if opts['ratio_fixe'] is not None or opts['slant_fix'] is not None:
-        raise ValueError('%s the limb fit\'s circle: ratio_fixe / slant_fix give none' % what[1])
-    if opts['de-vignette']:
-        raise ValueError('%s the 16-bit disk: de-vignette leaves a float64 one' % what[2])
-    opts.update(save_fit=False, flag_display=False, _nolog=True, basefich0='')
-    rdr = file_or_reader if hasattr(file_or_reader, 'device_stack') else video_reader(file_or_reader)
-    if dist.is_sharded(rdr):
-        raise ValueError('%s is single-process: give it the whole scan, not a frame shard' % what[0])
-    shift = int(shift)
-    ih, iw = int(rdr.ih), int(rdr.iw)
-    with contextlib.redirect_stdout(io.StringIO()):               # the stages report on stdout
-        _, fit, _, _ = compute_mean_return_fit(rdr, opts, make_header(rdr), iw, ih, '')
-        shifts = list(dict.fromkeys([opts['ellipse_fit_shift'], shift]))
-        disks, mm = extract_disks(rdr, fit, shifts, flip_x=bool(opts['flip_x']), want_minmax=True)
-        disk_list = [DeviceImage(disks[i], minmax=None if mm is None else mm[i]) for i in range(len(shifts))]
-        own = shifts.index(shift)
-        frame, circle, ratio, phi, borders = ellipse_to_circle(disk_list[0], opts, '', need_image=own == 0)
-        if own != 0:
-            # (solex_process keeps the angle in degrees between the disks, Solex_recon.py:117: the same round trip)
-            frame = correct_image(disk_list[own], math.radians(math.degrees(phi)), ratio, np.array([-1.0, -1.0]), -1.0, opts)[0]
-        if opts['transversalium']:
-            frame = correct_transversalium2(frame, circle, borders, opts, 0, '')
-        h, w = to_device_u16(frame).shape
-        crop, _ = crop_plan(h, w, circle, opts)
-        (frame,), circle_out = crop_to_width([frame], circle, opts)
-    return {'image': to_device_u16(frame), 'circle': tuple(float(v) for v in circle_out), 'shift': shift, 'ratio': float(ratio),
-            'phi': float(phi), 'crop': crop}
-
-
 def flatten_scan(file_or_reader, options=None, shift=0, smooth=1, level=None, max_gain=8.0):
-    """A scan's disk at `shift` (scan_disk_and_circle), flattened by flatten_disk.  -> {'image', 'flat' (uint16 device tensors),
+    """A scan's disk at `shift` (disk.scan_disk), flattened by flatten_disk.  -> {'image', 'flat' (uint16 device tensors),
     'circle' (of the image), 'profile', 'gain', 'level', 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe / slant_fix (no
     limb fit, hence no circle), de-vignette (a float64 frame) and a frame-sharded reader."""
-    disk = scan_disk_and_circle(file_or_reader, options, shift)
-    image, circle_out = disk['image'], disk['circle']
+    scan = disk.scan_disk(file_or_reader, options, shift)
+    image, circle_out = scan['image'], scan['circle']
     flat, profile, gain = flatten_disk(image, circle_out, smooth, level, max_gain)
     used = float(level) if level is not None else float(default_level(filled_profile(profile, smooth)))
-    return {'image': image, 'flat': flat, 'circle': circle_out, 'profile': profile, 'gain': gain, 'level': used, 'shift': disk['shift'],
-            'ratio': disk['ratio'], 'phi': disk['phi'], 'crop': disk['crop'], 'smooth': int(smooth), 'max_gain': float(max_gain)}
+    return {'image': image, 'flat': flat, 'circle': circle_out, 'profile': profile, 'gain': gain, 'level': used, 'shift': scan['shift'],
+            'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop'], 'smooth': int(smooth), 'max_gain': float(max_gain)}
 
 
 # ---- command line ---------------------------------------------------------------------------------
 def main(argv=None):
-    from . import CLI_handler, SHG_MAIN
-    from .fits_io import make_header, write_fits
     from .linemaps import _print_json
-    from .png_io import write_png
     from .solex_util import output_path
     from .video_reader import video_reader
     p = argparse.ArgumentParser(prog='python -m solex_ser_recon_en_amd.flatten',
@@ -161,27 +108,14 @@ def main(argv=None):
     p.add_argument('--smooth', type=int, default=1, help='running mean over N rings (odd; default 1: none)')
     p.add_argument('--max-gain', type=float, default=8.0, help='the largest gain a ring may get (default 8)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the flat image (<base>_flat_clahe.png, ...)')
-    args, rest = p.parse_known_args(sys.argv[1:] if argv is None else list(argv))
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        p.error('flattening is single-process: run it without torchrun')
-    if args.smooth < 1 or args.smooth % 2 == 0:
-        p.error('--smooth must be odd and >= 1')
-    if not (math.isfinite(args.max_gain) and args.max_gain >= 0):
-        p.error('--max-gain must be finite and >= 0')
-    if any(a.startswith('-') and not a.startswith('--') and 'w' in a for a in rest):
-        p.error('-w is not a flatten flag: give the shift with --shift')
-    opts = SHG_MAIN.default_options()
-    try:
-        with contextlib.redirect_stdout(sys.stderr):            # the SHG_MAIN parser reports on stdout: keep it for the JSON line
-            files = CLI_handler.handle_CLI(opts, rest)
-    except ValueError as e:
-        p.error(str(e))
-    unknown = [a for a in rest if not a.startswith('-') and a not in files and not a.isdigit()]
-    if len(files) != 1 or unknown:
-        p.error('exactly one SER or AVI file is needed (got %s)' % (files + unknown))
-    path = files[0]
-    if not os.path.isfile(path):
-        p.error('no such file: %s' % path)
+
+    def checks(args):
+        if args.smooth < 1 or args.smooth % 2 == 0:
+            p.error('--smooth must be odd and >= 1')
+        if not (math.isfinite(args.max_gain) and args.max_gain >= 0):
+            p.error('--max-gain must be finite and >= 0')
+
+    args, opts, (path,) = disk.parse(p, argv, 'flatten', 'flattening', checks)
     try:
         rdr = video_reader(path)
         res = flatten_scan(rdr, opts, args.shift, args.smooth, None, args.max_gain)
@@ -189,15 +123,9 @@ def main(argv=None):
         print('error: %s' % e, file=sys.stderr)
         return 1
     stem = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift'])
-    k = opts['img_rotate'] // 90
-    flat = np.ascontiguousarray(np.rot90(_host_u(res['flat'].contiguous(), np.uint16), k))
-    out = {'shape': list(flat.shape), 'shift': res['shift'], 'smooth': res['smooth'], 'max_gain': res['max_gain'], 'png': None, 'fits': None,
+    flat, png, fits = disk.write_image(res['flat'], stem + '_flat', opts, rdr)
+    out = {'shape': list(flat.shape), 'shift': res['shift'], 'smooth': res['smooth'], 'max_gain': res['max_gain'], 'png': png, 'fits': fits,
            'clv': None}
-    out['png'] = output_path(stem + '_flat.png', opts)
-    write_png(out['png'], flat, 0)
-    if opts['save_fit']:
-        out['fits'] = output_path(stem + '_flat.fits', opts)
-        write_fits(out['fits'], flat, make_header(rdr))
     profile, gain, rad = res['profile'], res['gain'], res['circle'][2]
     out['clv'] = output_path(stem + '_clv.txt', opts)
     with open(out['clv'], 'w') as f:
@@ -207,17 +135,13 @@ def main(argv=None):
                                                 profile['median'][i], gain[i]))
     have = np.flatnonzero(profile['count'] > 0)
     # a pixel counts as saturated where the flat image holds 65535 and the image did not
-    saturated = int(((flat == 65535) & (np.rot90(_host_u(res['image'].contiguous(), np.uint16), k) != 65535)).sum())
+    image = np.rot90(disk.host_u(res['image'].contiguous(), np.uint16), opts['img_rotate'] // 90)
     out.update(rings=int(gain.shape[0]), level=res['level'],
                centre_median=float(profile['median'][have[0]]) if have.size else None,
-               limb_median=float(profile['median'][have[-1]]) if have.size else None, saturated=saturated)
+               limb_median=float(profile['median'][have[-1]]) if have.size else None,
+               saturated=int(((flat == 65535) & (image != 65535)).sum()))
     if args.contrast:
-        from . import outputs
-        from .solex_util import image_process
-        with contextlib.redirect_stdout(sys.stderr):
-            image_process(res['flat'], res['circle'], opts, make_header(rdr), stem + '_flat')
-            outputs.flush()
-        out['contrast'] = stem + '_flat'
+        out['contrast'] = disk.contrast_products(res['flat'], res['circle'], opts, rdr, stem + '_flat')
     return _print_json(out, res)
 
 

@@ -219,7 +219,7 @@ def _cli(p, argv, single, w_flag, extra_checks=None):
     """The command line the CLIs share: parse, validate (`single`, `w_flag`: the refusals under torchrun and of -w; after --range
     the checks of --shift / --line when the parser has them, then extra_checks(args)), the SHG_MAIN flags, the one file and the
     atlas -> (args, opts, path, atlas or None).  Errors exit through p.error."""
-    from . import CLI_handler, SHG_MAIN, spectral
+    from . import CLI_handler, spectral
     args, rest = p.parse_known_args(sys.argv[1:] if argv is None else list(argv))
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         p.error(single)
@@ -246,18 +246,7 @@ def _cli(p, argv, single, w_flag, extra_checks=None):
             p.error('--%s must be positive' % name)
     if any(a.startswith('-') and 'w' in a for a in rest):
         p.error(w_flag)
-    opts = SHG_MAIN.default_options()
-    try:
-        with contextlib.redirect_stdout(sys.stderr):            # the SHG_MAIN parser reports on stdout: keep it for the JSON line
-            files = CLI_handler.handle_CLI(opts, rest)
-    except ValueError as e:
-        p.error(str(e))
-    unknown = [a for a in rest if not a.startswith('-') and a not in files and not a.isdigit()]
-    if len(files) != 1 or unknown:
-        p.error('exactly one SER or AVI file is needed (got %s)' % (files + unknown))
-    path = files[0]
-    if not os.path.isfile(path):
-        p.error('no such file: %s' % path)
+    opts, (path,) = CLI_handler.options_and_files(p, rest)
     try:
         atlas = spectral.load_atlas(args.atlas) if args.atlas is not None else None
     except (OSError, KeyError, ValueError) as e:

@@ -34,6 +34,22 @@ def _img(t, what, dtype=None):
     return t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)
 
 
+def _out_like(out, h, w, dtype, device, what='out'):
+    """(the tensor, ptr, pitch) of an [h, w] output view of `dtype`: the caller's `out`, or a new one when it is None."""
+    if out is None:
+        out = torch.empty((h, w), dtype=dtype, device=device)
+    ptr, oh, ow, pitch = _img(out, what, dtype)
+    if (oh, ow) != (h, w):
+        raise ValueError('%s must be a %s [%d, %d] view' % (what, str(dtype).split('.')[-1], h, w))
+    return out, ptr, pitch
+
+
+def _workspace(workspace, need, device):
+    """(the tensor, its bytes): the caller's workspace, or a new uint8 one of `need` bytes when it is None."""
+    ws = torch.empty(need, dtype=torch.uint8, device=device) if workspace is None else _dev(workspace, 'workspace')
+    return ws, ws.numel() * ws.element_size()
+
+
 def pitched_u16(h, w, device, align=64):
     """uint16 image whose row pitch is a multiple of `align` elements (128 B rows)."""
     pitch = (w + align - 1) // align * align
@@ -962,11 +978,7 @@ def map_detrend(m, plane, display_range=None, out=None):
     p3 = np.ascontiguousarray([float(v) for v in plane], dtype=np.float64)
     if p3.size != 3:
         raise ValueError('plane is (a, b, g)')
-    if out is None:
-        out = torch.empty((h, w), dtype=torch.float32, device=m.device)
-    optr, oh, ow, opitch = _img(out, 'out', torch.float32)
-    if (oh, ow) != (h, w):
-        raise ValueError('out must be a float32 [%d, %d] view' % (h, w))
+    out, optr, opitch = _out_like(out, h, w, torch.float32, m.device)
     png = None if display_range is None else torch.empty((h, w), dtype=torch.uint16, device=m.device)
     _lib.check(lib.shg_map_detrend(ptr, h, w, pitch, _host_ptr(p3), optr, opitch, None if png is None else png.data_ptr(), w,
                                    0.0 if display_range is None else float(display_range), _stream()), 'shg_map_detrend')
@@ -984,6 +996,14 @@ def _circle3(circle):
     return c3, int(np.floor(c3[2])) + 1
 
 
+def _circle3_or_none(circle):
+    """The optional disk of a pixel set as a host float64 [3] array, or None."""
+    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    if c3 is not None and c3.size != 3:
+        raise ValueError('circle is (cx, cy, r)')
+    return c3
+
+
 def ring_medians_u16(img, circle, out=None):
     """shg_ring_medians_u16: for each of the K = floor(r) + 1 one-pixel rings around the centre of `circle` (cx, cy, r), over the
     pixels of the uint16 image that lie on the disk -> (count uint32 [K], lo uint16 [K], hi uint16 [K]) on the image's device: the
@@ -998,10 +1018,9 @@ def ring_medians_u16(img, circle, out=None):
     for t, dt in ((count, torch.uint32), (lo, torch.uint16), (hi, torch.uint16)):
         if _dev(t, 'out').dtype != dt or tuple(t.shape) != (k,) or not t.is_contiguous():
             raise ValueError('out is (count uint32 [%d], lo uint16 [%d], hi uint16 [%d]), contiguous' % (k, k, k))
-    need = lib.shg_ring_medians_u16_workspace_bytes(k)
-    ws = torch.empty(need, dtype=torch.uint8, device=img.device)
-    _lib.check(lib.shg_ring_medians_u16(ptr, h, w, pitch, _host_ptr(c3), k, count.data_ptr(), lo.data_ptr(), hi.data_ptr(),
-                                        ws.data_ptr(), need, _stream()), 'shg_ring_medians_u16')
+    ws, ws_bytes = _workspace(None, lib.shg_ring_medians_u16_workspace_bytes(k), img.device)
+    _lib.check(lib.shg_ring_medians_u16(ptr, h, w, pitch, _host_ptr(c3), k, count.data_ptr(), lo.data_ptr(), hi.data_ptr(), ws.data_ptr(),
+                                        ws_bytes, _stream()), 'shg_ring_medians_u16')
     return count, lo, hi
 
 
@@ -1014,11 +1033,7 @@ def ring_flatten_u16(img, circle, gain, out=None):
     g = np.ascontiguousarray(gain, dtype=np.float64).reshape(-1)
     if g.size != k:
         raise ValueError('gain must hold %d values (floor(r) + 1), got %d' % (k, g.size))
-    if out is None:
-        out = torch.empty((h, w), dtype=torch.uint16, device=img.device)
-    optr, oh, ow, opitch = _img(out, 'out', torch.uint16)
-    if (oh, ow) != (h, w):
-        raise ValueError('out must be a uint16 [%d, %d] view' % (h, w))
+    out, optr, opitch = _out_like(out, h, w, torch.uint16, img.device)
     _lib.check(lib.shg_ring_flatten_u16(ptr, h, w, pitch, _host_ptr(c3), _host_ptr(g), k, optr, opitch, _stream()),
                'shg_ring_flatten_u16')
     return out
@@ -1044,18 +1059,10 @@ def stack_combine_u16(images, transforms, shape, mode='sigma', kappa=2.5, iterat
     geo = [_img(t, 'image', torch.uint16) for t in images]
     dev = images[0].device
     oh, ow = int(shape[0]), int(shape[1])
-    if out is None:
-        out = torch.empty((oh, ow), dtype=torch.uint16, device=dev)
-    optr, h, w, opitch = _img(out, 'out', torch.uint16)
-    if (h, w) != (oh, ow):
-        raise ValueError('out must be a uint16 [%d, %d] view' % (oh, ow))
+    out, optr, opitch = _out_like(out, oh, ow, torch.uint16, dev)
     cptr, cpitch = None, 0
-    if count is None and want_count:
-        count = torch.empty((oh, ow), dtype=torch.uint8, device=dev)
-    if count is not None:
-        cptr, h, w, cpitch = _img(count, 'count', torch.uint8)
-        if (h, w) != (oh, ow):
-            raise ValueError('count must be a uint8 [%d, %d] view' % (oh, ow))
+    if count is not None or want_count:
+        count, cptr, cpitch = _out_like(count, oh, ow, torch.uint8, dev, 'count')
     ptrs = (ctypes.c_void_p * n)(*[g[0] for g in geo])
     dims = np.ascontiguousarray([[g[1], g[2], g[3]] for g in geo], dtype=np.int64)
     _lib.check(lib.shg_stack_combine_u16(ptrs, _host_ptr(dims), _host_ptr(xf), n, STACK_MODES[mode], float(kappa), int(iterations), optr,
@@ -1075,9 +1082,7 @@ def shift_ssd_u16(ref, img, search, circle=None, out=None):
     s = int(search)
     if not 0 <= s <= 8:
         raise ValueError('search must be 0 to 8, got %r' % (search,))
-    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
-    if c3 is not None and c3.size != 3:
-        raise ValueError('circle is (cx, cy, r)')
+    c3 = _circle3_or_none(circle)
     words = (2 * s + 1) ** 2 + 1
     if out is None:
         out = torch.empty(words, dtype=torch.int64, device=ref.device)
@@ -1102,17 +1107,12 @@ def wavelet_sharpen_u16(img, gain_q8, threshold_q6=None, out=None, want_planes=F
     if g.min() < 0 or g.max() > 4096 or t.min() < 0 or t.max() > 1 << 22:
         raise ValueError('gain_q8 lies in [0, 4096] and threshold_q6 in [0, 2^22]')
     g, t = g.astype(np.int32), t.astype(np.int32)
-    if out is None:
-        out = torch.empty((h, w), dtype=torch.uint16, device=img.device)
-    optr, oh, ow, opitch = _img(out, 'out', torch.uint16)
-    if (oh, ow) != (h, w):
-        raise ValueError('out must be a uint16 [%d, %d] view' % (h, w))
+    out, optr, opitch = _out_like(out, h, w, torch.uint16, img.device)
     planes = torch.empty((levels + 1, h, w), dtype=torch.int32, device=img.device) if want_planes else None
-    need = lib.shg_wavelet_workspace_bytes(h, w, levels)
-    ws = torch.empty(need, dtype=torch.uint8, device=img.device) if workspace is None else _dev(workspace, 'workspace')
+    ws, ws_bytes = _workspace(workspace, lib.shg_wavelet_workspace_bytes(h, w, levels), img.device)
     _lib.check(lib.shg_wavelet_sharpen_u16(ptr, h, w, pitch, levels, _host_ptr(g), _host_ptr(t), optr, opitch,
-                                           None if planes is None else planes.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
-                                           _stream()), 'shg_wavelet_sharpen_u16')
+                                           None if planes is None else planes.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+               'shg_wavelet_sharpen_u16')
     return out, planes
 
 
@@ -1121,15 +1121,12 @@ def wavelet_noise_u16(img, circle=None, out=None, workspace=None):
     pixel) -> int64 [2] on the image's device: the lower median of |w_1|, the finest wavelet layer, in Q6 (64 a count), and the
     number of pixels (0 and 0 for an empty set).  out: the caller's, overwritten."""
     ptr, h, w, pitch = _img(img, 'img', torch.uint16)
-    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
-    if c3 is not None and c3.size != 3:
-        raise ValueError('circle is (cx, cy, r)')
+    c3 = _circle3_or_none(circle)
     if out is None:
         out = torch.empty(2, dtype=torch.int64, device=img.device)
     if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (2,) or not out.is_contiguous():
         raise ValueError('out must be a contiguous int64 [2] tensor')
-    need = lib.shg_wavelet_workspace_bytes(h, w, 1)
-    ws = torch.empty(need, dtype=torch.uint8, device=img.device) if workspace is None else _dev(workspace, 'workspace')
-    _lib.check(lib.shg_wavelet_noise_u16(ptr, h, w, pitch, _host_ptr(c3), out.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
-                                         _stream()), 'shg_wavelet_noise_u16')
+    ws, ws_bytes = _workspace(workspace, lib.shg_wavelet_workspace_bytes(h, w, 1), img.device)
+    _lib.check(lib.shg_wavelet_noise_u16(ptr, h, w, pitch, _host_ptr(c3), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+               'shg_wavelet_noise_u16')
     return out

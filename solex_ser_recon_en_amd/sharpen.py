@@ -10,13 +10,13 @@ Out of scope: limb protection (the limb's edge overshoots into the sky), deconvo
 command lines.
 """
 import argparse
-import contextlib
-import json
 import math
 import os
 import sys
 
 import numpy as np
+
+from . import disk
 
 MAX_LEVELS = 6
 MAX_GAIN = 16.0
@@ -138,14 +138,13 @@ def wavelet_planes(image, levels):
 
 
 def sharpen_scan(file_or_reader, options=None, shift=0, gains=DEFAULT_GAINS, denoise=DEFAULT_DENOISE, sigma=None, region=DEFAULT_REGION):
-    """A scan's disk at `shift` (flatten.scan_disk_and_circle, with its refusals: ratio_fixe / slant_fix, de-vignette, a frame
+    """A scan's disk at `shift` (disk.scan_disk, with its refusals: ratio_fixe / slant_fix, de-vignette, a frame
     shard), sharpened by sharpen_disk with the noise measured inside region * rad of the fitted circle -> {'image', 'sharp' (uint16
     device tensors), 'circle', 'record', 'shift', 'ratio', 'phi', 'crop'}."""
-    from .flatten import scan_disk_and_circle
-    disk = scan_disk_and_circle(file_or_reader, options, shift, ('sharpening', 'sharpening needs', 'sharpening takes'))
-    sharp, record = sharpen_disk(disk['image'], gains, denoise, sigma, disk['circle'], region)
-    return {'image': disk['image'], 'sharp': sharp, 'circle': disk['circle'], 'record': record, 'shift': disk['shift'],
-            'ratio': disk['ratio'], 'phi': disk['phi'], 'crop': disk['crop']}
+    scan = disk.scan_disk(file_or_reader, options, shift, 'sharpening')
+    sharp, record = sharpen_disk(scan['image'], gains, denoise, sigma, scan['circle'], region)
+    return {'image': scan['image'], 'sharp': sharp, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
+            'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
 
 
 # ---- command line ---------------------------------------------------------------------------------
@@ -163,11 +162,8 @@ class _PngHeaderSource:
 
 
 def main(argv=None):
-    from . import CLI_handler, SHG_MAIN
-    from .fits_io import make_header, write_fits
-    from .flatten import _host_u
-    from .png_io import read_png_gray, write_png
-    from .solex_util import output_path
+    from .linemaps import _print_json
+    from .png_io import read_png_gray
     from .video_reader import video_reader
     p = argparse.ArgumentParser(
         prog='python -m solex_ser_recon_en_amd.sharpen',
@@ -188,44 +184,29 @@ def main(argv=None):
     p.add_argument('--region', type=float, default=DEFAULT_REGION, help='fraction of the radius the noise is measured within (default %g)' % DEFAULT_REGION)
     p.add_argument('--shift', type=int, default=0, help='pixel shift of a scan\'s disk (the -w shift; default 0: the line centre)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the sharpened image (<base>_sharp_clahe.png, ...)')
-    args, rest = p.parse_known_args(sys.argv[1:] if argv is None else list(argv))
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        p.error('sharpening is single-process: run it without torchrun')
-    if any(a.startswith('-') and not a.startswith('--') and 'w' in a for a in rest):
-        p.error('-w is not a sharpen flag: give the shift with --shift')
-    levels = args.levels
-    if levels is None:
-        levels = len(args.gains) if args.gains else DEFAULT_LEVELS
-    if not 1 <= levels <= MAX_LEVELS:
-        p.error('--levels is 1 to %d' % MAX_LEVELS)
-    gains = list(DEFAULT_GAINS[:levels]) if args.gains is None else args.gains
-    denoise = list(DEFAULT_DENOISE[:levels]) if args.denoise is None else args.denoise
-    if len(gains) > levels or len(denoise) > levels:
-        p.error('more --gains or --denoise values than --levels')
-    gains = gains + [1.0] * (levels - len(gains))
-    denoise = denoise + [0.0] * (levels - len(denoise))
-    if args.circle is not None and len(args.circle) != 3:
-        p.error('--circle is cx,cy,rad')
-    try:
-        quantise_gains(gains)
-        thresholds(0.0 if args.sigma is None else args.sigma, denoise, levels)
-        _noise_circle(args.circle, args.region)
-    except ValueError as e:
-        p.error(str(e))
-    opts = SHG_MAIN.default_options()
-    pngs = [a for a in rest if not a.startswith('-') and a.lower().endswith('.png')]       # (the SHG_MAIN parser knows scans only)
-    rest = [a for a in rest if a not in pngs]
-    try:
-        with contextlib.redirect_stdout(sys.stderr):            # the SHG_MAIN parser reports on stdout: keep it for the JSON line
-            files = CLI_handler.handle_CLI(opts, rest) + pngs
-    except ValueError as e:
-        p.error(str(e))
-    unknown = [a for a in rest if not a.startswith('-') and a not in files and not a.isdigit()]
-    if len(files) != 1 or unknown:
-        p.error('exactly one SER, AVI or PNG file is needed (got %s)' % (files + unknown))
-    path = files[0]
-    if not os.path.isfile(path):
-        p.error('no such file: %s' % path)
+
+    def checks(args):
+        levels = args.levels
+        if levels is None:
+            levels = len(args.gains) if args.gains else DEFAULT_LEVELS
+        if not 1 <= levels <= MAX_LEVELS:
+            p.error('--levels is 1 to %d' % MAX_LEVELS)
+        gains = list(DEFAULT_GAINS[:levels]) if args.gains is None else args.gains
+        denoise = list(DEFAULT_DENOISE[:levels]) if args.denoise is None else args.denoise
+        if len(gains) > levels or len(denoise) > levels:
+            p.error('more --gains or --denoise values than --levels')
+        args.gains = gains + [1.0] * (levels - len(gains))
+        args.denoise = denoise + [0.0] * (levels - len(denoise))
+        if args.circle is not None and len(args.circle) != 3:
+            p.error('--circle is cx,cy,rad')
+        try:
+            quantise_gains(args.gains)
+            thresholds(0.0 if args.sigma is None else args.sigma, args.denoise, levels)
+            _noise_circle(args.circle, args.region)
+        except ValueError as e:
+            p.error(str(e))
+
+    args, opts, (path,) = disk.parse(p, argv, 'sharpen', 'sharpening', checks, need='exactly one SER, AVI or PNG file is needed', png=True)
     is_png = path.lower().endswith('.png')
     try:
         if is_png:
@@ -233,41 +214,29 @@ def main(argv=None):
             if img.dtype != np.uint16 or img.ndim != 2:
                 raise ValueError('%s is not a 16-bit grey PNG' % path)
             circle = None if args.circle is None else tuple(args.circle)
-            sharp, record = sharpen_disk(img, gains, denoise, args.sigma, circle, args.region)
+            sharp, record = sharpen_disk(img, args.gains, args.denoise, args.sigma, circle, args.region)
             header_source = _PngHeaderSource(*img.shape)
-            stem, k = os.path.splitext(path)[0], 0              # (a product is already rotated)
-            opts['img_rotate'] = 0
+            stem = os.path.splitext(path)[0]
+            opts['img_rotate'] = 0                              # (a product is already rotated)
             res = {'circle': circle if circle is not None else (-1, -1, -1), 'ratio': None, 'phi': None, 'crop': None}
         else:
             if args.circle is not None:
                 raise ValueError('--circle goes with a PNG: a scan brings its own limb fit')
             header_source = video_reader(path)
-            res = sharpen_scan(header_source, opts, args.shift, gains, denoise, args.sigma, args.region)
+            res = sharpen_scan(header_source, opts, args.shift, args.gains, args.denoise, args.sigma, args.region)
             sharp, record = res['sharp'], res['record']
-            stem, k = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift']), opts['img_rotate'] // 90
+            stem = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift'])
     except ValueError as e:
         print('error: %s' % e, file=sys.stderr)
         return 1
-    host = np.ascontiguousarray(np.rot90(_host_u(sharp.contiguous(), np.uint16), k))
+    host, png, fits = disk.write_image(sharp, stem + '_sharp', opts, header_source)
     out = {'input': path, 'shape': list(host.shape), 'levels': record['levels'], 'gains': record['gains'], 'denoise': record['denoise'],
            'sigma': record['sigma'], 'median': None if record['median_q6'] is None else record['median_q6'] / 64.0,
-           'pixels': record['pixels'], 'thresholds': record['thresholds'], 'shift': None if is_png else res['shift'], 'png': None,
-           'fits': None, 'contrast': None}
-    out['png'] = output_path(stem + '_sharp.png', opts)
-    write_png(out['png'], host, 0)
-    if opts['save_fit']:
-        out['fits'] = output_path(stem + '_sharp.fits', opts)
-        write_fits(out['fits'], host, make_header(header_source))
+           'pixels': record['pixels'], 'thresholds': record['thresholds'], 'shift': None if is_png else res['shift'], 'png': png,
+           'fits': fits, 'contrast': None}
     if args.contrast:
-        from . import outputs
-        from .solex_util import image_process
-        with contextlib.redirect_stdout(sys.stderr):
-            image_process(sharp, tuple(res['circle']), opts, make_header(header_source), stem + '_sharp')
-            outputs.flush()
-        out['contrast'] = stem + '_sharp'
-    out.update(circle=list(res['circle']), ratio=res['ratio'], phi=res['phi'], crop=None if res['crop'] is None else list(res['crop']))
-    print(json.dumps(out), flush=True)
-    return 0
+        out['contrast'] = disk.contrast_products(sharp, tuple(res['circle']), opts, header_source, stem + '_sharp')
+    return _print_json(out, res)
 
 
 if __name__ == '__main__':

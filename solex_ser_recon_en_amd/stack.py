@@ -8,12 +8,13 @@ the arithmetic between them is host float64, written step by step so that tests/
         [--iterations I] [--search S] [--coverage] [--contrast] [SHG_MAIN flags]
 """
 import argparse
-import contextlib
 import math
 import os
 import sys
 
 import numpy as np
+
+from . import disk
 
 MAX_SCANS = 32
 MAX_SEARCH = 8
@@ -23,8 +24,7 @@ MODES = ('mean', 'median', 'sigma')
 def scan_disk(file_or_reader, options=None, shift=0):
     """A scan's disk at `shift` and its circle, as flatten_scan computes them before it flattens -> {'image' (a uint16 device
     tensor), 'circle', 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe / slant_fix, de-vignette and a frame shard."""
-    from .flatten import scan_disk_and_circle
-    return scan_disk_and_circle(file_or_reader, options, shift, ('stacking', 'stacking needs', 'stacking takes'))
+    return disk.scan_disk(file_or_reader, options, shift, 'stacking')
 
 
 def disk_level(image, circle):
@@ -178,9 +178,6 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
 
 # ---- command line ---------------------------------------------------------------------------------
 def main(argv=None):
-    from . import CLI_handler, SHG_MAIN
-    from .fits_io import make_header, write_fits
-    from .flatten import _host_u
     from .linemaps import _print_json
     from .png_io import write_png
     from .solex_util import output_path
@@ -199,63 +196,43 @@ def main(argv=None):
     p.add_argument('--search', type=int, default=8, help='half-width of the offset search in pixels (0 to 8; default 8)')
     p.add_argument('--coverage', action='store_true', help='also the number of frames behind every pixel (<base>_stack_count.png)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the stack (<base>_stack_clahe.png, ...)')
-    args, rest = p.parse_known_args(sys.argv[1:] if argv is None else list(argv))
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        p.error('stacking is single-process: run it without torchrun')
-    if not args.kappa >= 1:
-        p.error('--kappa must be >= 1')
-    if not 1 <= args.iterations <= 3:
-        p.error('--iterations must be 1 to 3')
-    if not 0 <= args.search <= MAX_SEARCH:
-        p.error('--search must be 0 to %d' % MAX_SEARCH)
-    if any(a.startswith('-') and not a.startswith('--') and 'w' in a for a in rest):
-        p.error('-w is not a stack flag: give the shift with --shift')
-    opts = SHG_MAIN.default_options()
-    try:
-        with contextlib.redirect_stdout(sys.stderr):            # the SHG_MAIN parser reports on stdout: keep it for the JSON line
-            files = CLI_handler.handle_CLI(opts, rest)
-    except ValueError as e:
-        p.error(str(e))
-    unknown = [a for a in rest if not a.startswith('-') and a not in files and not a.isdigit()]
-    if len(files) < 2 or unknown:
-        p.error('at least two SER or AVI files are needed (got %s)' % (files + unknown))
-    if len(files) > MAX_SCANS:
-        p.error('at most %d scans are stacked at a time (got %d)' % (MAX_SCANS, len(files)))
-    if not 0 <= args.reference < len(files):
-        p.error('--reference must be 0 to %d' % (len(files) - 1))
-    for path in files:
-        if not os.path.isfile(path):
-            p.error('no such file: %s' % path)
+
+    def checks(args):
+        if not args.kappa >= 1:
+            p.error('--kappa must be >= 1')
+        if not 1 <= args.iterations <= 3:
+            p.error('--iterations must be 1 to 3')
+        if not 0 <= args.search <= MAX_SEARCH:
+            p.error('--search must be 0 to %d' % MAX_SEARCH)
+
+    def file_checks(args, files):
+        if len(files) > MAX_SCANS:
+            p.error('at most %d scans are stacked at a time (got %d)' % (MAX_SCANS, len(files)))
+        if not 0 <= args.reference < len(files):
+            p.error('--reference must be 0 to %d' % (len(files) - 1))
+
+    args, opts, files = disk.parse(p, argv, 'stack', 'stacking', checks, file_checks, least=2, most=None,
+                                   need='at least two SER or AVI files are needed')
     try:
         res = stack_scans(files, opts, args.shift, args.reference, args.mode, args.kappa, args.iterations, args.search)
     except ValueError as e:
         print('error: %s' % e, file=sys.stderr)
         return 1
     ref_path = files[args.reference]
+    rdr = video_reader(ref_path)                                    # (for the headers: the scans themselves were read above)
     stem = '%s_shift=%d_stack' % (os.path.splitext(ref_path)[0], res['shift'])
-    k = opts['img_rotate'] // 90
-    stack = np.ascontiguousarray(np.rot90(_host_u(res['stack'].contiguous(), np.uint16), k))
+    stack, png, fits = disk.write_image(res['stack'], stem, opts, rdr)
     out = {'shape': list(stack.shape), 'mode': res['mode'], 'kappa': res['kappa'], 'iterations': res['iterations'], 'shift': res['shift'],
            'reference': res['reference'], 'files': [files[i] for i in res['used']], 'rejected': [files[i] for i in res['rejected']],
            'frames': [{'file': files[i], 'scale': rec['s'], 'offset': list(rec['offset']), 'gain': rec['gain'],
                        'rms': None if rec['rejected'] and not rec['pixels'] else math.sqrt(rec['ssd_per_pixel']),
                        'rejected': rec['rejected']} for i, rec in enumerate(res['records'])],
-           'png': None, 'fits': None, 'count_png': None}
-    out['png'] = output_path(stem + '.png', opts)
-    write_png(out['png'], stack, 0)
-    if opts['save_fit']:
-        out['fits'] = output_path(stem + '.fits', opts)
-        write_fits(out['fits'], stack, make_header(video_reader(ref_path)))
+           'png': png, 'fits': fits, 'count_png': None}
     if args.coverage:
         out['count_png'] = output_path(stem + '_count.png', opts)
-        write_png(out['count_png'], np.ascontiguousarray(np.rot90(res['count'].contiguous().cpu().numpy(), k)), 0)
+        write_png(out['count_png'], np.ascontiguousarray(np.rot90(res['count'].contiguous().cpu().numpy(), opts['img_rotate'] // 90)), 0)
     if args.contrast:
-        from . import outputs
-        from .solex_util import image_process
-        with contextlib.redirect_stdout(sys.stderr):
-            image_process(res['stack'], res['circle'], opts, make_header(video_reader(ref_path)), stem)
-            outputs.flush()
-        out['contrast'] = stem
+        out['contrast'] = disk.contrast_products(res['stack'], res['circle'], opts, rdr, stem)
     return _print_json(out, res)
 
 
