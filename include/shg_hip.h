@@ -391,6 +391,48 @@ int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_
 int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w, int S,
                       const double* circle3, uint64_t* ssd, shg_stream_t stream);
 
+/* ---- local alignment points: one table of sums of squared differences a patch, and the combine that bends each source by a
+ * displacement field (not reference stages; tests/align_ref.py restates both calls in NumPy, bit for bit).
+ * shg_patch_ssd_u16: ref and img are uint16 images of h x w on one grid (pitches ref_pitch, img_pitch); points (device) = [n][2]
+ * int32 (row pr, column pc), the centres, which may lie anywhere, also outside the image.  B is the patch's half-size (the patch is
+ * (2 B + 1)^2), S the search.  The pixel set of point p, the same for every offset: every (r, c) with |r - pr| <= B, |c - pc| <= B,
+ * S <= c < w - S and S <= r < h - S that, given a circle3 (host; NULL or (-1, -1, -1): no circle), is ON THE DISK by the test of the
+ * flatten section above.  With W = (2 S + 1)^2 + 3, out (device) = [n][W] uint64, and for every integer offset (u, v), |u|, |v| <= S:
+ *   out[p][(v + S) * (2 S + 1) + (u + S)] = the sum over the set of (ref[r][c] - img[r + v][c + u])^2;
+ *   out[p][(2 S + 1)^2] = the number of pixels in the set;  out[p][(2 S + 1)^2 + 1] = the sum of ref[r][c] over the set;
+ *   out[p][(2 S + 1)^2 + 2] = the sum of ref[r][c]^2 over the set.
+ * A term is below 2^32 and a set holds at most 65^2 = 4225 pixels: every sum stays below 2^45 < 2^64.  All sums are integers and every
+ * word of out is written by one plain store: the result depends neither on the launch grid nor on any order, and the call needs no
+ * clearing pass.  An empty set gives a row of zeros; two equal points give two equal rows.  1 <= n <= 2^23 = 8 388 608, 1 <= B <= 32,
+ * 0 <= S <= 8, else SHG_E_ARG.  1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG for a null pointer, a pitch < w, a circle that
+ * is not finite, and an out that overlaps ref, img or points.  On any error nothing is written. */
+int shg_patch_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w,
+                      const int32_t* points, int64_t n, int B, int S, const double* circle3, uint64_t* out, shg_stream_t stream);
+
+/* shg_stack_combine_field_u16: shg_stack_combine_u16 with a displacement field a source.  host_srcs, host_dims3, host_xform4, n, mode,
+ * kappa, iterations, out, count and their pitches are that call's.  host_fields (host): n device pointers, each NULL (no field for
+ * that source) or a float64 array [gh][gw][2] that starts on 16 bytes: (dx, dy) at the lattice node (j, i), which sits at the output
+ * pixel (r, c) = (j * step, i * step).  The lattice is one for all sources and must cover the grid: gh = (oh - 1 + step - 1) / step + 1
+ * and gw = (ow - 1 + step - 1) / step + 1 in integer division.  Everything is float64, one IEEE operation a step, no contraction.
+ * For the output pixel in row r, column c:
+ *   j = r / step (integer division), j1 = min(j + 1, gh - 1), fy = (double)(r - j * step) / (double)step;
+ *   i = c / step, i1 = min(i + 1, gw - 1), fx = (double)(c - i * step) / (double)step;
+ * and for source s with a field F, per component k = 0 (dx), 1 (dy), with a = F[j][i][k], b = F[j][i1][k], c' = F[j1][i][k],
+ * d = F[j1][i1][k]:
+ *   top = a + (b - a) * fx;  bot = c' + (d - c') * fx;  d_k = top + (bot - top) * fy;
+ *   sx = tx + s * ((double)c + dx);  sy = ty + s * ((double)r + dy);
+ * without a field sx = tx + s * (double)c, sy = ty + s * (double)r.  Presence, the bilinear sample, the gain, the three modes, the
+ * rounding and the count are then exactly shg_stack_combine_u16's.  A displacement that is not finite makes sx or sy fail the
+ * presence test: the sample is absent (so are the samples of every pixel whose cell has such a node, whatever its weight: inf * 0
+ * is not a number).  A NULL field and a field of zeros give shg_stack_combine_u16's result bit for bit ((double)c + 0.0 is (double)c).
+ * 8 <= step <= 128, else SHG_E_ARG.  SHG_E_ARG also for a null host_fields, a gh or gw other than the above, a field that does not
+ * start on 16 bytes, and an output or count plane that overlaps a field; every limit and code of shg_stack_combine_u16 holds.  On
+ * any error nothing is written.  The call allocates nothing, waits for nothing and copies nothing from the device. */
+int shg_stack_combine_field_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
+                                const double* const* host_fields, int64_t gh, int64_t gw, int step, int n, int mode, double kappa,
+                                int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
+                                int64_t count_pitch, shg_stream_t stream);
+
 /* ---- sharpening a disk: the undecimated B3-spline ("a trous") wavelet layers of a 16-bit image, one gain a layer and a soft
  * noise gate a layer (not a reference stage; tests/sharpen_ref.py restates all of it in NumPy, bit for bit).  Everything is an
  * integer: the result depends neither on the launch grid, nor on how levels are fused, nor on the order of anything.

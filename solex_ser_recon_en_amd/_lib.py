@@ -106,6 +106,9 @@ SIGNATURES = {
     'shg_ring_flatten_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
     'shg_stack_combine_u16': (c_int, [P, P, P, c_int, c_int, c_double, c_int, P, c_int64, c_int64, c_int64, P, c_int64, P]),
     'shg_shift_ssd_u16': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, c_int, P, P, P]),
+    'shg_patch_ssd_u16': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, c_int64, c_int, c_int, P, P, P]),
+    'shg_stack_combine_field_u16': (c_int, [P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, c_double, c_int, P, c_int64, c_int64, c_int64,
+                                            P, c_int64, P]),
     'shg_wavelet_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int]),
     'shg_wavelet_sharpen_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, P, P, P, c_int64, P, P, c_size_t, P]),
     'shg_wavelet_noise_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, c_size_t, P]),

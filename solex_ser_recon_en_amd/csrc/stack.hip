@@ -8,11 +8,18 @@
 // and for those of the lanes beside it, into the same cache lines (s is within a few per cent of 1), and the eight results leave
 // in one 16-byte store (the counts in one 8-byte store) where pointer and pitch allow, element by element otherwise.  The source
 // count and the per-source records are wave-uniform: they are read from the kernel's arguments (32 records of 56 bytes), where
-// they are used (see k_stack_combine on why not once a thread).  The samples of a pixel sit in a private array that is only ever
+// they are used (see combine_octet on why not once a thread).  The samples of a pixel sit in a private array that is only ever
 // indexed by compile-time constants -- the kernel is a template on a capacity of 4 / 8 / 16 / 32 sources and on the mode, every
 // loop over the array is unrolled, a bit mask says which samples are present or kept -- so the array lives in registers: no
 // scratch.  The median pads the absent samples with +inf, runs a fixed bitonic network of compare-exchanges whose indices are
 // template arguments and picks its two ranks by masking the samples' bits.
+//
+// Combine with a displacement field a source (shg_stack_combine_field_u16): the same code, a template on whether there are
+// fields, under a kernel of its own that takes them as a second argument.  The lattice is one for all sources: the thread finds
+// its row's cell and weight once, its column's cell once a column (the remainder walks along with the column: step >= 8 = a
+// thread's columns, so it wraps once at most), and a source with a field costs four 16-byte node loads and two bilinear
+// interpolations before its sample; a null field costs a scalar test.  Without fields none of this is compiled:
+// k_stack_combine<CAP, MODE> is the kernel it was.
 //
 // SSD: a workgroup walks 64 x 16 tiles; it holds the tile of img with a border of S pixels in LDS and its own four pixels of ref
 // in registers, and for each of the (2 S + 1)^2 offsets sums the squared differences of its pixels (a term is below 2^32, the sum
@@ -53,7 +60,35 @@ struct CombineArgs {
 };
 static_assert(sizeof(CombineArgs) <= 4096, "kernel arguments");
 
-// The sample of source `s` at the output pixel (rd, cd): false when it is absent.
+// A displacement field a source on one lattice: nodes at (j step, i step), (dx, dy) a node, null for none.  A kernel argument of
+// its own: the compiler reads a by-value struct from the argument segment only while it counts fewer than 300 accesses to it --
+// beyond that it copies the struct to scratch first -- and the records' 32 x 8 are most of that.
+struct FieldArgs {
+    const double* field[kMaxSources];
+    int gh, gw, step;
+};
+static_assert(sizeof(CombineArgs) + sizeof(FieldArgs) <= 4096, "kernel arguments");
+constexpr int kMinStep = 8, kMaxStep = 128;
+static_assert(kMinStep >= 8, "a thread's eight columns cross one lattice line at most");
+
+// A pixel's place on the lattice: the element offsets of its cell's four nodes and its two weights.
+struct Cell {
+    int n00, n01, n10, n11;
+    double fx, fy;
+};
+
+// The displacement of field `f` at the cell: per component top = a + (b - a) fx, bot = c + (d - c) fx, top + (bot - top) fy.
+__device__ __forceinline__ void displacement(const double* f, const Cell& cell, double* dx, double* dy) {
+    const double2 a = *reinterpret_cast<const double2*>(f + cell.n00), b = *reinterpret_cast<const double2*>(f + cell.n01);
+    const double2 c = *reinterpret_cast<const double2*>(f + cell.n10), d = *reinterpret_cast<const double2*>(f + cell.n11);
+    const double top_x = a.x + (b.x - a.x) * cell.fx, bot_x = c.x + (d.x - c.x) * cell.fx;
+    const double top_y = a.y + (b.y - a.y) * cell.fx, bot_y = c.y + (d.y - c.y) * cell.fx;
+    *dx = top_x + (bot_x - top_x) * cell.fy;
+    *dy = top_y + (bot_y - top_y) * cell.fy;
+}
+
+// The sample of source `s` at the output pixel (rd, cd): false when it is absent (also when rd or cd is not a number: the
+// comparison is the negated one).
 __device__ __forceinline__ bool sample(const SourceRec& s, double cd, double rd, double* v) {
     const double sx = s.tx + s.s * cd, sy = s.ty + s.s * rd;
     if (!(sx >= 0.0 && sx <= (double)(s.w - 1) && sy >= 0.0 && sy <= (double)(s.h - 1))) return false;
@@ -116,9 +151,10 @@ __device__ __forceinline__ double pick(const double (&v)[CAP], int rank) {
     return __longlong_as_double((long long)bits);
 }
 
-// One output pixel -> its 16-bit value and its count.
-template <int CAP, int MODE>
-__device__ __forceinline__ void combine_pixel(const CombineArgs& a, int r, int c, int zero, uint32_t* value, uint32_t* count) {
+// One output pixel -> its 16-bit value and its count.  FIELD: `f` holds the fields and `cell` is the pixel's; else neither is read.
+template <int CAP, int MODE, bool FIELD>
+__device__ __forceinline__ void combine_pixel(const CombineArgs& a, const FieldArgs* f, int r, int c, int zero, const Cell& cell,
+                                              uint32_t* value, uint32_t* count) {
     double v[CAP];
     uint32_t present = 0;
     const double cd = (double)c, rd = (double)r;
@@ -126,8 +162,15 @@ __device__ __forceinline__ void combine_pixel(const CombineArgs& a, int r, int c
     for (int j = 0; j < CAP; ++j) {
         v[j] = INFINITY;
         if (j < a.n) {
-            double t;
-            if (sample(a.src[j + zero], cd, rd, &t)) v[j] = t, present |= 1u << j;
+            double t, cj = cd, rj = rd;
+            if constexpr (FIELD) {
+                if (const double* nodes = f->field[j + zero]) {
+                    double dx, dy;
+                    displacement(nodes, cell, &dx, &dy);
+                    cj = cd + dx, rj = rd + dy;
+                }
+            }
+            if (sample(a.src[j + zero], cj, rj, &t)) v[j] = t, present |= 1u << j;
         }
         // four sources' gathers in flight at a time: without the fence the scheduler hoists the loads of all CAP sources and
         // the registers of their addresses and records with them
@@ -168,12 +211,23 @@ __device__ __forceinline__ void combine_pixel(const CombineArgs& a, int r, int c
     *count = (uint32_t)__popc(kept);
 }
 
-template <int CAP, int MODE>
-__global__ __launch_bounds__(kThreads) void k_stack_combine(const CombineArgs a) {
+// A thread's eight columns.
+template <int CAP, int MODE, bool FIELD>
+__device__ __forceinline__ void combine_octet(const CombineArgs& a, const FieldArgs* f) {
     const int c0 = (blockIdx.x * kLanesX + (int)threadIdx.x % kLanesX) * kOct, r = blockIdx.y * kRows + (int)threadIdx.x / kLanesX;
     if (r >= a.oh || c0 >= a.ow) return;
     const int nc = min(kOct, a.ow - c0);
     uint64_t lo = 0, hi = 0, counts = 0;          // columns 0 .. 3, columns 4 .. 7, a byte a column
+    Cell cell{};
+    int row0 = 0, row1 = 0, i = 0, rem = 0;       // the row's two lattice rows (element offsets), the column's cell and remainder
+    double step_d = 0.0;
+    if constexpr (FIELD) {
+        const int j = r / f->step, j1 = min(j + 1, f->gh - 1);
+        step_d = (double)f->step;
+        cell.fy = (double)(r - j * f->step) / step_d;
+        row0 = j * f->gw * 2, row1 = j1 * f->gw * 2;
+        i = c0 / f->step, rem = c0 - i * f->step;
+    }
 #pragma unroll 1
     for (int j = 0; j < nc; ++j) {
         // A zero the compiler cannot see through, new for every column, in the index of the source records: they are then read
@@ -182,7 +236,13 @@ __global__ __launch_bounds__(kThreads) void k_stack_combine(const CombineArgs a)
         int zero = 0;
         asm volatile("" : "+s"(zero));
         uint32_t value, count;
-        combine_pixel<CAP, MODE>(a, r, c0 + j, zero, &value, &count);
+        if constexpr (FIELD) {
+            const int i1 = min(i + 1, f->gw - 1);
+            cell.n00 = row0 + 2 * i, cell.n01 = row0 + 2 * i1, cell.n10 = row1 + 2 * i, cell.n11 = row1 + 2 * i1;
+            cell.fx = (double)rem / step_d;
+            if (++rem == f->step) rem = 0, ++i;
+        }
+        combine_pixel<CAP, MODE, FIELD>(a, f, r, c0 + j, zero, cell, &value, &count);
         if (j < 4) lo |= (uint64_t)value << (16 * j);
         else hi |= (uint64_t)value << (16 * (j - 4));
         counts |= (uint64_t)count << (8 * j);
@@ -207,12 +267,37 @@ __global__ __launch_bounds__(kThreads) void k_stack_combine(const CombineArgs a)
     }
 }
 
+template <int CAP, int MODE>
+__global__ __launch_bounds__(kThreads) void k_stack_combine(const CombineArgs a) {
+    combine_octet<CAP, MODE, false>(a, nullptr);
+}
+
+template <int CAP, int MODE>
+__global__ __launch_bounds__(kThreads) void k_stack_combine_field(const CombineArgs a, const FieldArgs f) {
+    combine_octet<CAP, MODE, true>(a, &f);
+}
+
+template <int CAP, int MODE>
+int launch_mode(dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs* f) {
+    if (!f) return shg::launch(k_stack_combine<CAP, MODE>, grid, dim3(kThreads), 0, st, a, "k_stack_combine");
+    hipLaunchKernelGGL((k_stack_combine_field<CAP, MODE>), grid, dim3(kThreads), 0, st, a, *f);
+    return shg::check_launch("k_stack_combine_field");
+}
+
 template <int CAP>
-int launch_combine(int mode, dim3 grid, hipStream_t st, const CombineArgs& a) {
-    const char* what = "k_stack_combine";
-    if (mode == SHG_STACK_MEAN) return shg::launch(k_stack_combine<CAP, SHG_STACK_MEAN>, grid, dim3(kThreads), 0, st, a, what);
-    if (mode == SHG_STACK_MEDIAN) return shg::launch(k_stack_combine<CAP, SHG_STACK_MEDIAN>, grid, dim3(kThreads), 0, st, a, what);
-    return shg::launch(k_stack_combine<CAP, SHG_STACK_SIGMA>, grid, dim3(kThreads), 0, st, a, what);
+int launch_capacity(int mode, dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs* f) {
+    if (mode == SHG_STACK_MEAN) return launch_mode<CAP, SHG_STACK_MEAN>(grid, st, a, f);
+    if (mode == SHG_STACK_MEDIAN) return launch_mode<CAP, SHG_STACK_MEDIAN>(grid, st, a, f);
+    return launch_mode<CAP, SHG_STACK_SIGMA>(grid, st, a, f);
+}
+
+// f: the fields, or null for the plain combine
+int launch_combine(int mode, hipStream_t st, const CombineArgs& a, const FieldArgs* f) {
+    const dim3 grid((unsigned)((a.ow + kLanesX * kOct - 1) / (kLanesX * kOct)), (unsigned)((a.oh + kRows - 1) / kRows));
+    if (a.n <= 4) return launch_capacity<4>(mode, grid, st, a, f);
+    if (a.n <= 8) return launch_capacity<8>(mode, grid, st, a, f);
+    if (a.n <= 16) return launch_capacity<16>(mode, grid, st, a, f);
+    return launch_capacity<32>(mode, grid, st, a, f);
 }
 
 using shg::overlap;
@@ -294,12 +379,10 @@ __global__ __launch_bounds__(kThreads) void k_shift_ssd(const SsdArgs a) {
         if (acc[i]) atomicAdd(a.ssd + i, acc[i]);
 }
 
-}  // namespace
-
-extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
-                                     double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
-                                     int64_t count_pitch, shg_stream_t stream) {
-    const char* fn = "shg_stack_combine_u16";
+// The checks and the argument struct the two combine entry points share.  Nothing is written or launched.
+int combine_args(const char* fn, const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
+                 double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count, int64_t count_pitch,
+                 CombineArgs* args) {
     SHG_REQUIRE(host_srcs && host_dims3 && host_xform4 && out, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(n >= 1 && n <= kMaxSources, SHG_E_ARG, "%s: %d sources (1 to %d)", fn, n, kMaxSources);
     SHG_REQUIRE(shg::image_dims_ok(oh, ow), SHG_E_UNSUPPORTED, "%s: an output of %lld x %lld (1 to %d either way)", fn, (long long)oh,
@@ -312,7 +395,7 @@ extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int
     const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
     const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
     SHG_REQUIRE(!count || !overlap(out_span, count_span), SHG_E_ARG, "%s: the count plane overlaps the output", fn);
-    CombineArgs a{};
+    CombineArgs& a = *args;
     for (int j = 0; j < n; ++j) {
         const int64_t h = host_dims3[3 * j], w = host_dims3[3 * j + 1], pitch = host_dims3[3 * j + 2];
         const double s = host_xform4[4 * j], tx = host_xform4[4 * j + 1], ty = host_xform4[4 * j + 2], gain = host_xform4[4 * j + 3];
@@ -332,13 +415,52 @@ extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int
     a.n = n, a.iterations = iterations, a.kappa = kappa;
     a.vec_out = shg::rows_aligned(out, out_pitch, sizeof(uint16_t), 16);
     a.vec_count = count && shg::rows_aligned(count, count_pitch, sizeof(uint8_t), 8);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
+                                     double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
+                                     int64_t count_pitch, shg_stream_t stream) {
+    CombineArgs a{};
+    if (const int e = combine_args("shg_stack_combine_u16", host_srcs, host_dims3, host_xform4, n, mode, kappa, iterations, out, oh, ow,
+                                   out_pitch, count, count_pitch, &a))
+        return e;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("stack_combine", st);
-    const dim3 grid((unsigned)((ow + kLanesX * kOct - 1) / (kLanesX * kOct)), (unsigned)((oh + kRows - 1) / kRows));
-    if (n <= 4) return launch_combine<4>(mode, grid, st, a);
-    if (n <= 8) return launch_combine<8>(mode, grid, st, a);
-    if (n <= 16) return launch_combine<16>(mode, grid, st, a);
-    return launch_combine<32>(mode, grid, st, a);
+    return launch_combine(mode, st, a, nullptr);
+}
+
+extern "C" int shg_stack_combine_field_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
+                                           const double* const* host_fields, int64_t gh, int64_t gw, int step, int n, int mode, double kappa,
+                                           int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
+                                           int64_t count_pitch, shg_stream_t stream) {
+    const char* fn = "shg_stack_combine_field_u16";
+    SHG_REQUIRE(host_fields, SHG_E_ARG, "%s: null pointer", fn);
+    SHG_REQUIRE(step >= kMinStep && step <= kMaxStep, SHG_E_ARG, "%s: a lattice step of %d pixels (%d to %d)", fn, step, kMinStep, kMaxStep);
+    CombineArgs a{};
+    FieldArgs f{};
+    if (const int e = combine_args(fn, host_srcs, host_dims3, host_xform4, n, mode, kappa, iterations, out, oh, ow, out_pitch, count,
+                                   count_pitch, &a))
+        return e;
+    SHG_REQUIRE(gh == (oh - 1 + step - 1) / step + 1 && gw == (ow - 1 + step - 1) / step + 1, SHG_E_ARG,
+                "%s: a lattice of %lld x %lld nodes does not cover %lld x %lld pixels at a step of %d", fn, (long long)gh, (long long)gw,
+                (long long)oh, (long long)ow, step);
+    const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
+    const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
+    for (int j = 0; j < n; ++j) {
+        f.field[j] = host_fields[j];
+        if (!host_fields[j]) continue;
+        SHG_REQUIRE(reinterpret_cast<uintptr_t>(host_fields[j]) % 16 == 0, SHG_E_ARG, "%s: field %d does not start on 16 bytes", fn, j);
+        const Span field_span = span_of(host_fields[j], gh, gw * 2, gw * 2, sizeof(double));
+        SHG_REQUIRE(!overlap(out_span, field_span), SHG_E_ARG, "%s: the output overlaps field %d", fn, j);
+        SHG_REQUIRE(!count || !overlap(count_span, field_span), SHG_E_ARG, "%s: the count plane overlaps field %d", fn, j);
+    }
+    f.gh = (int)gh, f.gw = (int)gw, f.step = step;
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("stack_combine_field", st);
+    return launch_combine(mode, st, a, &f);
 }
 
 extern "C" int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w, int S,

@@ -1092,6 +1092,82 @@ def shift_ssd_u16(ref, img, search, circle=None, out=None):
     return out
 
 
+# ---- local alignment points: one SSD table a patch, and the combine with a displacement field a source ----
+def patch_ssd_u16(ref, img, points, half, search, circle=None, out=None):
+    """shg_patch_ssd_u16: for each of the n points (row, col) -- an int32 [n, 2] tensor on the images' device, or a host array that
+    is uploaded -- the sums of squared differences between the (2 half + 1)^2 patch of `ref` around it and `img`, for every integer
+    offset (u, v) with |u|, |v| <= search (0 to 8), over the patch's pixels at least `search` from every edge and, with `circle`, on
+    that disk -> int64 [n, (2 S + 1)^2 + 3] on the images' device: the sums, then the pixels of the set, the sum of ref and the sum
+    of ref^2 over it (a row of zeros for an empty set).  half is 1 to 32.  out: the caller's, overwritten."""
+    rptr, h, w, rpitch = _img(ref, 'ref', torch.uint16)
+    iptr, ih, iw, ipitch = _img(img, 'img', torch.uint16)
+    if (ih, iw) != (h, w):
+        raise ValueError('ref [%d, %d] and img [%d, %d] must have one shape' % (h, w, ih, iw))
+    b, s = int(half), int(search)
+    if not 1 <= b <= 32:
+        raise ValueError('half must be 1 to 32, got %r' % (half,))
+    if not 0 <= s <= 8:
+        raise ValueError('search must be 0 to 8, got %r' % (search,))
+    if not isinstance(points, torch.Tensor):
+        points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)).to(ref.device)
+    if _dev(points, 'points').dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 2 or not points.is_contiguous():
+        raise ValueError('points must be a contiguous int32 [n, 2] tensor of (row, col)')
+    n = int(points.shape[0])
+    if n < 1:
+        raise ValueError('at least one point is needed')
+    c3 = _circle3_or_none(circle)
+    words = (2 * s + 1) ** 2 + 3
+    if out is None:
+        out = torch.empty((n, words), dtype=torch.int64, device=ref.device)
+    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (n, words) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int64 [%d, %d] tensor' % (n, words))
+    _lib.check(lib.shg_patch_ssd_u16(rptr, rpitch, iptr, ipitch, h, w, points.data_ptr(), n, b, s, _host_ptr(c3), out.data_ptr(), _stream()),
+               'shg_patch_ssd_u16')
+    return out
+
+
+def lattice_shape(shape, step):
+    """(gh, gw) of the lattice of `step` pixels that covers a grid of `shape`: (oh - 1 + step - 1) // step + 1, columns alike."""
+    oh, ow, step = int(shape[0]), int(shape[1]), int(step)
+    return (oh - 1 + step - 1) // step + 1, (ow - 1 + step - 1) // step + 1
+
+
+def stack_combine_field_u16(images, transforms, fields, step, shape, mode='sigma', kappa=2.5, iterations=2, out=None, count=None,
+                            want_count=True):
+    """shg_stack_combine_field_u16: stack_combine_u16 with a displacement field a source.  fields: one entry an image, None (no
+    field) or a contiguous float64 [gh, gw, 2] tensor on the images' device, (dx, dy) at the nodes (j step, i step) of the lattice
+    lattice_shape(shape, step); step is 8 to 128.  The output pixel (r, c) reads source j at (tx + s (c + dx), ty + s (r + dy)) with
+    (dx, dy) bilinear between the four nodes around it; a displacement that is not finite makes the sample absent; None and a field
+    of zeros give stack_combine_u16's result bit for bit -> (out uint16 [oh, ow], count uint8 [oh, ow] or None)."""
+    if mode not in STACK_MODES:
+        raise ValueError('mode is one of %s, got %r' % (', '.join(STACK_MODES), mode))
+    images, fields = list(images), list(fields)
+    n = len(images)
+    xf = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4))
+    if n < 1 or xf.shape[0] != n or len(fields) != n:
+        raise ValueError('%d images, %d transforms (s, tx, ty, gain) and %d fields' % (n, xf.shape[0], len(fields)))
+    if not 8 <= int(step) <= 128:
+        raise ValueError('step must be 8 to 128, got %r' % (step,))
+    geo = [_img(t, 'image', torch.uint16) for t in images]
+    dev = images[0].device
+    oh, ow = int(shape[0]), int(shape[1])
+    gh, gw = lattice_shape((oh, ow), step)
+    for f in fields:
+        if f is not None and (_dev(f, 'field').dtype != torch.float64 or tuple(f.shape) != (gh, gw, 2) or not f.is_contiguous()):
+            raise ValueError('a field is None or a contiguous float64 [%d, %d, 2] tensor' % (gh, gw))
+    out, optr, opitch = _out_like(out, oh, ow, torch.uint16, dev)
+    cptr, cpitch = None, 0
+    if count is not None or want_count:
+        count, cptr, cpitch = _out_like(count, oh, ow, torch.uint8, dev, 'count')
+    ptrs = (ctypes.c_void_p * n)(*[g[0] for g in geo])
+    fptrs = (ctypes.c_void_p * n)(*[None if f is None else f.data_ptr() for f in fields])
+    dims = np.ascontiguousarray([[g[1], g[2], g[3]] for g in geo], dtype=np.int64)
+    _lib.check(lib.shg_stack_combine_field_u16(ptrs, _host_ptr(dims), _host_ptr(xf), fptrs, gh, gw, int(step), n, STACK_MODES[mode],
+                                               float(kappa), int(iterations), optr, oh, ow, opitch, cptr, cpitch, _stream()),
+               'shg_stack_combine_field_u16')
+    return out, count
+
+
 # ---- sharpening a disk: the a-trous wavelet layers with gains and gates, and the noise they are gated by ----
 def wavelet_sharpen_u16(img, gain_q8, threshold_q6=None, out=None, want_planes=False, workspace=None):
     """shg_wavelet_sharpen_u16: the uint16 image split into L = len(gain_q8) B3-spline a-trous layers (1 to 6) and put together again,
