@@ -473,6 +473,44 @@ int shg_wavelet_sharpen_u16(const uint16_t* img, int64_t h, int64_t w, int64_t p
 int shg_wavelet_noise_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, uint64_t* out2,
                           void* workspace, size_t workspace_bytes, shg_stream_t stream);
 
+/* ---- deconvolving a disk: Richardson-Lucy with a separable point-spread function (not a reference stage; tests/deconvolve_ref.py
+ * restates all of it in NumPy, bit for bit).  Every value is a float32 and every product and every sum is rounded on its own (no
+ * fused multiply-add, no fast-math); the division is IEEE's, correctly rounded.
+ * Inputs: img uint16 [h][w] with a pitch; a radius R, 0 <= R <= 16; 2 R + 1 host float32 taps k[-R .. R] (host_taps[R + i] = k[i]),
+ *   each 0 or in [2^-30, 1], their float64 sum within 2^-10 of 1; 1 <= iterations = N <= 200.
+ * The blur B(a, k) of a plane a, separable, with the reflection R(i, n) of the sharpening section above (an image narrower than R
+ * reflects more than once):
+ *   t[r][c] = sum over i = -R .. R, in increasing i, of k[i] * a[r][R(c + i, w)]       (the row pass: the sum starts from 0, and a tap
+ *                                                                                      is one rounded multiply and one rounded add);
+ *   B[r][c] = sum over i = -R .. R, in increasing i, of k[i] * t[R(r + i, h)][c]       (the column pass, accumulated the same way);
+ *   t is a float32 between the passes.
+ * The iteration: d = (float)img, e_0 = d; for n = 1 .. N:
+ *   1. b = B(e_(n-1), k);
+ *   2. q = d / max(b, 2^-10);
+ *   3. c = B(q, k~) with k~[i] = k[-i]                     (the adjoint: the taps reversed);
+ *   4. p = e_(n-1) * c;
+ *   5. e_n = 0 if p < 2^-20, else min(p, 2^20)             (the flush and the clamp).
+ * out[r * out_pitch + c] = (uint16)clip(rint(e_N), 0, 65535), ties to even; estimate, if given, receives e_N unrounded, dense [h][w].
+ * Four properties follow, and the tests use them:
+ *   (a) everything is finite and >= 0: b < 2^21, q <= 65535 * 2^10 < 2^26, c < 2^27 and p <= 2^20 c < 2^47;
+ *   (b) no operation has a subnormal result: a non-zero tap is >= 2^-30, a non-zero e >= 2^-20, a non-zero q > 1 / b > 2^-21, so the
+ *       smallest non-zero product of a tap and a value is above 2^-51, of a tap and a t above 2^-81, and of e and c above 2^-102: the
+ *       result does not depend on the denormal mode;
+ *   (c) taps padded with zeros on both sides to a larger R give the same bits: 0 * a = +0 for a finite a >= 0, and adding +0 to a
+ *       non-negative sum changes nothing;
+ *   (d) every pixel's value is a fixed expression of its inputs: neither the launch grid, nor the tile, nor any fusion of steps
+ *       can change a bit.
+ * workspace: shg_rl_workspace_bytes(h, w) -- the float planes e and q the launches hand each other, 8 bytes a pixel, plus the
+ *   round-up of its start to 256 bytes --, which is 0 for dimensions out of range and needs no GPU.
+ * 1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG for a null pointer (estimate excepted), a pitch below the width, a radius
+ * or an iteration count out of range, a tap that is not finite or out of range, a sum of taps off 1, a workspace that is too small,
+ * and an out, estimate or workspace that overlaps img or one another.  On any error nothing is written.  The call allocates nothing,
+ * waits for nothing and copies nothing from the device.  Elements between w and a pitch are never touched. */
+size_t shg_rl_workspace_bytes(int64_t h, int64_t w);
+int shg_rl_deconvolve_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const float* host_taps, int radius, int iterations,
+                          uint16_t* out, int64_t out_pitch, float* estimate, void* workspace, size_t workspace_bytes,
+                          shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -112,6 +112,8 @@ SIGNATURES = {
     'shg_wavelet_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int]),
     'shg_wavelet_sharpen_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, P, P, P, c_int64, P, P, c_size_t, P]),
     'shg_wavelet_noise_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, c_size_t, P]),
+    'shg_rl_workspace_bytes': (c_size_t, [c_int64, c_int64]),
+    'shg_rl_deconvolve_u16': (c_int, [P, c_int64, c_int64, c_int64, P, c_int, c_int, P, c_int64, P, P, c_size_t, P]),
     'shg_blur_fits_fused': (c_int, [c_int64, c_int]),
     'shg_blur_row_mean_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, P, P]),
     'shg_blur_argmin_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int64, c_int64, P, P, P]),

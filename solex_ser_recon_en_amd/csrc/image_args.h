@@ -1,5 +1,5 @@
-// What the host code of the disk products' entry points (rings.hip, stack.hip, wavelet.hip) and of the map detrend (detrend.hip)
-// share: the checks of an image argument, byte spans and their overlap, row alignment, the workspace's round-up, the optional disk
+// What the host code of the disk products' entry points (rings.hip, stack.hip, wavelet.hip, deconvolve.hip) and of the map detrend
+// (detrend.hip) share: the checks of an image argument, byte spans and their overlap, row alignment, the workspace's round-up, the optional disk
 // mask and the cleared table.  Host only: no kernel and no kernel argument struct is declared here.
 #pragma once
 

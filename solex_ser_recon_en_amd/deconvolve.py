@@ -1,0 +1,132 @@
+"""Deconvolve a disk: Richardson-Lucy iterations of a 16-bit image with a separable point-spread function --
+the step between a stack and its wavelets, which inverts the instrument-and-seeing blur where the wavelet gains only weigh scales.
+The iterations are HIP kernels in float32 whose arithmetic include/shg_hip.h states exactly (ops.rl_deconvolve_u16); the Gaussian
+taps are host float64, written step by step so that the tests restate them.
+
+    python -m solex_ser_recon_en_amd.deconvolve INPUT [--psf-sigma X] [--iterations N] [--radius R] [--shift S] [--contrast]
+        [SHG_MAIN flags]
+
+Richardson-Lucy amplifies noise: it suits a stack, and a single scan only for a few iterations.  Out of scope: point-spread
+functions that are not separable, measuring the blur from the limb, limb protection or damping against ringing, regularised or
+blind variants, stopping rules, and any change to the stack, flatten or sharpen command lines.
+"""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+
+from . import disk
+
+MAX_RADIUS = 16
+MAX_ITERATIONS = 200
+MIN_SIGMA, MAX_SIGMA = 0.3, 4.0
+MIN_TAP = 2.0 ** -30
+DEFAULT_SIGMA = 1.2
+DEFAULT_ITERATIONS = 10
+
+
+def gaussian_taps(sigma, radius=None):
+    """The 2 R + 1 taps of a Gaussian of `sigma` pixels (0.3 to 4): exp(-i^2 / (2 sigma^2)) over i = -R .. R in float64, normalised to
+    sum 1, cast to float32; a tap that comes out below 2^-30, the smallest non-zero tap the kernel takes, is 0 (on a full-scale pixel
+    it is worth 2^-14 of a count).  radius None: ceil(4 sigma); else an integer from 0 to 16.  ValueError outside the ranges."""
+    if not (isinstance(sigma, (int, float, np.integer, np.floating)) and math.isfinite(sigma) and MIN_SIGMA <= sigma <= MAX_SIGMA):
+        raise ValueError('sigma lies in [%g, %g], got %r' % (MIN_SIGMA, MAX_SIGMA, sigma))
+    if radius is None:
+        radius = int(math.ceil(4.0 * float(sigma)))
+    if not (isinstance(radius, (int, np.integer)) and 0 <= radius <= MAX_RADIUS):
+        raise ValueError('radius is an integer from 0 to %d, got %r' % (MAX_RADIUS, radius))
+    i = np.arange(-int(radius), int(radius) + 1, dtype=np.float64)
+    k = np.exp(-(i * i) / (2.0 * float(sigma) * float(sigma)))
+    k = (k / k.sum()).astype(np.float32)
+    k[k < np.float32(MIN_TAP)] = 0.0
+    return k
+
+
+def _check_iterations(iterations):
+    if not (isinstance(iterations, (int, np.integer)) and 1 <= iterations <= MAX_ITERATIONS):
+        raise ValueError('iterations is an integer from 1 to %d, got %r' % (MAX_ITERATIONS, iterations))
+    return int(iterations)
+
+
+def deconvolve_disk(image, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None):
+    """The uint16 device image after `iterations` Richardson-Lucy iterations with the separable blur of `taps` (2 R + 1 float32
+    values, as ops.rl_deconvolve_u16 takes them), or, without taps, of gaussian_taps(sigma, radius) (sigma None: 1.2) -> (the
+    deconvolved uint16 device image, the record {'sigma' (None with given taps), 'radius', 'taps', 'iterations'})."""
+    from . import ops
+    from .device import to_device_u16
+    iterations = _check_iterations(iterations)
+    if taps is None:
+        sigma = DEFAULT_SIGMA if sigma is None else float(sigma)
+        k = gaussian_taps(sigma, radius)
+    else:
+        if sigma is not None or radius is not None:
+            raise ValueError('taps come without sigma and radius')
+        k = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    out, _ = ops.rl_deconvolve_u16(to_device_u16(image), k, iterations)
+    return out, {'sigma': sigma, 'radius': int(k.size // 2), 'taps': [float(v) for v in k], 'iterations': iterations}
+
+
+def deconvolve_scan(file_or_reader, options=None, shift=0, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None):
+    """A scan's disk at `shift` (disk.scan_disk, with its refusals: ratio_fixe / slant_fix, de-vignette, a frame shard),
+    deconvolved by deconvolve_disk -> {'image', 'deconv' (uint16 device tensors), 'circle', 'record', 'shift', 'ratio', 'phi',
+    'crop'}."""
+    scan = disk.scan_disk(file_or_reader, options, shift, 'deconvolution')
+    deconv, record = deconvolve_disk(scan['image'], sigma, iterations, taps, radius)
+    return {'image': scan['image'], 'deconv': deconv, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
+            'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
+
+
+# ---- command line ---------------------------------------------------------------------------------
+def main(argv=None):
+    from .linemaps import _print_json
+    from .video_reader import video_reader
+    p = argparse.ArgumentParser(
+        prog='python -m solex_ser_recon_en_amd.deconvolve',
+        usage='%(prog)s INPUT [--psf-sigma X] [--iterations N] [--radius R] [--shift S] [--contrast] [SHG_MAIN flags]',
+        description='Deconvolve a disk: Richardson-Lucy iterations with a Gaussian point-spread function.  INPUT is a SER or AVI scan, or '
+                    'a 16-bit grey PNG this package wrote (_stack.png, _flat.png, _uncontrasted.png).  The iterations amplify noise: '
+                    'give a stack many, a single scan few.  No limb protection: the limb rings.')
+    p.add_argument('--psf-sigma', type=float, default=DEFAULT_SIGMA,
+                   help='the blur\'s Gaussian sigma in pixels, %g to %g (default %g)' % (MIN_SIGMA, MAX_SIGMA, DEFAULT_SIGMA))
+    p.add_argument('--iterations', type=int, default=DEFAULT_ITERATIONS, help='1 to %d (default %d)' % (MAX_ITERATIONS, DEFAULT_ITERATIONS))
+    p.add_argument('--radius', type=int, default=None, help='the taps reach this far, 0 to %d (default: ceil(4 sigma))' % MAX_RADIUS)
+    p.add_argument('--shift', type=int, default=0, help='pixel shift of a scan\'s disk (the -w shift; default 0: the line centre)')
+    p.add_argument('--contrast', action='store_true', help='also the contrast products of the deconvolved image (<base>_deconv_clahe.png, ...)')
+
+    def checks(args):
+        try:
+            gaussian_taps(args.psf_sigma, args.radius)
+            _check_iterations(args.iterations)
+        except ValueError as e:
+            p.error(str(e))
+
+    args, opts, (path,) = disk.parse(p, argv, 'deconvolve', 'deconvolution', checks, need='exactly one SER, AVI or PNG file is needed', png=True)
+    is_png = path.lower().endswith('.png')
+    try:
+        if is_png:
+            img, header_source, stem = disk.png_input(path, opts)
+            deconv, record = deconvolve_disk(img, args.psf_sigma, args.iterations, radius=args.radius)
+            res = {'circle': (-1, -1, -1), 'ratio': None, 'phi': None, 'crop': None}
+            total = float(img.astype(np.float64).sum())
+        else:
+            header_source = video_reader(path)
+            res = deconvolve_scan(header_source, opts, args.shift, args.psf_sigma, args.iterations, radius=args.radius)
+            deconv, record = res['deconv'], res['record']
+            stem = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift'])
+            total = float(disk.host_u(res['image'].contiguous(), np.uint16).astype(np.float64).sum())
+    except ValueError as e:
+        print('error: %s' % e, file=sys.stderr)
+        return 1
+    host, png, fits = disk.write_image(deconv, stem + '_deconv', opts, header_source)
+    out = {'input': path, 'shape': list(host.shape), 'psf_sigma': record['sigma'], 'radius': record['radius'], 'taps': record['taps'],
+           'iterations': record['iterations'], 'flux': float(host.astype(np.float64).sum()) / total if total else None,
+           'shift': None if is_png else res['shift'], 'png': png, 'fits': fits, 'contrast': None}
+    if args.contrast:
+        out['contrast'] = disk.contrast_products(deconv, tuple(res['circle']), opts, header_source, stem + '_deconv')
+    return _print_json(out, res)
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -1,4 +1,4 @@
-"""What the disk products -- flatten, stack, sharpen (DESIGN.md sections 16 to 18) -- share: a scan's 16-bit disk and its circle
+"""What the disk products -- flatten, stack, sharpen, deconvolve (DESIGN.md sections 16 to 20) -- share: a scan's 16-bit disk and its circle
 through the pipeline's own stages, and the frame of their command lines: the parse with its refusals, the image written as the
 products are, the contrast products."""
 import contextlib
@@ -60,7 +60,7 @@ def scan_disk(file_or_reader, options=None, shift=0, purpose='flattening'):
             'phi': float(phi), 'crop': crop}
 
 
-# ---- the frame of the three command lines ------------------------------------------------------------
+# ---- the frame of the four command lines ------------------------------------------------------------
 def parse(p, argv, noun, purpose, checks=None, file_checks=None, png=False, **count):
     """The command line of the product `noun` ('flatten'; `purpose`: 'flattening'): parse, the refusal under torchrun, the caller's
     checks(args), the refusal of -w, then CLI_handler.options_and_files -- `count`: its need, least, most -- with file_checks(args,
@@ -78,6 +78,23 @@ def parse(p, argv, noun, purpose, checks=None, file_checks=None, png=False, **co
     opts, files = CLI_handler.options_and_files(p, [a for a in rest if a not in pngs], extra=pngs,
                                                 checks=file_checks and (lambda files: file_checks(args, files)), **count)
     return args, opts, files
+
+
+class _PngHeaderSource:
+    """What fits_io.make_header reads of a reader, for an image that came from a PNG."""
+    def __init__(self, h, w):
+        self.ih, self.iw = h, w
+
+
+def png_input(path, opts):
+    """A 16-bit grey PNG this package wrote as a product's input -> (the uint16 host image, the header source of what is written
+    from it, the stem of its outputs); opts['img_rotate'] becomes 0 (a product is already rotated).  ValueError for any other PNG."""
+    from .png_io import read_png_gray
+    img = read_png_gray(path)
+    if img.dtype != np.uint16 or img.ndim != 2:
+        raise ValueError('%s is not a 16-bit grey PNG' % path)
+    opts['img_rotate'] = 0
+    return img, _PngHeaderSource(*img.shape), os.path.splitext(path)[0]
 
 
 def write_image(image, stem, opts, header_source):

@@ -1206,3 +1206,28 @@ def wavelet_noise_u16(img, circle=None, out=None, workspace=None):
     _lib.check(lib.shg_wavelet_noise_u16(ptr, h, w, pitch, _host_ptr(c3), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
                'shg_wavelet_noise_u16')
     return out
+
+
+# ---- deconvolving a disk: Richardson-Lucy with a separable point-spread function ----
+def rl_deconvolve_u16(img, taps, iterations, out=None, want_estimate=False, workspace=None):
+    """shg_rl_deconvolve_u16: `iterations` (1 to 200) Richardson-Lucy iterations of the uint16 image with the separable blur of the
+    2 R + 1 float32 `taps` (R = 0 to 16; each 0 or in [2^-30, 1]; their sum within 2^-10 of 1) -> (out uint16 [h, w], the estimate
+    float32 [h, w] before its rounding, or None).  out: the caller's view, which must not overlap the image.  workspace: the caller's
+    uint8 tensor of at least shg_rl_workspace_bytes(h, w)."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    k = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    if k.size % 2 != 1 or k.size > 33:
+        raise ValueError('2 R + 1 taps with R from 0 to 16, got %d' % k.size)
+    if not (np.isfinite(k).all() and ((k == 0) | ((k >= np.float32(2.0 ** -30)) & (k <= 1))).all()):
+        raise ValueError('a tap is 0 or lies in [2^-30, 1]')
+    if abs(float(k.astype(np.float64).sum()) - 1.0) > 2.0 ** -10:
+        raise ValueError('the taps sum to %r, more than 2^-10 off 1' % float(k.astype(np.float64).sum()))
+    if not (isinstance(iterations, (int, np.integer)) and 1 <= iterations <= 200):
+        raise ValueError('iterations is an integer from 1 to 200, got %r' % (iterations,))
+    out, optr, opitch = _out_like(out, h, w, torch.uint16, img.device)
+    estimate = torch.empty((h, w), dtype=torch.float32, device=img.device) if want_estimate else None
+    ws, ws_bytes = _workspace(workspace, lib.shg_rl_workspace_bytes(h, w), img.device)
+    _lib.check(lib.shg_rl_deconvolve_u16(ptr, h, w, pitch, _host_ptr(k), k.size // 2, int(iterations), optr, opitch,
+                                         None if estimate is None else estimate.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+               'shg_rl_deconvolve_u16')
+    return out, estimate

@@ -6,8 +6,9 @@ gate factors into their integer arguments is host float64, written step by step 
     python -m solex_ser_recon_en_amd.sharpen INPUT [--levels L] [--gains g1,..] [--denoise k1,..] [--sigma X] [--circle cx,cy,rad]
         [--region F] [--shift S] [--contrast] [SHG_MAIN flags]
 
-Out of scope: limb protection (the limb's edge overshoots into the sky), deconvolution, and any change to the stack or flatten
-command lines.
+Out of scope: limb protection (the limb's edge overshoots into the sky) and any change to the stack or flatten command lines.
+Deconvolution by the instrument-and-seeing blur is a step of its own, before this one (deconvolve.py): its
+_deconv.png is an input here.
 """
 import argparse
 import math
@@ -155,15 +156,8 @@ def _floats(text):
         raise argparse.ArgumentTypeError('a comma-separated list of numbers, got %r' % text)
 
 
-class _PngHeaderSource:
-    """What fits_io.make_header reads of a reader, for an image that came from a PNG."""
-    def __init__(self, h, w):
-        self.ih, self.iw = h, w
-
-
 def main(argv=None):
     from .linemaps import _print_json
-    from .png_io import read_png_gray
     from .video_reader import video_reader
     p = argparse.ArgumentParser(
         prog='python -m solex_ser_recon_en_amd.sharpen',
@@ -210,14 +204,9 @@ def main(argv=None):
     is_png = path.lower().endswith('.png')
     try:
         if is_png:
-            img = read_png_gray(path)
-            if img.dtype != np.uint16 or img.ndim != 2:
-                raise ValueError('%s is not a 16-bit grey PNG' % path)
+            img, header_source, stem = disk.png_input(path, opts)
             circle = None if args.circle is None else tuple(args.circle)
             sharp, record = sharpen_disk(img, args.gains, args.denoise, args.sigma, circle, args.region)
-            header_source = _PngHeaderSource(*img.shape)
-            stem = os.path.splitext(path)[0]
-            opts['img_rotate'] = 0                              # (a product is already rotated)
             res = {'circle': circle if circle is not None else (-1, -1, -1), 'ratio': None, 'phi': None, 'crop': None}
         else:
             if args.circle is not None:
