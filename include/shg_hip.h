@@ -433,6 +433,56 @@ int shg_stack_combine_field_u16(const uint16_t* const* host_srcs, const int64_t*
                                 int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
                                 int64_t count_pitch, shg_stream_t stream);
 
+/* ---- ranking scans by sharpness: the sums a quality figure is made of, one row a patch, and the combine that weights each source by
+ * a lattice of such figures (not reference stages; tests/quality_ref.py restates both calls in NumPy, bit for bit).
+ * shg_patch_sharpness_u16: img is a uint16 image of h x w (pitch in elements); points (device) = [n][2] int32 (row pr, column pc), the
+ * centres, which may lie anywhere, also outside the image, as for shg_patch_ssd_u16.  B is the patch's half-size, D the arm of the
+ * Laplacian.  The pixel set of point p: every (r, c) with |r - pr| <= B, |c - pc| <= B, D <= r < h - D and D <= c < w - D that, given a
+ * circle3 (host; NULL or (-1, -1, -1): no circle), is ON THE DISK by the test of the flatten section above, the test of
+ * shg_patch_ssd_u16 in the same float64 steps.  For a pixel of the set, as int64 (the arms may read pixels that are not in the set):
+ *   L = 4 * img[r][c] - img[r - D][c] - img[r + D][c] - img[r][c - D] - img[r][c + D].
+ * out (device) = [n][4] uint64:
+ *   out[p][0] = the number of pixels in the set;  out[p][1] = the sum of img[r][c] over the set;
+ *   out[p][2] = the sum of img[r][c]^2 over the set;  out[p][3] = the sum of L^2 over the set.
+ * |L| <= 4 * 65535 < 2^18, L^2 < 2^36, and a set holds at most 65^2 = 4225 pixels: every sum stays below 2^49 < 2^64.  All sums are
+ * integers and every word of out is written by one plain store: the result depends neither on the launch grid nor on any order, and
+ * the call needs no clearing pass.  An empty set (an image narrower or lower than 2 D + 1, a centre far outside, a circle off the
+ * patch) gives a row of zeros; two equal points give two equal rows.  1 <= n <= 2^23, 1 <= B <= 32, 1 <= D <= 8, else SHG_E_ARG.
+ * 1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG for a null pointer, a pitch < w, a circle that is not finite, and an out that
+ * overlaps img or points.  On any error nothing is written. */
+int shg_patch_sharpness_u16(const uint16_t* img, int64_t pitch, int64_t h, int64_t w, const int32_t* points, int64_t n, int B, int D,
+                            const double* circle3, uint64_t* out, shg_stream_t stream);
+
+/* shg_stack_combine_weighted_u16: shg_stack_combine_field_u16 with a weight lattice a source.  Every argument of that call is that
+ * call's, except that host_fields may be NULL as a whole (no source has a field).  host_weights (host): n device pointers, each NULL
+ * (weight 1 everywhere) or a float64 array [gh][gw] that starts on 8 bytes: one weight a node of the lattice the fields use (gh, gw
+ * and step follow that call's rules also when there is no field).  Everything is float64, one IEEE operation a step, no contraction.
+ * With the cell (j, j1, i, i1, fx, fy) of shg_stack_combine_field_u16 for the output pixel, and for source s with a lattice W,
+ * a = W[j][i], b = W[j][i1], c' = W[j1][i], d = W[j1][i1]:
+ *   top = a + (b - a) * fx;  bot = c' + (d - c') * fx;  w_s = top + (bot - top) * fy;
+ * without a lattice w_s = 1.0.  Source s is PRESENT at the pixel iff it is present by shg_stack_combine_field_u16's rule and
+ * w_s > 0.0 is true (a weight that is not a number removes the sample).  With v the present samples in source order:
+ *   SHG_STACK_MEAN: the kept set K is every present sample.
+ *   SHG_STACK_SIGMA: K comes from exactly shg_stack_combine_u16's clipping passes over the present samples, which do not see the
+ *     weights (unweighted means and deviations); its rule for n' < 3 and its rule for an empty K' hold.
+ *   SHG_STACK_MEDIAN: SHG_E_ARG (there is no weighted median).
+ *   num = the sum over K, in source order from 0.0, of w_s * v_s (every product rounded, then every sum);  den = the sum over K, in
+ *   source order from 0.0, of w_s;  m = num / den;  out = (uint16)clip(rint(m), 0, 65535), ties to even;  count = |K|.
+ *   Nothing present: out = 0, count = 0.
+ * Three exact properties follow.  (a) With every lattice NULL, or every node 1.0, the result is shg_stack_combine_field_u16's bit for
+ * bit: 1.0 * v is v, and the sum of |K| ones is the exact integer |K|.  (b) A lattice of zeros for source s gives the result of the
+ * call without source s, the order of the others kept, bit for bit.  (c) Multiplying every node of every lattice by one power of two
+ * changes no bit, as long as the nodes stay in range: every step scales exactly.
+ * The nodes are the caller's to keep finite, >= 0 and <= 2^20: the call copies nothing from the device and cannot check them.  A node
+ * outside that range makes the pixels of its cells unspecified; nothing outside out and count is ever written whatever the nodes
+ * hold.  SHG_E_ARG for a null host_weights, a lattice that does not start on 8 bytes, and an output or count plane that overlaps a
+ * weight lattice; every limit and code of shg_stack_combine_field_u16 holds (a null host_fields excepted).  On any error nothing is
+ * written.  The call allocates nothing, waits for nothing and copies nothing from the device. */
+int shg_stack_combine_weighted_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
+                                   const double* const* host_fields, const double* const* host_weights, int64_t gh, int64_t gw, int step,
+                                   int n, int mode, double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch,
+                                   uint8_t* count, int64_t count_pitch, shg_stream_t stream);
+
 /* ---- sharpening a disk: the undecimated B3-spline ("a trous") wavelet layers of a 16-bit image, one gain a layer and a soft
  * noise gate a layer (not a reference stage; tests/sharpen_ref.py restates all of it in NumPy, bit for bit).  Everything is an
  * integer: the result depends neither on the launch grid, nor on how levels are fused, nor on the order of anything.

@@ -109,6 +109,9 @@ SIGNATURES = {
     'shg_patch_ssd_u16': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, c_int64, c_int, c_int, P, P, P]),
     'shg_stack_combine_field_u16': (c_int, [P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, c_double, c_int, P, c_int64, c_int64, c_int64,
                                             P, c_int64, P]),
+    'shg_patch_sharpness_u16': (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, c_int, c_int, P, P, P]),
+    'shg_stack_combine_weighted_u16': (c_int, [P, P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, c_double, c_int, P, c_int64, c_int64,
+                                               c_int64, P, c_int64, P]),
     'shg_wavelet_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int]),
     'shg_wavelet_sharpen_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, P, P, P, c_int64, P, P, c_size_t, P]),
     'shg_wavelet_noise_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, c_size_t, P]),

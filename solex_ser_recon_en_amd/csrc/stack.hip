@@ -21,6 +21,13 @@
 // interpolations before its sample; a null field costs a scalar test.  Without fields none of this is compiled:
 // k_stack_combine<CAP, MODE> is the kernel it was.
 //
+// Combine with a weight lattice a source as well (shg_stack_combine_weighted_u16): the same code again, a second template switch
+// beside the first, under a third kernel that takes the lattices as a third argument.  A source's weight is interpolated between
+// the four nodes of the pixel's cell (8-byte loads: the nodes are cache-resident) before its sample, and a weight that is not > 0
+// skips the sample; the CAP weights sit in a second private array beside the samples, indexed by compile-time constants only, so
+// they too live in registers (past 256 the compiler takes accumulation registers: still no scratch).  The clipping passes do not
+// see the weights; the last step is a weighted in-order mean of the kept samples.  Without the switch none of this is compiled.
+//
 // SSD: a workgroup walks 64 x 16 tiles; it holds the tile of img with a border of S pixels in LDS and its own four pixels of ref
 // in registers, and for each of the (2 S + 1)^2 offsets sums the squared differences of its pixels (a term is below 2^32, the sum
 // 64-bit), folds the wave with DPP and adds the wave's total to a table in LDS; at its end it adds the table's non-zero entries
@@ -68,6 +75,11 @@ struct FieldArgs {
     int gh, gw, step;
 };
 static_assert(sizeof(CombineArgs) + sizeof(FieldArgs) <= 4096, "kernel arguments");
+// One weight a node a source on the same lattice, null for 1 everywhere: a third kernel argument, for the same reason.
+struct WeightArgs {
+    const double* weight[kMaxSources];
+};
+static_assert(sizeof(CombineArgs) + sizeof(FieldArgs) + sizeof(WeightArgs) <= 4096, "kernel arguments");
 constexpr int kMinStep = 8, kMaxStep = 128;
 static_assert(kMinStep >= 8, "a thread's eight columns cross one lattice line at most");
 
@@ -85,6 +97,14 @@ __device__ __forceinline__ void displacement(const double* f, const Cell& cell, 
     const double top_y = a.y + (b.y - a.y) * cell.fx, bot_y = c.y + (d.y - c.y) * cell.fx;
     *dx = top_x + (bot_x - top_x) * cell.fy;
     *dy = top_y + (bot_y - top_y) * cell.fy;
+}
+
+// The weight of lattice `w` at the cell (whose offsets count the fields' two doubles a node): top = a + (b - a) fx,
+// bot = c + (d - c) fx, top + (bot - top) fy.
+__device__ __forceinline__ double node_weight(const double* w, const Cell& cell) {
+    const double a = w[cell.n00 >> 1], b = w[cell.n01 >> 1], c = w[cell.n10 >> 1], d = w[cell.n11 >> 1];
+    const double top = a + (b - a) * cell.fx, bot = c + (d - c) * cell.fx;
+    return top + (bot - top) * cell.fy;
 }
 
 // The sample of source `s` at the output pixel (rd, cd): false when it is absent (also when rd or cd is not a number: the
@@ -152,17 +172,28 @@ __device__ __forceinline__ double pick(const double (&v)[CAP], int rank) {
 }
 
 // One output pixel -> its 16-bit value and its count.  FIELD: `f` holds the fields and `cell` is the pixel's; else neither is read.
-template <int CAP, int MODE, bool FIELD>
-__device__ __forceinline__ void combine_pixel(const CombineArgs& a, const FieldArgs* f, int r, int c, int zero, const Cell& cell,
-                                              uint32_t* value, uint32_t* count) {
+// WEIGHT (with FIELD only: the cell is the lattice's): `w` holds the weight lattices.
+template <int CAP, int MODE, bool FIELD, bool WEIGHT>
+__device__ __forceinline__ void combine_pixel(const CombineArgs& a, const FieldArgs* f, const WeightArgs* w, int r, int c, int zero,
+                                              const Cell& cell, uint32_t* value, uint32_t* count) {
+    static_assert(!WEIGHT || (FIELD && MODE != SHG_STACK_MEDIAN), "weights come on the fields' lattice, and not to a median");
     double v[CAP];
+    double wt[WEIGHT ? CAP : 1];
     uint32_t present = 0;
     const double cd = (double)c, rd = (double)r;
 #pragma unroll
     for (int j = 0; j < CAP; ++j) {
         v[j] = INFINITY;
+        if constexpr (WEIGHT) wt[j] = 0.0;
         if (j < a.n) {
             double t, cj = cd, rj = rd;
+            bool wanted = true;
+            if constexpr (WEIGHT) {
+                double wj = 1.0;
+                if (const double* nodes = w->weight[j + zero]) wj = node_weight(nodes, cell);
+                wanted = wj > 0.0;                                   // (false for a weight that is not a number)
+                if (wanted) wt[j] = wj;
+            }
             if constexpr (FIELD) {
                 if (const double* nodes = f->field[j + zero]) {
                     double dx, dy;
@@ -170,7 +201,7 @@ __device__ __forceinline__ void combine_pixel(const CombineArgs& a, const FieldA
                     cj = cd + dx, rj = rd + dy;
                 }
             }
-            if (sample(a.src[j + zero], cj, rj, &t)) v[j] = t, present |= 1u << j;
+            if (wanted && sample(a.src[j + zero], cj, rj, &t)) v[j] = t, present |= 1u << j;
         }
         // four sources' gathers in flight at a time: without the fence the scheduler hoists the loads of all CAP sources and
         // the registers of their addresses and records with them
@@ -205,15 +236,26 @@ __device__ __forceinline__ void combine_pixel(const CombineArgs& a, const FieldA
                 if (__popc(kept) < 3) break;
             }
         }
-        m = sum_of<CAP>(v, kept) / (double)__popc(kept);
+        if constexpr (WEIGHT) {
+            double num = 0.0, den = 0.0;
+#pragma unroll
+            for (int j = 0; j < CAP; ++j)
+                if (kept >> j & 1u) {
+                    const double t = wt[j] * v[j];
+                    num = num + t, den = den + wt[j];
+                }
+            m = num / den;
+        } else {
+            m = sum_of<CAP>(v, kept) / (double)__popc(kept);
+        }
     }
     *value = (uint32_t)fmin(fmax(rint(m), 0.0), 65535.0);
     *count = (uint32_t)__popc(kept);
 }
 
 // A thread's eight columns.
-template <int CAP, int MODE, bool FIELD>
-__device__ __forceinline__ void combine_octet(const CombineArgs& a, const FieldArgs* f) {
+template <int CAP, int MODE, bool FIELD, bool WEIGHT = false>
+__device__ __forceinline__ void combine_octet(const CombineArgs& a, const FieldArgs* f, const WeightArgs* w = nullptr) {
     const int c0 = (blockIdx.x * kLanesX + (int)threadIdx.x % kLanesX) * kOct, r = blockIdx.y * kRows + (int)threadIdx.x / kLanesX;
     if (r >= a.oh || c0 >= a.ow) return;
     const int nc = min(kOct, a.ow - c0);
@@ -242,7 +284,7 @@ __device__ __forceinline__ void combine_octet(const CombineArgs& a, const FieldA
             cell.fx = (double)rem / step_d;
             if (++rem == f->step) rem = 0, ++i;
         }
-        combine_pixel<CAP, MODE, FIELD>(a, f, r, c0 + j, zero, cell, &value, &count);
+        combine_pixel<CAP, MODE, FIELD, WEIGHT>(a, f, w, r, c0 + j, zero, cell, &value, &count);
         if (j < 4) lo |= (uint64_t)value << (16 * j);
         else hi |= (uint64_t)value << (16 * (j - 4));
         counts |= (uint64_t)count << (8 * j);
@@ -278,6 +320,11 @@ __global__ __launch_bounds__(kThreads) void k_stack_combine_field(const CombineA
 }
 
 template <int CAP, int MODE>
+__global__ __launch_bounds__(kThreads) void k_stack_combine_weighted(const CombineArgs a, const FieldArgs f, const WeightArgs w) {
+    combine_octet<CAP, MODE, true, true>(a, &f, &w);
+}
+
+template <int CAP, int MODE>
 int launch_mode(dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs* f) {
     if (!f) return shg::launch(k_stack_combine<CAP, MODE>, grid, dim3(kThreads), 0, st, a, "k_stack_combine");
     hipLaunchKernelGGL((k_stack_combine_field<CAP, MODE>), grid, dim3(kThreads), 0, st, a, *f);
@@ -298,6 +345,22 @@ int launch_combine(int mode, hipStream_t st, const CombineArgs& a, const FieldAr
     if (a.n <= 8) return launch_capacity<8>(mode, grid, st, a, f);
     if (a.n <= 16) return launch_capacity<16>(mode, grid, st, a, f);
     return launch_capacity<32>(mode, grid, st, a, f);
+}
+
+template <int CAP>
+int launch_weighted_capacity(int mode, dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs& f, const WeightArgs& w) {
+    if (mode == SHG_STACK_MEAN) hipLaunchKernelGGL((k_stack_combine_weighted<CAP, SHG_STACK_MEAN>), grid, dim3(kThreads), 0, st, a, f, w);
+    else hipLaunchKernelGGL((k_stack_combine_weighted<CAP, SHG_STACK_SIGMA>), grid, dim3(kThreads), 0, st, a, f, w);
+    return shg::check_launch("k_stack_combine_weighted");
+}
+
+// mode: SHG_STACK_MEAN or SHG_STACK_SIGMA
+int launch_weighted(int mode, hipStream_t st, const CombineArgs& a, const FieldArgs& f, const WeightArgs& w) {
+    const dim3 grid((unsigned)((a.ow + kLanesX * kOct - 1) / (kLanesX * kOct)), (unsigned)((a.oh + kRows - 1) / kRows));
+    if (a.n <= 4) return launch_weighted_capacity<4>(mode, grid, st, a, f, w);
+    if (a.n <= 8) return launch_weighted_capacity<8>(mode, grid, st, a, f, w);
+    if (a.n <= 16) return launch_weighted_capacity<16>(mode, grid, st, a, f, w);
+    return launch_weighted_capacity<32>(mode, grid, st, a, f, w);
 }
 
 using shg::overlap;
@@ -418,6 +481,32 @@ int combine_args(const char* fn, const uint16_t* const* host_srcs, const int64_t
     return 0;
 }
 
+// combine_args, then the lattice and the fields on it (host_fields may be null as a whole: no source has one).
+int lattice_args(const char* fn, const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
+                 const double* const* host_fields, int64_t gh, int64_t gw, int step, int n, int mode, double kappa, int iterations, uint16_t* out,
+                 int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count, int64_t count_pitch, CombineArgs* args, FieldArgs* fields) {
+    SHG_REQUIRE(step >= kMinStep && step <= kMaxStep, SHG_E_ARG, "%s: a lattice step of %d pixels (%d to %d)", fn, step, kMinStep, kMaxStep);
+    if (const int e = combine_args(fn, host_srcs, host_dims3, host_xform4, n, mode, kappa, iterations, out, oh, ow, out_pitch, count,
+                                   count_pitch, args))
+        return e;
+    SHG_REQUIRE(gh == (oh - 1 + step - 1) / step + 1 && gw == (ow - 1 + step - 1) / step + 1, SHG_E_ARG,
+                "%s: a lattice of %lld x %lld nodes does not cover %lld x %lld pixels at a step of %d", fn, (long long)gh, (long long)gw,
+                (long long)oh, (long long)ow, step);
+    const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
+    const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
+    FieldArgs& f = *fields;
+    for (int j = 0; j < n; ++j) {
+        f.field[j] = host_fields ? host_fields[j] : nullptr;
+        if (!f.field[j]) continue;
+        SHG_REQUIRE(reinterpret_cast<uintptr_t>(f.field[j]) % 16 == 0, SHG_E_ARG, "%s: field %d does not start on 16 bytes", fn, j);
+        const Span field_span = span_of(f.field[j], gh, gw * 2, gw * 2, sizeof(double));
+        SHG_REQUIRE(!overlap(out_span, field_span), SHG_E_ARG, "%s: the output overlaps field %d", fn, j);
+        SHG_REQUIRE(!count || !overlap(count_span, field_span), SHG_E_ARG, "%s: the count plane overlaps field %d", fn, j);
+    }
+    f.gh = (int)gh, f.gw = (int)gw, f.step = step;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
@@ -438,29 +527,42 @@ extern "C" int shg_stack_combine_field_u16(const uint16_t* const* host_srcs, con
                                            int64_t count_pitch, shg_stream_t stream) {
     const char* fn = "shg_stack_combine_field_u16";
     SHG_REQUIRE(host_fields, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(step >= kMinStep && step <= kMaxStep, SHG_E_ARG, "%s: a lattice step of %d pixels (%d to %d)", fn, step, kMinStep, kMaxStep);
     CombineArgs a{};
     FieldArgs f{};
-    if (const int e = combine_args(fn, host_srcs, host_dims3, host_xform4, n, mode, kappa, iterations, out, oh, ow, out_pitch, count,
-                                   count_pitch, &a))
+    if (const int e = lattice_args(fn, host_srcs, host_dims3, host_xform4, host_fields, gh, gw, step, n, mode, kappa, iterations, out, oh, ow,
+                                   out_pitch, count, count_pitch, &a, &f))
         return e;
-    SHG_REQUIRE(gh == (oh - 1 + step - 1) / step + 1 && gw == (ow - 1 + step - 1) / step + 1, SHG_E_ARG,
-                "%s: a lattice of %lld x %lld nodes does not cover %lld x %lld pixels at a step of %d", fn, (long long)gh, (long long)gw,
-                (long long)oh, (long long)ow, step);
-    const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
-    const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
-    for (int j = 0; j < n; ++j) {
-        f.field[j] = host_fields[j];
-        if (!host_fields[j]) continue;
-        SHG_REQUIRE(reinterpret_cast<uintptr_t>(host_fields[j]) % 16 == 0, SHG_E_ARG, "%s: field %d does not start on 16 bytes", fn, j);
-        const Span field_span = span_of(host_fields[j], gh, gw * 2, gw * 2, sizeof(double));
-        SHG_REQUIRE(!overlap(out_span, field_span), SHG_E_ARG, "%s: the output overlaps field %d", fn, j);
-        SHG_REQUIRE(!count || !overlap(count_span, field_span), SHG_E_ARG, "%s: the count plane overlaps field %d", fn, j);
-    }
-    f.gh = (int)gh, f.gw = (int)gw, f.step = step;
     hipStream_t st = shg::as_stream(stream);
     SHG_PROF("stack_combine_field", st);
     return launch_combine(mode, st, a, &f);
+}
+
+extern "C" int shg_stack_combine_weighted_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
+                                              const double* const* host_fields, const double* const* host_weights, int64_t gh, int64_t gw,
+                                              int step, int n, int mode, double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow,
+                                              int64_t out_pitch, uint8_t* count, int64_t count_pitch, shg_stream_t stream) {
+    const char* fn = "shg_stack_combine_weighted_u16";
+    SHG_REQUIRE(host_weights, SHG_E_ARG, "%s: null pointer", fn);
+    SHG_REQUIRE(mode != SHG_STACK_MEDIAN, SHG_E_ARG, "%s: there is no weighted median", fn);
+    CombineArgs a{};
+    FieldArgs f{};
+    WeightArgs w{};
+    if (const int e = lattice_args(fn, host_srcs, host_dims3, host_xform4, host_fields, gh, gw, step, n, mode, kappa, iterations, out, oh, ow,
+                                   out_pitch, count, count_pitch, &a, &f))
+        return e;
+    const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
+    const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
+    for (int j = 0; j < n; ++j) {
+        w.weight[j] = host_weights[j];
+        if (!host_weights[j]) continue;
+        SHG_REQUIRE(reinterpret_cast<uintptr_t>(host_weights[j]) % 8 == 0, SHG_E_ARG, "%s: weight lattice %d does not start on 8 bytes", fn, j);
+        const Span weight_span = span_of(host_weights[j], gh, gw, gw, sizeof(double));
+        SHG_REQUIRE(!overlap(out_span, weight_span), SHG_E_ARG, "%s: the output overlaps weight lattice %d", fn, j);
+        SHG_REQUIRE(!count || !overlap(count_span, weight_span), SHG_E_ARG, "%s: the count plane overlaps weight lattice %d", fn, j);
+    }
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF("stack_combine_weighted", st);
+    return launch_weighted(mode, st, a, f, w);
 }
 
 extern "C" int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w, int S,

@@ -1168,6 +1168,82 @@ def stack_combine_field_u16(images, transforms, fields, step, shape, mode='sigma
     return out, count
 
 
+# ---- ranking scans by sharpness: the sums of a quality figure a patch, and the combine with a weight lattice a source ----
+def patch_sharpness_u16(img, points, half, arm, circle=None, out=None):
+    """shg_patch_sharpness_u16: for each of the n points (row, col) -- an int32 [n, 2] tensor on the image's device, or a host array
+    that is uploaded -- over the pixels of the (2 half + 1)^2 patch of the uint16 image around it that lie at least `arm` from every
+    edge and, with `circle`, on that disk -> int64 [n, 4] on the image's device: the pixels of the set, the sum of I, the sum of I^2
+    and the sum of L^2 with L = 4 I[r, c] - I[r - arm, c] - I[r + arm, c] - I[r, c - arm] - I[r, c + arm] (a row of zeros for an empty
+    set).  half is 1 to 32, arm 1 to 8.  out: the caller's, overwritten."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    b, d = int(half), int(arm)
+    if not 1 <= b <= 32:
+        raise ValueError('half must be 1 to 32, got %r' % (half,))
+    if not 1 <= d <= 8:
+        raise ValueError('arm must be 1 to 8, got %r' % (arm,))
+    if not isinstance(points, torch.Tensor):
+        points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)).to(img.device)
+    if _dev(points, 'points').dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 2 or not points.is_contiguous():
+        raise ValueError('points must be a contiguous int32 [n, 2] tensor of (row, col)')
+    n = int(points.shape[0])
+    if n < 1:
+        raise ValueError('at least one point is needed')
+    c3 = _circle3_or_none(circle)
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.int64, device=img.device)
+    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int64 [%d, 4] tensor' % n)
+    _lib.check(lib.shg_patch_sharpness_u16(ptr, pitch, h, w, points.data_ptr(), n, b, d, _host_ptr(c3), out.data_ptr(), _stream()),
+               'shg_patch_sharpness_u16')
+    return out
+
+
+def stack_combine_weighted_u16(images, transforms, fields, weights, step, shape, mode='sigma', kappa=2.5, iterations=2, out=None, count=None,
+                               want_count=True):
+    """shg_stack_combine_weighted_u16: stack_combine_field_u16 with a weight lattice a source.  fields: None (no image has one) or one
+    entry an image as there; weights: one entry an image, None (weight 1 everywhere) or a contiguous float64 [gh, gw] tensor on the
+    images' device, one weight a node of lattice_shape(shape, step), the caller's to keep finite, >= 0 and <= 2^20.  A source's
+    weight at a pixel is bilinear between the four nodes around it; a source is present where stack_combine_field_u16 has it and
+    its weight is > 0; mode 'mean' or 'sigma' (the clipping does not see the weights; 'median' is a ValueError); the result is
+    sum (w v) / sum w over the kept samples in source order and count the kept samples.  Weights of None or 1 give
+    stack_combine_field_u16's result bit for bit -> (out uint16 [oh, ow], count uint8 [oh, ow] or None)."""
+    if mode not in STACK_MODES:
+        raise ValueError('mode is one of %s, got %r' % (', '.join(STACK_MODES), mode))
+    if mode == 'median':
+        raise ValueError('there is no weighted median: mode is mean or sigma')
+    images, weights = list(images), list(weights)
+    n = len(images)
+    fields = [None] * n if fields is None else list(fields)
+    xf = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4))
+    if n < 1 or xf.shape[0] != n or len(fields) != n or len(weights) != n:
+        raise ValueError('%d images, %d transforms (s, tx, ty, gain), %d fields and %d weight lattices' % (n, xf.shape[0], len(fields),
+                                                                                                           len(weights)))
+    if not 8 <= int(step) <= 128:
+        raise ValueError('step must be 8 to 128, got %r' % (step,))
+    geo = [_img(t, 'image', torch.uint16) for t in images]
+    dev = images[0].device
+    oh, ow = int(shape[0]), int(shape[1])
+    gh, gw = lattice_shape((oh, ow), step)
+    for f in fields:
+        if f is not None and (_dev(f, 'field').dtype != torch.float64 or tuple(f.shape) != (gh, gw, 2) or not f.is_contiguous()):
+            raise ValueError('a field is None or a contiguous float64 [%d, %d, 2] tensor' % (gh, gw))
+    for wt in weights:
+        if wt is not None and (_dev(wt, 'weights').dtype != torch.float64 or tuple(wt.shape) != (gh, gw) or not wt.is_contiguous()):
+            raise ValueError('a weight lattice is None or a contiguous float64 [%d, %d] tensor' % (gh, gw))
+    out, optr, opitch = _out_like(out, oh, ow, torch.uint16, dev)
+    cptr, cpitch = None, 0
+    if count is not None or want_count:
+        count, cptr, cpitch = _out_like(count, oh, ow, torch.uint8, dev, 'count')
+    ptrs = (ctypes.c_void_p * n)(*[g[0] for g in geo])
+    fptrs = None if all(f is None for f in fields) else (ctypes.c_void_p * n)(*[None if f is None else f.data_ptr() for f in fields])
+    wptrs = (ctypes.c_void_p * n)(*[None if wt is None else wt.data_ptr() for wt in weights])
+    dims = np.ascontiguousarray([[g[1], g[2], g[3]] for g in geo], dtype=np.int64)
+    _lib.check(lib.shg_stack_combine_weighted_u16(ptrs, _host_ptr(dims), _host_ptr(xf), fptrs, wptrs, gh, gw, int(step), n, STACK_MODES[mode],
+                                                  float(kappa), int(iterations), optr, oh, ow, opitch, cptr, cpitch, _stream()),
+               'shg_stack_combine_weighted_u16')
+    return out, count
+
+
 # ---- sharpening a disk: the a-trous wavelet layers with gains and gates, and the noise they are gated by ----
 def wavelet_sharpen_u16(img, gain_q8, threshold_q6=None, out=None, want_planes=False, workspace=None):
     """shg_wavelet_sharpen_u16: the uint16 image split into L = len(gain_q8) B3-spline a-trous layers (1 to 6) and put together again,
