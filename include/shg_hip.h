@@ -1096,7 +1096,8 @@ int shg_host_line_fit(const int32_t* host_trace_blur, const int32_t* host_trace_
 /* read_video_improved's per-shift sample columns and weights (solex_util.py:113-123) */
 int shg_host_column_plan(const double* host_fit, int64_t ih, int64_t iw, const int32_t* host_shifts, int n_shifts,
                          int32_t* host_ind_l, double* host_lw, double* host_rw);
-/* get_flood_image's threshold from the reduced image statistics (ellipse_to_circle.py:159-225) */
+/* get_flood_image's threshold from the reduced image statistics (ellipse_to_circle.py:159-225).  Empty data (a constant image:
+ * the kernels leave mn / mx as NaN and 20 zero counts): SHG_E_VALUE, never a threshold. */
 int shg_host_flood_threshold(double total, int64_t h, int64_t w, double mn, double mx, const int64_t* host_counts20,
                              double* thresh_out);
 /* get_edge_list after canny (ellipse_to_circle.py:251-291): region choice, convex-hull filter, row crop on the

@@ -371,6 +371,12 @@ extern "C" int shg_host_flood_threshold(double total, int64_t h, int64_t w, doub
                                         const int64_t* host_counts20, double* thresh_out) {
     SHG_HOST_TIME("host flood_threshold");
     SHG_REQUIRE(host_counts20 && thresh_out && h > 0 && w > 0, SHG_E_ARG, "shg_host_flood_threshold: bad argument");
+    // data is empty (a constant image: nothing lies below its own 99th percentile): the kernels leave mn / mx as the NaNs of their
+    // untouched accumulators.  The reference fails on such a disk as well; a threshold is never built on those numbers.
+    if (!(mn <= mx)) {
+        shg::set_error("ellipse fit: no pixel of the blurred image lies below its 99th percentile (a constant image?)");
+        return SHG_E_VALUE;
+    }
     const double thresh = 0.9 * total / (double)(h * w);
     if (mn == mx) { mn -= 0.5; mx += 0.5; }                      // np.histogram's range for constant data
     double bins[21];
