@@ -561,6 +561,40 @@ int shg_rl_deconvolve_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pit
                           uint16_t* out, int64_t out_pitch, float* estimate, void* workspace, size_t workspace_bytes,
                           shg_stream_t stream);
 
+/* ---- limb protection for the two filters above: the image split into a disk plane and a sky plane that have no step at the limb, and
+ * the filtered planes put back around the untouched limb (not reference stages; tests/limbguard_ref.py restates both calls in NumPy,
+ * bit for bit).  Everything is float64, one IEEE operation a step, no contraction; sqrt and / are correctly rounded.
+ * circle3 (host) = (cx, cy, rad); E = rad - margin, F = rad + margin.  For the pixel in row r, column c:
+ *   dx = (double)c - cx, dy = (double)r - cy, d2 = dx * dx + dy * dy, rho = sqrt(d2);
+ *   ux = dx / rho, uy = dy / rho when rho > 0, else ux = 1, uy = 0                       (the pixel's ray);
+ *   sample(t) = bilin(cx + ux * t, cy + uy * t)                                           (the image at the distance t on that ray);
+ *   bilin(x, y): x clamped to [0, w - 1], y to [0, h - 1]; x0 = (int64)x, x1 = min(x0 + 1, w - 1), fx = x - (double)x0, and y0, y1, fy
+ *     likewise; with a = img[y0][x0], b = img[y0][x1], c' = img[y1][x0], d = img[y1][x1] as doubles:
+ *     top = a + (b - a) * fx, bot = c' + (d - c') * fx, bilin = top + (bot - top) * fy    (well defined for w = 1 or h = 1);
+ *   Q(v) = (uint16)clip(rint(v), 0, 65535), rint to nearest, ties to even.
+ * shg_limb_split_u16: one launch, one read of img, two planes; inner or outer may be NULL, not both.
+ *   inner[r][c] = img[r][c] where not rho > E; elsewhere, with s = sample(E): Q((s + s) - sample(max((E + E) - rho, E - reach)));
+ *   outer[r][c] = img[r][c] where not rho < F; elsewhere, with s = sample(F): Q((s + s) - sample(min((F + F) - rho, F + reach))).
+ *   Each plane continues the image across the limb by a POINT REFLECTION about its value at the edge of what it keeps: continuous in
+ *   value and in slope along the ray.  Beyond `reach` the continuation holds a plateau along the ray.
+ * shg_limb_merge_u16: disk and sky are the filtered inner and outer planes; sky may be NULL.  With o = (double)img[r][c]:
+ *   rho < E:                 wt = min((E - rho) / blend, 1), out = Q(o + wt * ((double)disk[r][c] - o));
+ *   rho > F and sky given:   wt = min((rho - F) / blend, 1), out = Q(o + wt * ((double)sky[r][c] - o));
+ *   otherwise                out = img[r][c].
+ *   Two consequences the tests use: the band E <= rho <= F of out is img bit for bit; where wt = 1 (o + (d - o) is exact for two
+ *   16-bit values) out is disk, or sky, bit for bit.
+ * Every pixel's value is a fixed expression of its inputs: neither the launch grid nor any early-out of the kernels can change a bit.
+ * 1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG, with nothing written, for a null pointer it does not allow, a pitch below w,
+ * a circle3, margin, reach or blend that is not finite, rad <= 0, rad >= 16384, |cx| or |cy| >= 65536 (the limits of
+ * shg_ring_medians_u16: every coordinate of a sample stays finite), margin < 0, E < 1, reach < 1, reach > E, blend <= 0, and an output
+ * that overlaps an input or the other output.  The calls allocate nothing, wait for nothing and copy nothing from the device.
+ * Elements between w and a pitch are never touched. */
+int shg_limb_split_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, double margin, double reach,
+                       uint16_t* inner, int64_t inner_pitch, uint16_t* outer, int64_t outer_pitch, shg_stream_t stream);
+int shg_limb_merge_u16(const uint16_t* img, int64_t pitch, const uint16_t* disk, int64_t disk_pitch, const uint16_t* sky, int64_t sky_pitch,
+                       int64_t h, int64_t w, const double* circle3, double margin, double blend, uint16_t* out, int64_t out_pitch,
+                       shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

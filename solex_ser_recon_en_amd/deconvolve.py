@@ -4,11 +4,13 @@ The iterations are HIP kernels in float32 whose arithmetic include/shg_hip.h sta
 taps are host float64, written step by step so that the tests restate them.
 
     python -m solex_ser_recon_en_amd.deconvolve INPUT [--psf-sigma X] [--iterations N] [--radius R] [--shift S] [--contrast]
-        [SHG_MAIN flags]
+        [--circle cx,cy,rad] [--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only] [SHG_MAIN flags]
 
-Richardson-Lucy amplifies noise: it suits a stack, and a single scan only for a few iterations.  Out of scope: point-spread
-functions that are not separable, measuring the blur from the limb, limb protection or damping against ringing, regularised or
-blind variants, stopping rules, and any change to the stack, flatten or sharpen command lines.
+Richardson-Lucy amplifies noise: it suits a stack, and a single scan only for a few iterations.  The limb is a step, and the
+iterations ring on it: --limb-protect (limb=) runs them on a disk plane and a sky plane that have no step and leaves the band of
+the limb as it is (limbguard.py).  Out of scope: point-spread functions that are not separable, measuring
+the blur from the limb, damping against ringing, regularised or blind variants, stopping rules, and any change to the stack or
+flatten command lines.
 """
 import argparse
 import math
@@ -17,7 +19,7 @@ import sys
 
 import numpy as np
 
-from . import disk
+from . import disk, limbguard
 
 MAX_RADIUS = 16
 MAX_ITERATIONS = 200
@@ -50,10 +52,12 @@ def _check_iterations(iterations):
     return int(iterations)
 
 
-def deconvolve_disk(image, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None):
+def deconvolve_disk(image, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None, limb=None):
     """The uint16 device image after `iterations` Richardson-Lucy iterations with the separable blur of `taps` (2 R + 1 float32
     values, as ops.rl_deconvolve_u16 takes them), or, without taps, of gaussian_taps(sigma, radius) (sigma None: 1.2) -> (the
-    deconvolved uint16 device image, the record {'sigma' (None with given taps), 'radius', 'taps', 'iterations'})."""
+    deconvolved uint16 device image, the record {'sigma' (None with given taps), 'radius', 'taps', 'iterations'}).  limb: a dict
+    {'circle': (cx, cy, rad), 'margin' (default: the taps' radius), 'blend', 'reach', 'sky'} runs the iterations under
+    limbguard.protect -- on the disk plane and, unless sky is False, on the sky plane --, and the record gains 'limb', protect's."""
     from . import ops
     from .device import to_device_u16
     iterations = _check_iterations(iterations)
@@ -64,55 +68,87 @@ def deconvolve_disk(image, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None,
         if sigma is not None or radius is not None:
             raise ValueError('taps come without sigma and radius')
         k = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-    out, _ = ops.rl_deconvolve_u16(to_device_u16(image), k, iterations)
-    return out, {'sigma': sigma, 'radius': int(k.size // 2), 'taps': [float(v) for v in k], 'iterations': iterations}
+    record = {'sigma': sigma, 'radius': int(k.size // 2), 'taps': [float(v) for v in k], 'iterations': iterations}
+    if limb is None:
+        out, _ = ops.rl_deconvolve_u16(to_device_u16(image), k, iterations)
+        return out, record
+    circle, margin, blend, reach, sky = limbguard.settings(limb, float(k.size // 2))
+    out, record['limb'] = limbguard.protect(image, circle, lambda plane: ops.rl_deconvolve_u16(plane, k, iterations)[0], margin, blend,
+                                            reach, sky)
+    return out, record
 
 
-def deconvolve_scan(file_or_reader, options=None, shift=0, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None):
+def deconvolve_scan(file_or_reader, options=None, shift=0, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None, limb=None):
     """A scan's disk at `shift` (disk.scan_disk, with its refusals: ratio_fixe / slant_fix, de-vignette, a frame shard),
     deconvolved by deconvolve_disk -> {'image', 'deconv' (uint16 device tensors), 'circle', 'record', 'shift', 'ratio', 'phi',
-    'crop'}."""
+    'crop'}.  limb: deconvolve_disk's dict without 'circle': the scan's own limb fit is the circle."""
     scan = disk.scan_disk(file_or_reader, options, shift, 'deconvolution')
-    deconv, record = deconvolve_disk(scan['image'], sigma, iterations, taps, radius)
+    if limb is not None:
+        if not isinstance(limb, dict) or limb.get('circle') is not None:
+            raise ValueError('a scan brings its own limb fit: limb is a dict without a circle')
+        limb = dict(limb, circle=scan['circle'])
+    deconv, record = deconvolve_disk(scan['image'], sigma, iterations, taps, radius, limb)
     return {'image': scan['image'], 'deconv': deconv, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
             'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
 
 
 # ---- command line ---------------------------------------------------------------------------------
+def _floats(text):
+    try:
+        return [float(v) for v in text.split(',') if v.strip() != '']
+    except ValueError:
+        raise argparse.ArgumentTypeError('a comma-separated list of numbers, got %r' % text)
+
+
 def main(argv=None):
     from .linemaps import _print_json
     from .video_reader import video_reader
     p = argparse.ArgumentParser(
         prog='python -m solex_ser_recon_en_amd.deconvolve',
-        usage='%(prog)s INPUT [--psf-sigma X] [--iterations N] [--radius R] [--shift S] [--contrast] [SHG_MAIN flags]',
+        usage='%(prog)s INPUT [--psf-sigma X] [--iterations N] [--radius R] [--shift S] [--contrast] [--circle cx,cy,rad] '
+              '[--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only] [SHG_MAIN flags]',
         description='Deconvolve a disk: Richardson-Lucy iterations with a Gaussian point-spread function.  INPUT is a SER or AVI scan, or '
                     'a 16-bit grey PNG this package wrote (_stack.png, _flat.png, _uncontrasted.png).  The iterations amplify noise: '
-                    'give a stack many, a single scan few.  No limb protection: the limb rings.')
+                    'give a stack many, a single scan few.  The limb rings unless --limb-protect is given.')
     p.add_argument('--psf-sigma', type=float, default=DEFAULT_SIGMA,
                    help='the blur\'s Gaussian sigma in pixels, %g to %g (default %g)' % (MIN_SIGMA, MAX_SIGMA, DEFAULT_SIGMA))
     p.add_argument('--iterations', type=int, default=DEFAULT_ITERATIONS, help='1 to %d (default %d)' % (MAX_ITERATIONS, DEFAULT_ITERATIONS))
     p.add_argument('--radius', type=int, default=None, help='the taps reach this far, 0 to %d (default: ceil(4 sigma))' % MAX_RADIUS)
     p.add_argument('--shift', type=int, default=0, help='pixel shift of a scan\'s disk (the -w shift; default 0: the line centre)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the deconvolved image (<base>_deconv_clahe.png, ...)')
+    p.add_argument('--circle', type=_floats, default=None, help='cx,cy,rad of the disk in a PNG: what --limb-protect and --contrast go by')
+    limbguard.add_arguments(p, 'the radius of the taps')
+    limb = []
 
     def checks(args):
         try:
-            gaussian_taps(args.psf_sigma, args.radius)
+            taps = gaussian_taps(args.psf_sigma, args.radius)
             _check_iterations(args.iterations)
         except ValueError as e:
             p.error(str(e))
+        if args.circle is not None and len(args.circle) != 3:
+            p.error('--circle is cx,cy,rad')
+        limb.append(limbguard.from_arguments(p, args, args.circle, float(taps.size // 2)))
 
-    args, opts, (path,) = disk.parse(p, argv, 'deconvolve', 'deconvolution', checks, need='exactly one SER, AVI or PNG file is needed', png=True)
+    def file_checks(args, files):
+        if limb[0] is not None and args.circle is None and any(f.lower().endswith('.png') for f in files):
+            p.error('--limb-protect on a PNG needs --circle cx,cy,rad')
+
+    args, opts, (path,) = disk.parse(p, argv, 'deconvolve', 'deconvolution', checks, file_checks,
+                                     need='exactly one SER, AVI or PNG file is needed', png=True)
     is_png = path.lower().endswith('.png')
+    limb = limb[0]
     try:
         if is_png:
             img, header_source, stem = disk.png_input(path, opts)
-            deconv, record = deconvolve_disk(img, args.psf_sigma, args.iterations, radius=args.radius)
-            res = {'circle': (-1, -1, -1), 'ratio': None, 'phi': None, 'crop': None}
+            deconv, record = deconvolve_disk(img, args.psf_sigma, args.iterations, radius=args.radius, limb=limb)
+            res = {'circle': (-1, -1, -1) if args.circle is None else tuple(args.circle), 'ratio': None, 'phi': None, 'crop': None}
             total = float(img.astype(np.float64).sum())
         else:
+            if args.circle is not None:
+                raise ValueError('--circle goes with a PNG: a scan brings its own limb fit')
             header_source = video_reader(path)
-            res = deconvolve_scan(header_source, opts, args.shift, args.psf_sigma, args.iterations, radius=args.radius)
+            res = deconvolve_scan(header_source, opts, args.shift, args.psf_sigma, args.iterations, radius=args.radius, limb=limb)
             deconv, record = res['deconv'], res['record']
             stem = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift'])
             total = float(disk.host_u(res['image'].contiguous(), np.uint16).astype(np.float64).sum())
@@ -123,6 +159,8 @@ def main(argv=None):
     out = {'input': path, 'shape': list(host.shape), 'psf_sigma': record['sigma'], 'radius': record['radius'], 'taps': record['taps'],
            'iterations': record['iterations'], 'flux': float(host.astype(np.float64).sum()) / total if total else None,
            'shift': None if is_png else res['shift'], 'png': png, 'fits': fits, 'contrast': None}
+    if limb is not None:
+        out['limb'] = record['limb']
     if args.contrast:
         out['contrast'] = disk.contrast_products(deconv, tuple(res['circle']), opts, header_source, stem + '_deconv')
     return _print_json(out, res)

@@ -1307,3 +1307,59 @@ def rl_deconvolve_u16(img, taps, iterations, out=None, want_estimate=False, work
                                          None if estimate is None else estimate.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
                'shg_rl_deconvolve_u16')
     return out, estimate
+
+
+# ---- limb protection: the image as a disk plane and a sky plane without the limb's step, and the filtered planes put back ----
+def _limb_ring(circle, margin):
+    """(circle as a host float64 [3] array, margin as a float); ValueError unless rad > 0, margin >= 0 and rad - margin >= 1."""
+    c3, _ = _circle3(circle)
+    if not (isinstance(margin, (int, float, np.integer, np.floating)) and np.isfinite(margin) and margin >= 0.0):
+        raise ValueError('margin is finite and >= 0, got %r' % (margin,))
+    if not (c3[2] > 0.0 and c3[2] - float(margin) >= 1.0):
+        raise ValueError('rad - margin is at least 1, got a radius of %r and a margin of %r' % (float(c3[2]), margin))
+    return c3, float(margin)
+
+
+def limb_split_u16(img, circle, margin, reach, inner=None, outer=None, want_inner=True, want_outer=True):
+    """shg_limb_split_u16: the uint16 image as two planes without the step at the limb of `circle` (cx, cy, r) -> (inner, outer)
+    uint16 [h, w]: inner is the image out to r - margin and its point reflection about that edge beyond it, outer the image from
+    r + margin outwards and its point reflection inwards; both hold a plateau beyond `reach` (1 to r - margin) pixels from their
+    edge.  want_inner / want_outer False: None in that place (not both).  inner, outer: the caller's views, which must overlap
+    neither the image nor each other."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    c3, margin = _limb_ring(circle, margin)
+    if not (isinstance(reach, (int, float, np.integer, np.floating)) and np.isfinite(reach) and 1.0 <= reach <= c3[2] - margin):
+        raise ValueError('reach lies in [1, rad - margin = %r], got %r' % (float(c3[2] - margin), reach))
+    if not (want_inner or want_outer):
+        raise ValueError('at least one of the two planes')
+    iptr = optr = None
+    ipitch = opitch = 0
+    if want_inner:
+        inner, iptr, ipitch = _out_like(inner, h, w, torch.uint16, img.device, 'inner')
+    if want_outer:
+        outer, optr, opitch = _out_like(outer, h, w, torch.uint16, img.device, 'outer')
+    _lib.check(lib.shg_limb_split_u16(ptr, h, w, pitch, _host_ptr(c3), margin, float(reach), iptr, ipitch, optr, opitch, _stream()),
+               'shg_limb_split_u16')
+    return (inner if want_inner else None), (outer if want_outer else None)
+
+
+def limb_merge_u16(img, disk, sky, circle, margin, blend, out=None):
+    """shg_limb_merge_u16: the filtered planes put back -> uint16 [h, w]: `disk` inside r - margin and `sky` (None: the image)
+    beyond r + margin, each blended into the image over `blend` pixels from that edge, and the image itself in between.  out: the
+    caller's view, which must overlap none of the three."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    dptr, dh, dw, dpitch = _img(disk, 'disk', torch.uint16)
+    sptr, spitch = None, 0
+    if sky is not None:
+        sptr, sh, sw, spitch = _img(sky, 'sky', torch.uint16)
+        if (sh, sw) != (h, w):
+            raise ValueError('sky must be a uint16 [%d, %d] view' % (h, w))
+    if (dh, dw) != (h, w):
+        raise ValueError('disk must be a uint16 [%d, %d] view' % (h, w))
+    c3, margin = _limb_ring(circle, margin)
+    if not (isinstance(blend, (int, float, np.integer, np.floating)) and np.isfinite(blend) and blend > 0.0):
+        raise ValueError('blend is finite and > 0, got %r' % (blend,))
+    out, optr, opitch = _out_like(out, h, w, torch.uint16, img.device)
+    _lib.check(lib.shg_limb_merge_u16(ptr, pitch, dptr, dpitch, sptr, spitch, h, w, _host_ptr(c3), margin, float(blend), optr, opitch,
+                                      _stream()), 'shg_limb_merge_u16')
+    return out

@@ -4,9 +4,12 @@ the noise measure are HIP kernels in integers (ops.wavelet_sharpen_u16, ops.wave
 gate factors into their integer arguments is host float64, written step by step so that the tests restate it.
 
     python -m solex_ser_recon_en_amd.sharpen INPUT [--levels L] [--gains g1,..] [--denoise k1,..] [--sigma X] [--circle cx,cy,rad]
-        [--region F] [--shift S] [--contrast] [SHG_MAIN flags]
+        [--region F] [--shift S] [--contrast] [--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only]
+        [SHG_MAIN flags]
 
-Out of scope: limb protection (the limb's edge overshoots into the sky) and any change to the stack or flatten command lines.
+The limb's edge overshoots into the sky unless --limb-protect (limb=) is given: the layers are then taken of a disk plane and a sky
+plane that have no step, and the band of the limb stays as it is (limbguard.py).  Out of scope: any change
+to the stack or flatten command lines.
 Deconvolution by the instrument-and-seeing blur is a step of its own, before this one (deconvolve.py): its
 _deconv.png is an input here.
 """
@@ -17,7 +20,7 @@ import sys
 
 import numpy as np
 
-from . import disk
+from . import disk, limbguard
 
 MAX_LEVELS = 6
 MAX_GAIN = 16.0
@@ -27,6 +30,7 @@ DEFAULT_LEVELS = 4
 DEFAULT_GAINS = (1.0, 1.8, 1.4, 1.0)
 DEFAULT_DENOISE = (3.0, 1.0, 0.0, 0.0)
 DEFAULT_REGION = 0.9
+DEFAULT_LIMB_MARGIN = 6.0
 
 
 def quantise_gains(gains):
@@ -110,11 +114,13 @@ def estimate_sigma(image, circle=None, region=DEFAULT_REGION):
     return sigma_from_median(median), median, count
 
 
-def sharpen_disk(image, gains, denoise=(), sigma=None, circle=None, region=DEFAULT_REGION):
+def sharpen_disk(image, gains, denoise=(), sigma=None, circle=None, region=DEFAULT_REGION, limb=None):
     """The uint16 device image sharpened: len(gains) layers, layer j times gains[j] after a soft threshold at denoise[j] times the
     layer's noise (denoise shorter than gains: 0 beyond it).  sigma None: estimate_sigma(image, circle, region) -> (the sharpened
     uint16 device image, the record {'levels', 'gains' (as quantised), 'gain_q8', 'denoise', 'sigma', 'median_q6', 'pixels' (None
-    with a given sigma), 'threshold_q6', 'thresholds' (in counts)})."""
+    with a given sigma), 'threshold_q6', 'thresholds' (in counts)}).  limb: a dict {'circle' (default: `circle`), 'margin' (default 6),
+    'blend', 'reach', 'sky'} sharpens under limbguard.protect -- the disk plane and, unless sky is False, the sky plane, both with
+    the thresholds of the noise measured once, on the image itself --, and the record gains 'limb', protect's."""
     from . import ops
     from .device import to_device_u16
     t = to_device_u16(image)
@@ -124,10 +130,15 @@ def sharpen_disk(image, gains, denoise=(), sigma=None, circle=None, region=DEFAU
     if sigma is None:
         sigma, median, pixels = estimate_sigma(t, circle, region)
     thr = thresholds(float(sigma), denoise, levels)
-    out, _ = ops.wavelet_sharpen_u16(t, gain_q8, thr)
     k = [float(v) for v in denoise] + [0.0] * (levels - len(list(denoise)))
-    return out, {'levels': levels, 'gains': (gain_q8 / 256.0).tolist(), 'gain_q8': gain_q8.tolist(), 'denoise': k, 'sigma': float(sigma),
-                 'median_q6': median, 'pixels': pixels, 'threshold_q6': thr.tolist(), 'thresholds': (thr / 64.0).tolist()}
+    record = {'levels': levels, 'gains': (gain_q8 / 256.0).tolist(), 'gain_q8': gain_q8.tolist(), 'denoise': k, 'sigma': float(sigma),
+              'median_q6': median, 'pixels': pixels, 'threshold_q6': thr.tolist(), 'thresholds': (thr / 64.0).tolist()}
+    if limb is None:
+        out, _ = ops.wavelet_sharpen_u16(t, gain_q8, thr)
+        return out, record
+    ring, margin, blend, reach, sky = limbguard.settings(limb, DEFAULT_LIMB_MARGIN, circle)
+    out, record['limb'] = limbguard.protect(t, ring, lambda plane: ops.wavelet_sharpen_u16(plane, gain_q8, thr)[0], margin, blend, reach, sky)
+    return out, record
 
 
 def wavelet_planes(image, levels):
@@ -138,12 +149,16 @@ def wavelet_planes(image, levels):
     return ops.wavelet_sharpen_u16(to_device_u16(image), [256] * _check_levels(levels), want_planes=True)[1]
 
 
-def sharpen_scan(file_or_reader, options=None, shift=0, gains=DEFAULT_GAINS, denoise=DEFAULT_DENOISE, sigma=None, region=DEFAULT_REGION):
+def sharpen_scan(file_or_reader, options=None, shift=0, gains=DEFAULT_GAINS, denoise=DEFAULT_DENOISE, sigma=None, region=DEFAULT_REGION,
+                 limb=None):
     """A scan's disk at `shift` (disk.scan_disk, with its refusals: ratio_fixe / slant_fix, de-vignette, a frame
     shard), sharpened by sharpen_disk with the noise measured inside region * rad of the fitted circle -> {'image', 'sharp' (uint16
-    device tensors), 'circle', 'record', 'shift', 'ratio', 'phi', 'crop'}."""
+    device tensors), 'circle', 'record', 'shift', 'ratio', 'phi', 'crop'}.  limb: sharpen_disk's dict without 'circle': the scan's own
+    limb fit is the circle."""
     scan = disk.scan_disk(file_or_reader, options, shift, 'sharpening')
-    sharp, record = sharpen_disk(scan['image'], gains, denoise, sigma, scan['circle'], region)
+    if limb is not None and (not isinstance(limb, dict) or limb.get('circle') is not None):
+        raise ValueError('a scan brings its own limb fit: limb is a dict without a circle')
+    sharp, record = sharpen_disk(scan['image'], gains, denoise, sigma, scan['circle'], region, limb)
     return {'image': scan['image'], 'sharp': sharp, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
             'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
 
@@ -162,12 +177,12 @@ def main(argv=None):
     p = argparse.ArgumentParser(
         prog='python -m solex_ser_recon_en_amd.sharpen',
         usage='%(prog)s INPUT [--levels L] [--gains g1,..] [--denoise k1,..] [--sigma X] [--circle cx,cy,rad] [--region F] [--shift S] '
-              '[--contrast] [SHG_MAIN flags]',
+              '[--contrast] [--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only] [SHG_MAIN flags]',
         description='Sharpen a disk with B3-spline a-trous wavelet layers: one gain a layer and a soft noise gate on the finest layers.  '
                     'INPUT is a SER or AVI scan, or a 16-bit grey PNG this package wrote (_stack.png, _flat.png, _uncontrasted.png).  '
                     'For a PNG without --circle the noise is measured over the whole image: a black sky biases the estimate low '
-                    '(--circle confines it to the disk, --sigma skips the estimate).  No limb protection: the limb\'s edge overshoots '
-                    'into the sky.')
+                    '(--circle confines it to the disk, --sigma skips the estimate).  The limb\'s edge overshoots into the sky unless '
+                    '--limb-protect is given.')
     p.add_argument('--levels', type=int, default=None, help='layers, 1 to 6 (default %d, or as many as --gains names)' % DEFAULT_LEVELS)
     p.add_argument('--gains', type=_floats, default=None,
                    help='gain of every layer, finest first, 0 to 16 (default %s; fewer than --levels: the rest 1)' % ','.join('%g' % g for g in DEFAULT_GAINS))
@@ -178,6 +193,12 @@ def main(argv=None):
     p.add_argument('--region', type=float, default=DEFAULT_REGION, help='fraction of the radius the noise is measured within (default %g)' % DEFAULT_REGION)
     p.add_argument('--shift', type=int, default=0, help='pixel shift of a scan\'s disk (the -w shift; default 0: the line centre)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the sharpened image (<base>_sharp_clahe.png, ...)')
+    limbguard.add_arguments(p, '%g' % DEFAULT_LIMB_MARGIN)
+    limb = []
+
+    def file_checks(args, files):
+        if limb[0] is not None and args.circle is None and any(f.lower().endswith('.png') for f in files):
+            p.error('--limb-protect on a PNG needs --circle cx,cy,rad')
 
     def checks(args):
         levels = args.levels
@@ -199,20 +220,25 @@ def main(argv=None):
             _noise_circle(args.circle, args.region)
         except ValueError as e:
             p.error(str(e))
+        limb.append(limbguard.from_arguments(p, args, args.circle, DEFAULT_LIMB_MARGIN))
 
-    args, opts, (path,) = disk.parse(p, argv, 'sharpen', 'sharpening', checks, need='exactly one SER, AVI or PNG file is needed', png=True)
+    args, opts, (path,) = disk.parse(p, argv, 'sharpen', 'sharpening', checks, file_checks, need='exactly one SER, AVI or PNG file is needed',
+                                     png=True)
     is_png = path.lower().endswith('.png')
+    limb = limb[0]
     try:
         if is_png:
             img, header_source, stem = disk.png_input(path, opts)
             circle = None if args.circle is None else tuple(args.circle)
-            sharp, record = sharpen_disk(img, args.gains, args.denoise, args.sigma, circle, args.region)
+            sharp, record = sharpen_disk(img, args.gains, args.denoise, args.sigma, circle, args.region, limb)
             res = {'circle': circle if circle is not None else (-1, -1, -1), 'ratio': None, 'phi': None, 'crop': None}
         else:
             if args.circle is not None:
                 raise ValueError('--circle goes with a PNG: a scan brings its own limb fit')
             header_source = video_reader(path)
-            res = sharpen_scan(header_source, opts, args.shift, args.gains, args.denoise, args.sigma, args.region)
+            if limb is not None:
+                limb.pop('circle', None)
+            res = sharpen_scan(header_source, opts, args.shift, args.gains, args.denoise, args.sigma, args.region, limb)
             sharp, record = res['sharp'], res['record']
             stem = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift'])
     except ValueError as e:
@@ -223,6 +249,8 @@ def main(argv=None):
            'sigma': record['sigma'], 'median': None if record['median_q6'] is None else record['median_q6'] / 64.0,
            'pixels': record['pixels'], 'thresholds': record['thresholds'], 'shift': None if is_png else res['shift'], 'png': png,
            'fits': fits, 'contrast': None}
+    if limb is not None:
+        out['limb'] = record['limb']
     if args.contrast:
         out['contrast'] = disk.contrast_products(sharp, tuple(res['circle']), opts, header_source, stem + '_sharp')
     return _print_json(out, res)
