@@ -1,4 +1,4 @@
-// What the host code of the disk products' entry points (rings.hip, stack.hip, wavelet.hip, deconvolve.hip) and of the map detrend
+// What the host code of the disk products' entry points (rings.hip, stack.hip, wavelet.hip, deconvolve.hip), of the patch kernels (patch_args.h) and of the map detrend
 // (detrend.hip) share: the checks of an image argument, byte spans and their overlap, row alignment, the workspace's round-up, the optional disk
 // mask and the cleared table.  Host only: no kernel and no kernel argument struct is declared here.
 #pragma once
@@ -13,12 +13,16 @@ constexpr int kMaxImageDim = 16384;
 
 inline bool image_dims_ok(int64_t h, int64_t w) { return h >= 1 && h <= kMaxImageDim && w >= 1 && w <= kMaxImageDim; }
 
-inline int check_image(const char* fn, const void* img, int64_t h, int64_t w, int64_t pitch) {
-    SHG_REQUIRE(img, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(image_dims_ok(h, w), SHG_E_UNSUPPORTED, "%s: an image of %lld x %lld (1 to %d either way)", fn, (long long)h, (long long)w,
+// `pointers`: none of the entry point's pointers is null; `images`: "an image", or "images" of one shape with `pitch` the smallest.
+inline int check_images(const char* fn, bool pointers, const char* images, int64_t h, int64_t w, int64_t pitch) {
+    SHG_REQUIRE(pointers, SHG_E_ARG, "%s: null pointer", fn);
+    SHG_REQUIRE(image_dims_ok(h, w), SHG_E_UNSUPPORTED, "%s: %s of %lld x %lld (1 to %d either way)", fn, images, (long long)h, (long long)w,
                 kMaxImageDim);
     SHG_REQUIRE(pitch >= w, SHG_E_ARG, "%s: pitch < w", fn);
     return 0;
+}
+inline int check_image(const char* fn, const void* img, int64_t h, int64_t w, int64_t pitch) {
+    return check_images(fn, img != nullptr, "an image", h, w, pitch);
 }
 
 // [p, p + ((h - 1) pitch + w) item) of an image

@@ -3,25 +3,18 @@
 // is the one include/shg_hip.h states, restated in NumPy by tests/quality_ref.py.  The host places the points and turns the sums
 // into a quality figure (stack.py); the combine that weights each source by a lattice of such figures is in stack.hip.
 //
-// One workgroup a point, the layout of align.hip.  The patch with its halo of D pixels sits in LDS (at most 81 x 81 x 2 B, the
-// pitch 81: odd, rows fall on different banks); a thread owns the pixels threadIdx.x + 256 k of the patch in row-major order, at
-// most 17 of the 65 x 65, reads a pixel and its four arms from the tile and keeps four 64-bit sums.  The wave folds them with
-// DPP, the first lane puts the wave's totals into its wave's row of a table in LDS, and four threads add the rows and write the
-// point's four words by plain stores.  No global atomic, no memset, and everything accumulated is an integer: no grid shape or
-// order can change a bit.  Whether a pixel is in the set is decided before anything is loaded: an empty set writes its row of
-// zeros and returns without a read of the image.
-#include "image_args.h"
+// The frame is patch_args.h's.  A thread reads each of its at most 17 pixels and its four arms from the tile and keeps four 64-bit
+// sums; the wave folds them with DPP and the first lane puts the wave's totals into its wave's row of the table in LDS.  No global
+// atomic, no memset, and everything accumulated is an integer: no grid shape or order can change a bit.  Whether a pixel is in the
+// set is decided before anything is loaded: an empty set writes its row of zeros and returns without a read of the image.
+#include "patch_args.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxB = 32, kMaxD = 8;
-constexpr int kMaxSide = 2 * kMaxB + 1;                         // 65
-constexpr int kTile = kMaxSide + 2 * kMaxD;                     // 81: the LDS tile's side and its pitch
-constexpr int kPerThread = (kMaxSide * kMaxSide + kThreads - 1) / kThreads;      // 17
+using namespace shg::patch;
+
+constexpr int kMaxD = kMaxMargin;
 constexpr int kWords = 4;                                       // the size of the set, the sums of I, I^2 and L^2
-constexpr int64_t kMaxPoints = (int64_t)1 << 23;
 
 struct SharpArgs {
     const uint16_t* img;
@@ -35,36 +28,16 @@ struct SharpArgs {
 __global__ __launch_bounds__(kThreads) void k_patch_sharpness(const SharpArgs a) {
     __shared__ uint16_t tile[kTile * kTile];
     __shared__ unsigned long long part[kWaves][kWords];
-    const int D = a.D, ps = 2 * a.B + 1, pixels = ps * ps, per = (pixels + kThreads - 1) / kThreads;
+    const int D = a.D, ps = 2 * a.B + 1;
     unsigned long long* row = a.out + (int64_t)blockIdx.x * kWords;
-    // the patch's first row and column; 64-bit: a centre may lie anywhere
-    const int64_t r0 = (int64_t)a.points[2 * blockIdx.x] - a.B, c0 = (int64_t)a.points[2 * blockIdx.x + 1] - a.B;
-    uint32_t valid = 0;
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-        const int i = (int)threadIdx.x + k * kThreads;
-        if (k < per && i < pixels) {
-            const int y = i / ps, x = i - y * ps;
-            const int64_t r = r0 + y, c = c0 + x;
-            bool ok = c >= D && c < a.w - D && r >= D && r < a.h - D;
-            if (ok && a.masked) {
-                const double dx = (double)c - a.cx, dy = (double)r - a.cy, d2 = dx * dx + dy * dy;
-                ok = !(d2 > a.rad2);
-            }
-            if (ok) valid |= 1u << k;
-        }
-    }
+    int64_t r0, c0;
+    patch_origin(a, &r0, &c0);
+    const uint32_t valid = pixels_of_set(a, r0, c0, ps, D);
     if (!__syncthreads_or(valid != 0)) {                                         // an empty set: a row of zeros
         if (threadIdx.x < kWords) row[threadIdx.x] = 0;
         return;
     }
-    const int ts = ps + 2 * D;
-    for (int i = threadIdx.x; i < ts * ts; i += kThreads) {
-        const int y = i / ts, x = i - y * ts;
-        const int64_t gr = r0 - D + y, gc = c0 - D + x;
-        // (outside the image: a pixel of the set never reads it)
-        tile[y * kTile + x] = gr >= 0 && gr < a.h && gc >= 0 && gc < a.w ? a.img[gr * a.pitch + gc] : (uint16_t)0;
-    }
+    load_tile(tile, a.img, a.pitch, a.h, a.w, r0, c0, ps, D);
     __syncthreads();
     uint64_t n_valid = 0, sum1 = 0, sum2 = 0, sum_l2 = 0;
 #pragma unroll
@@ -85,12 +58,7 @@ __global__ __launch_bounds__(kThreads) void k_patch_sharpness(const SharpArgs a)
         mine[0] = n_valid, mine[1] = sum1, mine[2] = sum2, mine[3] = sum_l2;
     }
     __syncthreads();
-    if (threadIdx.x < kWords) {
-        unsigned long long t = part[0][threadIdx.x];
-#pragma unroll
-        for (int wv = 1; wv < kWaves; ++wv) t += part[wv][threadIdx.x];
-        row[threadIdx.x] = t;
-    }
+    fold_partials(part, kWords, row);
 }
 
 }  // namespace
@@ -98,19 +66,11 @@ __global__ __launch_bounds__(kThreads) void k_patch_sharpness(const SharpArgs a)
 extern "C" int shg_patch_sharpness_u16(const uint16_t* img, int64_t pitch, int64_t h, int64_t w, const int32_t* points, int64_t n, int B,
                                        int D, const double* circle3, uint64_t* out, shg_stream_t stream) {
     const char* fn = "shg_patch_sharpness_u16";
-    SHG_REQUIRE(img && points && out, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(shg::image_dims_ok(h, w), SHG_E_UNSUPPORTED, "%s: an image of %lld x %lld (1 to %d either way)", fn, (long long)h,
-                (long long)w, shg::kMaxImageDim);
-    SHG_REQUIRE(pitch >= w, SHG_E_ARG, "%s: pitch < w", fn);
-    SHG_REQUIRE(n >= 1 && n <= kMaxPoints, SHG_E_ARG, "%s: %lld points (1 to %lld)", fn, (long long)n, (long long)kMaxPoints);
-    SHG_REQUIRE(B >= 1 && B <= kMaxB, SHG_E_ARG, "%s: a half-size of %d pixels (1 to %d)", fn, B, kMaxB);
+    if (const int e = check_patches(fn, img && points && out, "an image", h, w, pitch, n, B)) return e;
     SHG_REQUIRE(D >= 1 && D <= kMaxD, SHG_E_ARG, "%s: an arm of %d pixels (1 to %d)", fn, D, kMaxD);
     SharpArgs a{};
     if (const int e = shg::parse_disk_mask(fn, circle3, &a.masked, &a.cx, &a.cy, &a.rad2)) return e;
-    const shg::Span out_span = shg::span_of(out, 1, n * kWords, n * kWords, sizeof(uint64_t));
-    SHG_REQUIRE(!shg::overlap(out_span, shg::span_of(img, h, w, pitch, sizeof(uint16_t))) &&
-                    !shg::overlap(out_span, shg::span_of(points, 1, 2 * n, 2 * n, sizeof(int32_t))),
-                SHG_E_ARG, "%s: the output overlaps an input", fn);
+    if (const int e = check_output(fn, out, kWords, points, n, h, w, img, pitch)) return e;
     a.img = img, a.pitch = pitch, a.h = (int)h, a.w = (int)w, a.B = B, a.D = D;
     a.points = points, a.out = reinterpret_cast<unsigned long long*>(out);
     hipStream_t st = shg::as_stream(stream);

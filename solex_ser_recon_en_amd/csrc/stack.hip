@@ -27,6 +27,7 @@
 // skips the sample; the CAP weights sit in a second private array beside the samples, indexed by compile-time constants only, so
 // they too live in registers (past 256 the compiler takes accumulation registers: still no scratch).  The clipping passes do not
 // see the weights; the last step is a weighted in-order mean of the kept samples.  Without the switch none of this is compiled.
+// On the host the three entry points are one function, combine(): one set of checks, one ladder over capacity and mode.
 //
 // SSD: a workgroup walks 64 x 16 tiles; it holds the tile of img with a border of S pixels in LDS and its own four pixels of ref
 // in registers, and for each of the (2 S + 1)^2 offsets sums the squared differences of its pixels (a term is below 2^32, the sum
@@ -324,43 +325,35 @@ __global__ __launch_bounds__(kThreads) void k_stack_combine_weighted(const Combi
     combine_octet<CAP, MODE, true, true>(a, &f, &w);
 }
 
+// The one ladder over mode and capacity behind the three entry points.  f: the fields, null for the plain combine; w: the weight
+// lattices (with f), null for none -- and never with the median: that combination is not instantiated.
 template <int CAP, int MODE>
-int launch_mode(dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs* f) {
+int launch_kernel(dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs* f, const WeightArgs* w) {
     if (!f) return shg::launch(k_stack_combine<CAP, MODE>, grid, dim3(kThreads), 0, st, a, "k_stack_combine");
-    hipLaunchKernelGGL((k_stack_combine_field<CAP, MODE>), grid, dim3(kThreads), 0, st, a, *f);
-    return shg::check_launch("k_stack_combine_field");
+    if (!w) {
+        hipLaunchKernelGGL((k_stack_combine_field<CAP, MODE>), grid, dim3(kThreads), 0, st, a, *f);
+        return shg::check_launch("k_stack_combine_field");
+    }
+    if constexpr (MODE != SHG_STACK_MEDIAN) {
+        hipLaunchKernelGGL((k_stack_combine_weighted<CAP, MODE>), grid, dim3(kThreads), 0, st, a, *f, *w);
+        return shg::check_launch("k_stack_combine_weighted");
+    }
+    return SHG_E_ARG;                                                    // (the entry point has refused it)
 }
 
 template <int CAP>
-int launch_capacity(int mode, dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs* f) {
-    if (mode == SHG_STACK_MEAN) return launch_mode<CAP, SHG_STACK_MEAN>(grid, st, a, f);
-    if (mode == SHG_STACK_MEDIAN) return launch_mode<CAP, SHG_STACK_MEDIAN>(grid, st, a, f);
-    return launch_mode<CAP, SHG_STACK_SIGMA>(grid, st, a, f);
+int launch_modes(int mode, dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs* f, const WeightArgs* w) {
+    if (mode == SHG_STACK_MEAN) return launch_kernel<CAP, SHG_STACK_MEAN>(grid, st, a, f, w);
+    if (mode == SHG_STACK_MEDIAN) return launch_kernel<CAP, SHG_STACK_MEDIAN>(grid, st, a, f, w);
+    return launch_kernel<CAP, SHG_STACK_SIGMA>(grid, st, a, f, w);
 }
 
-// f: the fields, or null for the plain combine
-int launch_combine(int mode, hipStream_t st, const CombineArgs& a, const FieldArgs* f) {
+int launch_combine(int mode, hipStream_t st, const CombineArgs& a, const FieldArgs* f, const WeightArgs* w) {
     const dim3 grid((unsigned)((a.ow + kLanesX * kOct - 1) / (kLanesX * kOct)), (unsigned)((a.oh + kRows - 1) / kRows));
-    if (a.n <= 4) return launch_capacity<4>(mode, grid, st, a, f);
-    if (a.n <= 8) return launch_capacity<8>(mode, grid, st, a, f);
-    if (a.n <= 16) return launch_capacity<16>(mode, grid, st, a, f);
-    return launch_capacity<32>(mode, grid, st, a, f);
-}
-
-template <int CAP>
-int launch_weighted_capacity(int mode, dim3 grid, hipStream_t st, const CombineArgs& a, const FieldArgs& f, const WeightArgs& w) {
-    if (mode == SHG_STACK_MEAN) hipLaunchKernelGGL((k_stack_combine_weighted<CAP, SHG_STACK_MEAN>), grid, dim3(kThreads), 0, st, a, f, w);
-    else hipLaunchKernelGGL((k_stack_combine_weighted<CAP, SHG_STACK_SIGMA>), grid, dim3(kThreads), 0, st, a, f, w);
-    return shg::check_launch("k_stack_combine_weighted");
-}
-
-// mode: SHG_STACK_MEAN or SHG_STACK_SIGMA
-int launch_weighted(int mode, hipStream_t st, const CombineArgs& a, const FieldArgs& f, const WeightArgs& w) {
-    const dim3 grid((unsigned)((a.ow + kLanesX * kOct - 1) / (kLanesX * kOct)), (unsigned)((a.oh + kRows - 1) / kRows));
-    if (a.n <= 4) return launch_weighted_capacity<4>(mode, grid, st, a, f, w);
-    if (a.n <= 8) return launch_weighted_capacity<8>(mode, grid, st, a, f, w);
-    if (a.n <= 16) return launch_weighted_capacity<16>(mode, grid, st, a, f, w);
-    return launch_weighted_capacity<32>(mode, grid, st, a, f, w);
+    if (a.n <= 4) return launch_modes<4>(mode, grid, st, a, f, w);
+    if (a.n <= 8) return launch_modes<8>(mode, grid, st, a, f, w);
+    if (a.n <= 16) return launch_modes<16>(mode, grid, st, a, f, w);
+    return launch_modes<32>(mode, grid, st, a, f, w);
 }
 
 using shg::overlap;
@@ -442,10 +435,16 @@ __global__ __launch_bounds__(kThreads) void k_shift_ssd(const SsdArgs a) {
         if (acc[i]) atomicAdd(a.ssd + i, acc[i]);
 }
 
-// The checks and the argument struct the two combine entry points share.  Nothing is written or launched.
+// The byte spans of the two outputs (count: empty without a count plane, which overlaps nothing).
+struct OutSpans {
+    Span out, count;
+};
+
+// The checks and the argument struct the three combine entry points share, and the outputs' spans for the checks that follow.
+// Nothing is written or launched.
 int combine_args(const char* fn, const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
                  double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count, int64_t count_pitch,
-                 CombineArgs* args) {
+                 CombineArgs* args, OutSpans* spans) {
     SHG_REQUIRE(host_srcs && host_dims3 && host_xform4 && out, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(n >= 1 && n <= kMaxSources, SHG_E_ARG, "%s: %d sources (1 to %d)", fn, n, kMaxSources);
     SHG_REQUIRE(shg::image_dims_ok(oh, ow), SHG_E_UNSUPPORTED, "%s: an output of %lld x %lld (1 to %d either way)", fn, (long long)oh,
@@ -457,7 +456,8 @@ int combine_args(const char* fn, const uint16_t* const* host_srcs, const int64_t
     SHG_REQUIRE(iterations >= 1 && iterations <= 3, SHG_E_ARG, "%s: %d iterations (1 to 3)", fn, iterations);
     const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
     const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
-    SHG_REQUIRE(!count || !overlap(out_span, count_span), SHG_E_ARG, "%s: the count plane overlaps the output", fn);
+    SHG_REQUIRE(!overlap(out_span, count_span), SHG_E_ARG, "%s: the count plane overlaps the output", fn);
+    *spans = OutSpans{out_span, count_span};
     CombineArgs& a = *args;
     for (int j = 0; j < n; ++j) {
         const int64_t h = host_dims3[3 * j], w = host_dims3[3 * j + 1], pitch = host_dims3[3 * j + 2];
@@ -471,7 +471,7 @@ int combine_args(const char* fn, const uint16_t* const* host_srcs, const int64_t
         SHG_REQUIRE(isfinite(gain) && gain >= 0.0, SHG_E_ARG, "%s: source %d: gain %g is negative or not finite", fn, j, gain);
         const Span src_span = span_of(host_srcs[j], h, w, pitch, sizeof(uint16_t));
         SHG_REQUIRE(!overlap(out_span, src_span), SHG_E_ARG, "%s: the output overlaps source %d", fn, j);
-        SHG_REQUIRE(!count || !overlap(count_span, src_span), SHG_E_ARG, "%s: the count plane overlaps source %d", fn, j);
+        SHG_REQUIRE(!overlap(count_span, src_span), SHG_E_ARG, "%s: the count plane overlaps source %d", fn, j);
         a.src[j] = SourceRec{host_srcs[j], (int)h, (int)w, pitch, s, tx, ty, gain};
     }
     a.out = out, a.count = count, a.oh = (int)oh, a.ow = (int)ow, a.out_pitch = out_pitch, a.count_pitch = count ? count_pitch : 0;
@@ -481,30 +481,46 @@ int combine_args(const char* fn, const uint16_t* const* host_srcs, const int64_t
     return 0;
 }
 
-// combine_args, then the lattice and the fields on it (host_fields may be null as a whole: no source has one).
-int lattice_args(const char* fn, const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
-                 const double* const* host_fields, int64_t gh, int64_t gw, int step, int n, int mode, double kappa, int iterations, uint16_t* out,
-                 int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count, int64_t count_pitch, CombineArgs* args, FieldArgs* fields) {
-    SHG_REQUIRE(step >= kMinStep && step <= kMaxStep, SHG_E_ARG, "%s: a lattice step of %d pixels (%d to %d)", fn, step, kMinStep, kMaxStep);
+// The lattice `p` of source j -- `what`: "field" or "weight lattice", `row` doubles a row of nodes -- starts on `align` bytes and
+// overlaps neither output.
+int check_lattice(const char* fn, const char* what, int j, const double* p, int64_t gh, int64_t row, int align, const OutSpans& spans) {
+    SHG_REQUIRE(reinterpret_cast<uintptr_t>(p) % align == 0, SHG_E_ARG, "%s: %s %d does not start on %d bytes", fn, what, j, align);
+    const Span span = span_of(p, gh, row, row, sizeof(double));
+    SHG_REQUIRE(!overlap(spans.out, span), SHG_E_ARG, "%s: the output overlaps %s %d", fn, what, j);
+    SHG_REQUIRE(!overlap(spans.count, span), SHG_E_ARG, "%s: the count plane overlaps %s %d", fn, what, j);
+    return 0;
+}
+
+// What the three entry points do.  lattice: the fields of `step` pixels a node (host_fields may be null as a whole: no source has
+// one) and, with host_weights, the weight lattices; else the plain combine, and gh, gw, step are not read.
+int combine(const char* fn, const char* tag, const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
+            bool lattice, const double* const* host_fields, const double* const* host_weights, int64_t gh, int64_t gw, int step, int n, int mode,
+            double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count, int64_t count_pitch,
+            shg_stream_t stream) {
+    SHG_REQUIRE(!lattice || (step >= kMinStep && step <= kMaxStep), SHG_E_ARG, "%s: a lattice step of %d pixels (%d to %d)", fn, step, kMinStep,
+                kMaxStep);
+    CombineArgs a{};
+    FieldArgs f{};
+    WeightArgs w{};
+    OutSpans spans;
     if (const int e = combine_args(fn, host_srcs, host_dims3, host_xform4, n, mode, kappa, iterations, out, oh, ow, out_pitch, count,
-                                   count_pitch, args))
+                                   count_pitch, &a, &spans))
         return e;
-    SHG_REQUIRE(gh == (oh - 1 + step - 1) / step + 1 && gw == (ow - 1 + step - 1) / step + 1, SHG_E_ARG,
+    SHG_REQUIRE(!lattice || (gh == (oh - 1 + step - 1) / step + 1 && gw == (ow - 1 + step - 1) / step + 1), SHG_E_ARG,
                 "%s: a lattice of %lld x %lld nodes does not cover %lld x %lld pixels at a step of %d", fn, (long long)gh, (long long)gw,
                 (long long)oh, (long long)ow, step);
-    const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
-    const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
-    FieldArgs& f = *fields;
-    for (int j = 0; j < n; ++j) {
-        f.field[j] = host_fields ? host_fields[j] : nullptr;
-        if (!f.field[j]) continue;
-        SHG_REQUIRE(reinterpret_cast<uintptr_t>(f.field[j]) % 16 == 0, SHG_E_ARG, "%s: field %d does not start on 16 bytes", fn, j);
-        const Span field_span = span_of(f.field[j], gh, gw * 2, gw * 2, sizeof(double));
-        SHG_REQUIRE(!overlap(out_span, field_span), SHG_E_ARG, "%s: the output overlaps field %d", fn, j);
-        SHG_REQUIRE(!count || !overlap(count_span, field_span), SHG_E_ARG, "%s: the count plane overlaps field %d", fn, j);
+    for (int j = 0; lattice && host_fields && j < n; ++j) {
+        f.field[j] = host_fields[j];
+        if (const int e = f.field[j] ? check_lattice(fn, "field", j, f.field[j], gh, gw * 2, 16, spans) : 0) return e;
     }
     f.gh = (int)gh, f.gw = (int)gw, f.step = step;
-    return 0;
+    for (int j = 0; host_weights && j < n; ++j) {
+        w.weight[j] = host_weights[j];
+        if (const int e = w.weight[j] ? check_lattice(fn, "weight lattice", j, w.weight[j], gh, gw, 8, spans) : 0) return e;
+    }
+    hipStream_t st = shg::as_stream(stream);
+    SHG_PROF(tag, st);
+    return launch_combine(mode, st, a, lattice ? &f : nullptr, host_weights ? &w : nullptr);
 }
 
 }  // namespace
@@ -512,13 +528,8 @@ int lattice_args(const char* fn, const uint16_t* const* host_srcs, const int64_t
 extern "C" int shg_stack_combine_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4, int n, int mode,
                                      double kappa, int iterations, uint16_t* out, int64_t oh, int64_t ow, int64_t out_pitch, uint8_t* count,
                                      int64_t count_pitch, shg_stream_t stream) {
-    CombineArgs a{};
-    if (const int e = combine_args("shg_stack_combine_u16", host_srcs, host_dims3, host_xform4, n, mode, kappa, iterations, out, oh, ow,
-                                   out_pitch, count, count_pitch, &a))
-        return e;
-    hipStream_t st = shg::as_stream(stream);
-    SHG_PROF("stack_combine", st);
-    return launch_combine(mode, st, a, nullptr);
+    return combine("shg_stack_combine_u16", "stack_combine", host_srcs, host_dims3, host_xform4, false, nullptr, nullptr, 0, 0, 0, n, mode, kappa,
+                   iterations, out, oh, ow, out_pitch, count, count_pitch, stream);
 }
 
 extern "C" int shg_stack_combine_field_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
@@ -527,14 +538,8 @@ extern "C" int shg_stack_combine_field_u16(const uint16_t* const* host_srcs, con
                                            int64_t count_pitch, shg_stream_t stream) {
     const char* fn = "shg_stack_combine_field_u16";
     SHG_REQUIRE(host_fields, SHG_E_ARG, "%s: null pointer", fn);
-    CombineArgs a{};
-    FieldArgs f{};
-    if (const int e = lattice_args(fn, host_srcs, host_dims3, host_xform4, host_fields, gh, gw, step, n, mode, kappa, iterations, out, oh, ow,
-                                   out_pitch, count, count_pitch, &a, &f))
-        return e;
-    hipStream_t st = shg::as_stream(stream);
-    SHG_PROF("stack_combine_field", st);
-    return launch_combine(mode, st, a, &f);
+    return combine(fn, "stack_combine_field", host_srcs, host_dims3, host_xform4, true, host_fields, nullptr, gh, gw, step, n, mode, kappa,
+                   iterations, out, oh, ow, out_pitch, count, count_pitch, stream);
 }
 
 extern "C" int shg_stack_combine_weighted_u16(const uint16_t* const* host_srcs, const int64_t* host_dims3, const double* host_xform4,
@@ -544,34 +549,14 @@ extern "C" int shg_stack_combine_weighted_u16(const uint16_t* const* host_srcs, 
     const char* fn = "shg_stack_combine_weighted_u16";
     SHG_REQUIRE(host_weights, SHG_E_ARG, "%s: null pointer", fn);
     SHG_REQUIRE(mode != SHG_STACK_MEDIAN, SHG_E_ARG, "%s: there is no weighted median", fn);
-    CombineArgs a{};
-    FieldArgs f{};
-    WeightArgs w{};
-    if (const int e = lattice_args(fn, host_srcs, host_dims3, host_xform4, host_fields, gh, gw, step, n, mode, kappa, iterations, out, oh, ow,
-                                   out_pitch, count, count_pitch, &a, &f))
-        return e;
-    const Span out_span = span_of(out, oh, ow, out_pitch, sizeof(uint16_t));
-    const Span count_span = count ? span_of(count, oh, ow, count_pitch, 1) : Span{0, 0};
-    for (int j = 0; j < n; ++j) {
-        w.weight[j] = host_weights[j];
-        if (!host_weights[j]) continue;
-        SHG_REQUIRE(reinterpret_cast<uintptr_t>(host_weights[j]) % 8 == 0, SHG_E_ARG, "%s: weight lattice %d does not start on 8 bytes", fn, j);
-        const Span weight_span = span_of(host_weights[j], gh, gw, gw, sizeof(double));
-        SHG_REQUIRE(!overlap(out_span, weight_span), SHG_E_ARG, "%s: the output overlaps weight lattice %d", fn, j);
-        SHG_REQUIRE(!count || !overlap(count_span, weight_span), SHG_E_ARG, "%s: the count plane overlaps weight lattice %d", fn, j);
-    }
-    hipStream_t st = shg::as_stream(stream);
-    SHG_PROF("stack_combine_weighted", st);
-    return launch_weighted(mode, st, a, f, w);
+    return combine(fn, "stack_combine_weighted", host_srcs, host_dims3, host_xform4, true, host_fields, host_weights, gh, gw, step, n, mode,
+                   kappa, iterations, out, oh, ow, out_pitch, count, count_pitch, stream);
 }
 
 extern "C" int shg_shift_ssd_u16(const uint16_t* ref, int64_t ref_pitch, const uint16_t* img, int64_t img_pitch, int64_t h, int64_t w, int S,
                                  const double* circle3, uint64_t* ssd, shg_stream_t stream) {
     const char* fn = "shg_shift_ssd_u16";
-    SHG_REQUIRE(ref && img && ssd, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(shg::image_dims_ok(h, w), SHG_E_UNSUPPORTED, "%s: images of %lld x %lld (1 to %d either way)", fn, (long long)h,
-                (long long)w, shg::kMaxImageDim);
-    SHG_REQUIRE(ref_pitch >= w && img_pitch >= w, SHG_E_ARG, "%s: pitch < w", fn);
+    if (const int e = shg::check_images(fn, ref && img && ssd, "images", h, w, ref_pitch < img_pitch ? ref_pitch : img_pitch)) return e;
     SHG_REQUIRE(S >= 0 && S <= kMaxS, SHG_E_ARG, "%s: a search of %d pixels (0 to %d)", fn, S, kMaxS);
     SsdArgs a{};
     if (const int e = shg::parse_disk_mask(fn, circle3, &a.masked, &a.cx, &a.cy, &a.rad2)) return e;

@@ -44,6 +44,26 @@ def _out_like(out, h, w, dtype, device, what='out'):
     return out, ptr, pitch
 
 
+def _int64_out(out, shape, device):
+    """A contiguous int64 output of `shape`: the caller's `out`, or a new one when it is None."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int64, device=device)
+    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int64 [%s] tensor' % ', '.join('%d' % v for v in shape))
+    return out
+
+
+def _points(points, device):
+    """(the points as a contiguous int32 [n, 2] tensor on `device` -- a host array is uploaded --, n)."""
+    if not isinstance(points, torch.Tensor):
+        points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)).to(device)
+    if _dev(points, 'points').dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 2 or not points.is_contiguous():
+        raise ValueError('points must be a contiguous int32 [n, 2] tensor of (row, col)')
+    if points.shape[0] < 1:
+        raise ValueError('at least one point is needed')
+    return points, int(points.shape[0])
+
+
 def _workspace(workspace, need, device):
     """(the tensor, its bytes): the caller's workspace, or a new uint8 one of `need` bytes when it is None."""
     ws = torch.empty(need, dtype=torch.uint8, device=device) if workspace is None else _dev(workspace, 'workspace')
@@ -957,14 +977,11 @@ def map_plane_moments(m, circle=None, prev=None, out=None):
     overwritten).  Used: finite, |v| < 64, inside `circle` (cx, cy, r; None or (-1, -1, -1): no mask) and, with prev = (a, b, g,
     limit), within limit of that plane."""
     ptr, h, w, pitch = _img(m, 'map', torch.float32)
-    c3 = None if circle is None else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    c3 = _circle3_or_none(circle)
     p4 = None if prev is None else np.ascontiguousarray([float(v) for v in prev], dtype=np.float64)
-    if (c3 is not None and c3.size != 3) or (p4 is not None and p4.size != 4):
+    if p4 is not None and p4.size != 4:
         raise ValueError('circle is (cx, cy, r) and prev is (a, b, g, limit)')
-    if out is None:
-        out = torch.empty(10, dtype=torch.int64, device=m.device)
-    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (10,) or not out.is_contiguous():
-        raise ValueError('out must be a contiguous int64 [10] tensor')
+    out = _int64_out(out, (10,), m.device)
     _lib.check(lib.shg_map_plane_moments(ptr, h, w, pitch, _host_ptr(c3), _host_ptr(p4), out.data_ptr(), _stream()),
                'shg_map_plane_moments')
     return out
@@ -1043,31 +1060,73 @@ def ring_flatten_u16(img, circle, gain, out=None):
 STACK_MODES = {'mean': 0, 'median': 1, 'sigma': 2}
 
 
-def stack_combine_u16(images, transforms, shape, mode='sigma', kappa=2.5, iterations=2, out=None, count=None, want_count=True):
-    """shg_stack_combine_u16: the N uint16 images (2-D views, any sizes) resampled into one grid of `shape` = (oh, ow) by their
-    transforms -- N rows (s, tx, ty, gain): the output pixel (r, c) reads source j at (tx + s c, ty + s r), bilinear, times gain --
-    and combined pixel by pixel in one launch; mode 'mean', 'median' or 'sigma' (the kappa-sigma clipped mean, `iterations` passes)
-    -> (out uint16 [oh, ow], count uint8 [oh, ow] or None): the samples that went into each pixel.  out, count: the caller's
-    views."""
+def lattice_shape(shape, step):
+    """(gh, gw) of the lattice of `step` pixels that covers a grid of `shape`: nodes at every multiple of `step`, the last at or past the last pixel."""
+    oh, ow, step = int(shape[0]), int(shape[1]), int(step)
+    return (oh - 1 + step - 1) // step + 1, (ow - 1 + step - 1) // step + 1
+
+
+def _lattices(tensors, who, what, shape):
+    """The node pointers of one optional lattice a source (None: a null pointer), each a contiguous float64 tensor of `shape`."""
+    for t in tensors:
+        if t is not None and (_dev(t, who).dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError('a %s is None or a contiguous float64 [%s] tensor' % (what, ', '.join('%d' % v for v in shape)))
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _stack_combine(fn, images, transforms, fields, weights, step, shape, mode, kappa, iterations, out, count, want_count):
+    """What the three combines share: the checks, the marshalling and the call of the entry point `fn`.  step None: the plain
+    combine, without a lattice; weights None: without weight lattices (with them, fields None is no field for any image)."""
     if mode not in STACK_MODES:
         raise ValueError('mode is one of %s, got %r' % (', '.join(STACK_MODES), mode))
+    if weights is not None and mode == 'median':
+        raise ValueError('there is no weighted median: mode is mean or sigma')
     images = list(images)
     n = len(images)
     xf = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4))
-    if n < 1 or xf.shape[0] != n:
-        raise ValueError('%d images and %d transforms (s, tx, ty, gain)' % (n, xf.shape[0]))
+    given = ['%d images' % n, '%d transforms (s, tx, ty, gain)' % xf.shape[0]]
+    lengths = [n, xf.shape[0]]
+    if step is not None:
+        fields = [None] * n if fields is None and weights is not None else list(fields)
+        given.append('%d fields' % len(fields)), lengths.append(len(fields))
+    if weights is not None:
+        weights = list(weights)
+        given.append('%d weight lattices' % len(weights)), lengths.append(len(weights))
+    if n < 1 or lengths != [n] * len(lengths):
+        raise ValueError(', '.join(given[:-1]) + ' and ' + given[-1])
+    if step is not None and not 8 <= int(step) <= 128:
+        raise ValueError('step must be 8 to 128, got %r' % (step,))
     geo = [_img(t, 'image', torch.uint16) for t in images]
     dev = images[0].device
     oh, ow = int(shape[0]), int(shape[1])
+    lattice = ()
+    if step is not None:
+        gh, gw = lattice_shape((oh, ow), step)
+        fptrs = _lattices(fields, 'field', 'field', (gh, gw, 2))
+        if weights is None:
+            lattice = (fptrs, gh, gw, int(step))
+        else:
+            wptrs = _lattices(weights, 'weights', 'weight lattice', (gh, gw))
+            lattice = (None if all(f is None for f in fields) else fptrs, wptrs, gh, gw, int(step))
     out, optr, opitch = _out_like(out, oh, ow, torch.uint16, dev)
     cptr, cpitch = None, 0
     if count is not None or want_count:
         count, cptr, cpitch = _out_like(count, oh, ow, torch.uint8, dev, 'count')
     ptrs = (ctypes.c_void_p * n)(*[g[0] for g in geo])
     dims = np.ascontiguousarray([[g[1], g[2], g[3]] for g in geo], dtype=np.int64)
-    _lib.check(lib.shg_stack_combine_u16(ptrs, _host_ptr(dims), _host_ptr(xf), n, STACK_MODES[mode], float(kappa), int(iterations), optr,
-                                         oh, ow, opitch, cptr, cpitch, _stream()), 'shg_stack_combine_u16')
+    _lib.check(getattr(lib, fn)(ptrs, _host_ptr(dims), _host_ptr(xf), *lattice, n, STACK_MODES[mode], float(kappa), int(iterations), optr,
+                                oh, ow, opitch, cptr, cpitch, _stream()), fn)
     return out, count
+
+
+def stack_combine_u16(images, transforms, shape, mode='sigma', kappa=2.5, iterations=2, out=None, count=None, want_count=True):
+    """shg_stack_combine_u16: the N uint16 images (2-D views, any sizes) resampled into one grid of `shape` = (oh, ow) by their
+    transforms -- N rows (s, tx, ty, gain): the output pixel (r, c) reads source j at (tx + s c, ty + s r), bilinear, times gain --
+    and combined pixel by pixel in one launch; mode 'mean', 'median' or 'sigma' (the kappa-sigma clipped mean, `iterations` passes)
+    -> (out uint16 [oh, ow], count uint8 [oh, ow] or None): the samples that went into each pixel.  out, count: the caller's
+    views."""
+    return _stack_combine('shg_stack_combine_u16', images, transforms, None, None, None, shape, mode, kappa, iterations, out, count,
+                          want_count)
 
 
 def shift_ssd_u16(ref, img, search, circle=None, out=None):
@@ -1083,11 +1142,7 @@ def shift_ssd_u16(ref, img, search, circle=None, out=None):
     if not 0 <= s <= 8:
         raise ValueError('search must be 0 to 8, got %r' % (search,))
     c3 = _circle3_or_none(circle)
-    words = (2 * s + 1) ** 2 + 1
-    if out is None:
-        out = torch.empty(words, dtype=torch.int64, device=ref.device)
-    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (words,) or not out.is_contiguous():
-        raise ValueError('out must be a contiguous int64 [%d] tensor' % words)
+    out = _int64_out(out, ((2 * s + 1) ** 2 + 1,), ref.device)
     _lib.check(lib.shg_shift_ssd_u16(rptr, rpitch, iptr, ipitch, h, w, s, _host_ptr(c3), out.data_ptr(), _stream()), 'shg_shift_ssd_u16')
     return out
 
@@ -1108,28 +1163,12 @@ def patch_ssd_u16(ref, img, points, half, search, circle=None, out=None):
         raise ValueError('half must be 1 to 32, got %r' % (half,))
     if not 0 <= s <= 8:
         raise ValueError('search must be 0 to 8, got %r' % (search,))
-    if not isinstance(points, torch.Tensor):
-        points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)).to(ref.device)
-    if _dev(points, 'points').dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 2 or not points.is_contiguous():
-        raise ValueError('points must be a contiguous int32 [n, 2] tensor of (row, col)')
-    n = int(points.shape[0])
-    if n < 1:
-        raise ValueError('at least one point is needed')
+    points, n = _points(points, ref.device)
     c3 = _circle3_or_none(circle)
-    words = (2 * s + 1) ** 2 + 3
-    if out is None:
-        out = torch.empty((n, words), dtype=torch.int64, device=ref.device)
-    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (n, words) or not out.is_contiguous():
-        raise ValueError('out must be a contiguous int64 [%d, %d] tensor' % (n, words))
+    out = _int64_out(out, (n, (2 * s + 1) ** 2 + 3), ref.device)
     _lib.check(lib.shg_patch_ssd_u16(rptr, rpitch, iptr, ipitch, h, w, points.data_ptr(), n, b, s, _host_ptr(c3), out.data_ptr(), _stream()),
                'shg_patch_ssd_u16')
     return out
-
-
-def lattice_shape(shape, step):
-    """(gh, gw) of the lattice of `step` pixels that covers a grid of `shape`: (oh - 1 + step - 1) // step + 1, columns alike."""
-    oh, ow, step = int(shape[0]), int(shape[1]), int(step)
-    return (oh - 1 + step - 1) // step + 1, (ow - 1 + step - 1) // step + 1
 
 
 def stack_combine_field_u16(images, transforms, fields, step, shape, mode='sigma', kappa=2.5, iterations=2, out=None, count=None,
@@ -1139,33 +1178,8 @@ def stack_combine_field_u16(images, transforms, fields, step, shape, mode='sigma
     lattice_shape(shape, step); step is 8 to 128.  The output pixel (r, c) reads source j at (tx + s (c + dx), ty + s (r + dy)) with
     (dx, dy) bilinear between the four nodes around it; a displacement that is not finite makes the sample absent; None and a field
     of zeros give stack_combine_u16's result bit for bit -> (out uint16 [oh, ow], count uint8 [oh, ow] or None)."""
-    if mode not in STACK_MODES:
-        raise ValueError('mode is one of %s, got %r' % (', '.join(STACK_MODES), mode))
-    images, fields = list(images), list(fields)
-    n = len(images)
-    xf = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4))
-    if n < 1 or xf.shape[0] != n or len(fields) != n:
-        raise ValueError('%d images, %d transforms (s, tx, ty, gain) and %d fields' % (n, xf.shape[0], len(fields)))
-    if not 8 <= int(step) <= 128:
-        raise ValueError('step must be 8 to 128, got %r' % (step,))
-    geo = [_img(t, 'image', torch.uint16) for t in images]
-    dev = images[0].device
-    oh, ow = int(shape[0]), int(shape[1])
-    gh, gw = lattice_shape((oh, ow), step)
-    for f in fields:
-        if f is not None and (_dev(f, 'field').dtype != torch.float64 or tuple(f.shape) != (gh, gw, 2) or not f.is_contiguous()):
-            raise ValueError('a field is None or a contiguous float64 [%d, %d, 2] tensor' % (gh, gw))
-    out, optr, opitch = _out_like(out, oh, ow, torch.uint16, dev)
-    cptr, cpitch = None, 0
-    if count is not None or want_count:
-        count, cptr, cpitch = _out_like(count, oh, ow, torch.uint8, dev, 'count')
-    ptrs = (ctypes.c_void_p * n)(*[g[0] for g in geo])
-    fptrs = (ctypes.c_void_p * n)(*[None if f is None else f.data_ptr() for f in fields])
-    dims = np.ascontiguousarray([[g[1], g[2], g[3]] for g in geo], dtype=np.int64)
-    _lib.check(lib.shg_stack_combine_field_u16(ptrs, _host_ptr(dims), _host_ptr(xf), fptrs, gh, gw, int(step), n, STACK_MODES[mode],
-                                               float(kappa), int(iterations), optr, oh, ow, opitch, cptr, cpitch, _stream()),
-               'shg_stack_combine_field_u16')
-    return out, count
+    return _stack_combine('shg_stack_combine_field_u16', images, transforms, fields, None, step, shape, mode, kappa, iterations, out,
+                          count, want_count)
 
 
 # ---- ranking scans by sharpness: the sums of a quality figure a patch, and the combine with a weight lattice a source ----
@@ -1181,18 +1195,9 @@ def patch_sharpness_u16(img, points, half, arm, circle=None, out=None):
         raise ValueError('half must be 1 to 32, got %r' % (half,))
     if not 1 <= d <= 8:
         raise ValueError('arm must be 1 to 8, got %r' % (arm,))
-    if not isinstance(points, torch.Tensor):
-        points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)).to(img.device)
-    if _dev(points, 'points').dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 2 or not points.is_contiguous():
-        raise ValueError('points must be a contiguous int32 [n, 2] tensor of (row, col)')
-    n = int(points.shape[0])
-    if n < 1:
-        raise ValueError('at least one point is needed')
+    points, n = _points(points, img.device)
     c3 = _circle3_or_none(circle)
-    if out is None:
-        out = torch.empty((n, 4), dtype=torch.int64, device=img.device)
-    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous():
-        raise ValueError('out must be a contiguous int64 [%d, 4] tensor' % n)
+    out = _int64_out(out, (n, 4), img.device)
     _lib.check(lib.shg_patch_sharpness_u16(ptr, pitch, h, w, points.data_ptr(), n, b, d, _host_ptr(c3), out.data_ptr(), _stream()),
                'shg_patch_sharpness_u16')
     return out
@@ -1207,41 +1212,8 @@ def stack_combine_weighted_u16(images, transforms, fields, weights, step, shape,
     its weight is > 0; mode 'mean' or 'sigma' (the clipping does not see the weights; 'median' is a ValueError); the result is
     sum (w v) / sum w over the kept samples in source order and count the kept samples.  Weights of None or 1 give
     stack_combine_field_u16's result bit for bit -> (out uint16 [oh, ow], count uint8 [oh, ow] or None)."""
-    if mode not in STACK_MODES:
-        raise ValueError('mode is one of %s, got %r' % (', '.join(STACK_MODES), mode))
-    if mode == 'median':
-        raise ValueError('there is no weighted median: mode is mean or sigma')
-    images, weights = list(images), list(weights)
-    n = len(images)
-    fields = [None] * n if fields is None else list(fields)
-    xf = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4))
-    if n < 1 or xf.shape[0] != n or len(fields) != n or len(weights) != n:
-        raise ValueError('%d images, %d transforms (s, tx, ty, gain), %d fields and %d weight lattices' % (n, xf.shape[0], len(fields),
-                                                                                                           len(weights)))
-    if not 8 <= int(step) <= 128:
-        raise ValueError('step must be 8 to 128, got %r' % (step,))
-    geo = [_img(t, 'image', torch.uint16) for t in images]
-    dev = images[0].device
-    oh, ow = int(shape[0]), int(shape[1])
-    gh, gw = lattice_shape((oh, ow), step)
-    for f in fields:
-        if f is not None and (_dev(f, 'field').dtype != torch.float64 or tuple(f.shape) != (gh, gw, 2) or not f.is_contiguous()):
-            raise ValueError('a field is None or a contiguous float64 [%d, %d, 2] tensor' % (gh, gw))
-    for wt in weights:
-        if wt is not None and (_dev(wt, 'weights').dtype != torch.float64 or tuple(wt.shape) != (gh, gw) or not wt.is_contiguous()):
-            raise ValueError('a weight lattice is None or a contiguous float64 [%d, %d] tensor' % (gh, gw))
-    out, optr, opitch = _out_like(out, oh, ow, torch.uint16, dev)
-    cptr, cpitch = None, 0
-    if count is not None or want_count:
-        count, cptr, cpitch = _out_like(count, oh, ow, torch.uint8, dev, 'count')
-    ptrs = (ctypes.c_void_p * n)(*[g[0] for g in geo])
-    fptrs = None if all(f is None for f in fields) else (ctypes.c_void_p * n)(*[None if f is None else f.data_ptr() for f in fields])
-    wptrs = (ctypes.c_void_p * n)(*[None if wt is None else wt.data_ptr() for wt in weights])
-    dims = np.ascontiguousarray([[g[1], g[2], g[3]] for g in geo], dtype=np.int64)
-    _lib.check(lib.shg_stack_combine_weighted_u16(ptrs, _host_ptr(dims), _host_ptr(xf), fptrs, wptrs, gh, gw, int(step), n, STACK_MODES[mode],
-                                                  float(kappa), int(iterations), optr, oh, ow, opitch, cptr, cpitch, _stream()),
-               'shg_stack_combine_weighted_u16')
-    return out, count
+    return _stack_combine('shg_stack_combine_weighted_u16', images, transforms, fields, weights, step, shape, mode, kappa, iterations,
+                          out, count, want_count)
 
 
 # ---- sharpening a disk: the a-trous wavelet layers with gains and gates, and the noise they are gated by ----
@@ -1274,10 +1246,7 @@ def wavelet_noise_u16(img, circle=None, out=None, workspace=None):
     number of pixels (0 and 0 for an empty set).  out: the caller's, overwritten."""
     ptr, h, w, pitch = _img(img, 'img', torch.uint16)
     c3 = _circle3_or_none(circle)
-    if out is None:
-        out = torch.empty(2, dtype=torch.int64, device=img.device)
-    if _dev(out, 'out').dtype != torch.int64 or tuple(out.shape) != (2,) or not out.is_contiguous():
-        raise ValueError('out must be a contiguous int64 [2] tensor')
+    out = _int64_out(out, (2,), img.device)
     ws, ws_bytes = _workspace(workspace, lib.shg_wavelet_workspace_bytes(h, w, 1), img.device)
     _lib.check(lib.shg_wavelet_noise_u16(ptr, h, w, pitch, _host_ptr(c3), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
                'shg_wavelet_noise_u16')

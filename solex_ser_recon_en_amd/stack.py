@@ -90,6 +90,37 @@ def refined_transform(s, tx, ty, fit):
     return tx + s * (np.float64(fit['u']) + np.float64(fit['du'])), ty + s * (np.float64(fit['v']) + np.float64(fit['dv']))
 
 
+def _series(images, circles, reference, records=None, fields=None):
+    """(the images on the device, how many): circles -- and records and fields, where given -- are as many, and the reference is
+    one of them (ValueError else)."""
+    from .device import to_device_u16
+    images = [to_device_u16(t) for t in images]
+    n = len(images)
+    if n < 1 or any(t is not None and len(t) != n for t in (circles, records, fields)):
+        raise ValueError('%d images and %d circles' % (n, len(circles)) if records is None else
+                         '%d images, %d records and %d circles' % (n, len(records), len(circles)))
+    if not 0 <= int(reference) < n:
+        raise ValueError('reference %r outside the %d frames' % (reference, n))
+    return images, n
+
+
+def _check_region(region):
+    if not (math.isfinite(region) and region > 0):
+        raise ValueError('region must be a positive fraction of the radius')
+
+
+def _region_disk(circle, region):
+    """The disk two planes are compared over, or one is measured over: (cx, cy, region rad), one float64 product."""
+    cx, cy, rad = (float(v) for v in circle)
+    return cx, cy, float(np.float64(region) * np.float64(rad))
+
+
+def _resampled_alone(image, row, shape):
+    """One image resampled alone by its row (s, tx, ty, gain) into a grid of `shape`."""
+    from . import ops
+    return ops.stack_combine_u16([image], [row], shape, 'mean', want_count=False)[0]
+
+
 def register_disks(images, circles, reference=0, search=8, region=0.9):
     """One record a frame: {'s', 'tx', 'ty' (the refined transform into the frame), 'gain' (level of the reference / level of the
     frame), 'level', 'offset' (u + du, v + dv), 'ssd_per_pixel', 'pixels', 'rejected'}.  The frame is resampled alone into the
@@ -97,17 +128,10 @@ def register_disks(images, circles, reference=0, search=8, region=0.9):
     pixels, and the first minimum refined by a parabola an axis.  The reference's own record is the identity.  ValueError for a
     level of 0."""
     from . import ops
-    from .device import to_device_u16
-    images = [to_device_u16(t) for t in images]
-    n = len(images)
-    if n < 1 or len(circles) != n:
-        raise ValueError('%d images and %d circles' % (n, len(circles)))
-    if not 0 <= int(reference) < n:
-        raise ValueError('reference %r outside the %d frames' % (reference, n))
+    images, n = _series(images, circles, reference)
     if not 0 <= int(search) <= MAX_SEARCH:
         raise ValueError('search must be 0 to %d pixels, got %r' % (MAX_SEARCH, search))
-    if not (math.isfinite(region) and region > 0):
-        raise ValueError('region must be a positive fraction of the radius')
+    _check_region(region)
     reference, search = int(reference), int(search)
     levels = [disk_level(images[i], circles[i]) for i in range(n)]
     for i, level in enumerate(levels):
@@ -116,7 +140,7 @@ def register_disks(images, circles, reference=0, search=8, region=0.9):
     ref_circle = tuple(float(v) for v in circles[reference])
     ref_img = images[reference]
     shape = tuple(ref_img.shape)
-    disk = (ref_circle[0], ref_circle[1], float(np.float64(region) * np.float64(ref_circle[2])))
+    disk = _region_disk(ref_circle, region)
     records = []
     for i in range(n):
         if i == reference:
@@ -125,7 +149,7 @@ def register_disks(images, circles, reference=0, search=8, region=0.9):
             continue
         s, tx, ty = initial_transform(circles[i], ref_circle)
         gain = np.float64(levels[reference]) / np.float64(levels[i])
-        plane, _ = ops.stack_combine_u16([images[i]], [(s, tx, ty, gain)], shape, 'mean', want_count=False)
+        plane = _resampled_alone(images[i], (s, tx, ty, gain), shape)
         fit = refine_offset(ops.shift_ssd_u16(ref_img, plane, search, disk).cpu().numpy(), search)
         tx2, ty2 = refined_transform(s, tx, ty, fit)
         records.append({'s': float(s), 'tx': float(tx2), 'ty': float(ty2), 'gain': float(gain), 'level': levels[i],
@@ -139,11 +163,16 @@ def register_disks(images, circles, reference=0, search=8, region=0.9):
 LOCAL_DEFAULTS = {'step': 16, 'size': 33, 'search': 4, 'region': 0.9, 'min_contrast': 0.0}
 
 
-def check_local(step, size, search, min_contrast=0.0):
+def _check_patches(step, size, lattice, patches):
+    """The ranges of a lattice's step and its patches' size, in the caller's wording."""
     if not 8 <= int(step) <= 128:
-        raise ValueError('the alignment points\' step must be 8 to 128 pixels, got %r' % (step,))
+        raise ValueError('the %s step must be 8 to 128 pixels, got %r' % (lattice, step))
     if not (3 <= int(size) <= 65 and int(size) % 2 == 1):
-        raise ValueError('the alignment patches\' size must be odd and 3 to 65 pixels, got %r' % (size,))
+        raise ValueError('the %s size must be odd and 3 to 65 pixels, got %r' % (patches, size))
+
+
+def check_local(step, size, search, min_contrast=0.0):
+    _check_patches(step, size, 'alignment points\'', 'alignment patches\'')
     if not 0 <= int(search) <= MAX_SEARCH:
         raise ValueError('the alignment points\' search must be 0 to %d pixels, got %r' % (MAX_SEARCH, search))
     if not min_contrast >= 0:
@@ -152,12 +181,13 @@ def check_local(step, size, search, min_contrast=0.0):
 
 def align_lattice(shape, step):
     """The lattice of alignment points over a grid of `shape`: nodes at (j step, i step), as many as cover the grid -> (gh, gw,
-    points int32 [gh gw, 2] of (row, col) in row-major order): gh = (oh - 1 + step - 1) // step + 1, gw alike.  (The last row or
+    points int32 [gh gw, 2] of (row, col) in row-major order): (gh, gw) = ops.lattice_shape(shape, step).  (The last row or
     column of nodes may lie beyond the grid.)"""
-    oh, ow, step = int(shape[0]), int(shape[1]), int(step)
-    if oh < 1 or ow < 1 or step < 1:
+    from .ops import lattice_shape
+    step = int(step)
+    if int(shape[0]) < 1 or int(shape[1]) < 1 or step < 1:
         raise ValueError('a lattice needs a grid and a step of at least one pixel')
-    gh, gw = (oh - 1 + step - 1) // step + 1, (ow - 1 + step - 1) // step + 1
+    gh, gw = lattice_shape(shape, step)
     points = np.empty((gh, gw, 2), dtype=np.int32)
     points[:, :, 0] = (np.arange(gh, dtype=np.int32) * step)[:, None]
     points[:, :, 1] = (np.arange(gw, dtype=np.int32) * step)[None, :]
@@ -248,21 +278,13 @@ def local_fields(images, records, circles, reference=0, step=16, size=33, search
     filled from their neighbours (fill_field).  The output pixel (r, c) then reads the frame at (tx + s (c + dx), ty + s (r + dy))."""
     import torch
     from . import ops
-    from .device import to_device_u16
-    images = [to_device_u16(t) for t in images]
-    n = len(images)
-    if n < 1 or len(circles) != n or len(records) != n:
-        raise ValueError('%d images, %d records and %d circles' % (n, len(records), len(circles)))
-    if not 0 <= int(reference) < n:
-        raise ValueError('reference %r outside the %d frames' % (reference, n))
+    images, n = _series(images, circles, reference, records)
     check_local(step, size, search, min_contrast)
-    if not (math.isfinite(region) and region > 0):
-        raise ValueError('region must be a positive fraction of the radius')
+    _check_region(region)
     reference, step, search, half = int(reference), int(step), int(search), (int(size) - 1) // 2
-    ref_circle = tuple(float(v) for v in circles[reference])
     ref_img = images[reference]
     shape = tuple(ref_img.shape)
-    disk = (ref_circle[0], ref_circle[1], float(np.float64(region) * np.float64(ref_circle[2])))
+    disk = _region_disk(circles[reference], region)
     gh, gw, points = align_lattice(shape, step)
     points_dev = torch.from_numpy(points).to(ref_img.device)
     fields, stats = [], []
@@ -271,7 +293,7 @@ def local_fields(images, records, circles, reference=0, step=16, size=33, search
         if i == reference or rec['rejected']:
             fields.append(None), stats.append(None)
             continue
-        plane, _ = ops.stack_combine_u16([images[i]], [(rec['s'], rec['tx'], rec['ty'], rec['gain'])], shape, 'mean', want_count=False)
+        plane = _resampled_alone(images[i], (rec['s'], rec['tx'], rec['ty'], rec['gain']), shape)
         table = ops.patch_ssd_u16(ref_img, plane, points_dev, half, search, disk).cpu().numpy()
         raw, measured = measure_field(table, gh, gw, half, search, min_contrast)
         fields.append(torch.from_numpy(fill_field(raw, measured)).to(ref_img.device))
@@ -285,14 +307,10 @@ MAX_WEIGHT = float(2 ** 20)
 
 
 def check_quality(step, size, arm, region=0.9, best=None, min_quality=None, lucky=None, power=0.0):
-    if not 8 <= int(step) <= 128:
-        raise ValueError('the quality lattice\'s step must be 8 to 128 pixels, got %r' % (step,))
-    if not (3 <= int(size) <= 65 and int(size) % 2 == 1):
-        raise ValueError('the quality patches\' size must be odd and 3 to 65 pixels, got %r' % (size,))
+    _check_patches(step, size, 'quality lattice\'s', 'quality patches\'')
     if not 1 <= int(arm) <= 8:
         raise ValueError('the Laplacian\'s arm must be 1 to 8 pixels, got %r' % (arm,))
-    if not (math.isfinite(region) and region > 0):
-        raise ValueError('region must be a positive fraction of the radius')
+    _check_region(region)
     if best is not None and int(best) < 2:
         raise ValueError('best must keep at least two scans, got %r' % (best,))
     if min_quality is not None and not 0 <= min_quality <= 1:
@@ -331,9 +349,8 @@ def disk_quality(image, circle, step=16, size=33, arm=3, region=0.9):
     check_quality(step, size, arm, region)
     image = to_device_u16(image)
     half = (int(size) - 1) // 2
-    cx, cy, rad = (float(v) for v in circle)
     gh, gw, points = align_lattice(tuple(image.shape), int(step))
-    table = ops.patch_sharpness_u16(image, points, half, int(arm), (cx, cy, float(np.float64(region) * np.float64(rad)))).cpu().numpy()
+    table = ops.patch_sharpness_u16(image, points, half, int(arm), _region_disk(circle, region)).cpu().numpy()
     qmap = patch_quality(table, half).reshape(gh, gw)
     figure, nodes = map_figure(qmap)
     return {'map': qmap, 'quality': figure, 'nodes': nodes}
@@ -347,14 +364,8 @@ def local_quality(images, records, circles, reference, fields=None, step=16, siz
     node (fields: local_fields', device or host arrays) or 0 without one, the result clipped to int32 --; the patch is `size`
     source pixels a side, the disk the scan's own (cx_s, cy_s, region rad_s), and the figure patch_quality's."""
     from . import ops
-    from .device import to_device_u16
     check_quality(step, size, arm, region)
-    images = [to_device_u16(t) for t in images]
-    n = len(images)
-    if n < 1 or len(circles) != n or len(records) != n or (fields is not None and len(fields) != n):
-        raise ValueError('%d images, %d records and %d circles' % (n, len(records), len(circles)))
-    if not 0 <= int(reference) < n:
-        raise ValueError('reference %r outside the %d frames' % (reference, n))
+    images, n = _series(images, circles, reference, records, fields)
     half = (int(size) - 1) // 2
     gh, gw, points = align_lattice(tuple(images[int(reference)].shape), int(step))
     r, c = points[:, 0].astype(np.float64), points[:, 1].astype(np.float64)
@@ -372,8 +383,7 @@ def local_quality(images, records, circles, reference, fields=None, step=16, siz
             cc, rr = c + f[:, 0], r + f[:, 1]
         src = np.stack([np.rint(ty + s * rr), np.rint(tx + s * cc)], axis=1)
         src = np.clip(src, -2.0 ** 31, 2.0 ** 31 - 1.0).astype(np.int32)
-        cx, cy, rad = (float(v) for v in circles[i])
-        table = ops.patch_sharpness_u16(images[i], src, half, int(arm), (cx, cy, float(np.float64(region) * np.float64(rad)))).cpu().numpy()
+        table = ops.patch_sharpness_u16(images[i], src, half, int(arm), _region_disk(circles[i], region)).cpu().numpy()
         maps.append(patch_quality(table, half).reshape(gh, gw))
     return maps
 

@@ -49,18 +49,25 @@ def lattice_shape(shape, step):
     return (oh - 1 + step - 1) // step + 1, (ow - 1 + step - 1) // step + 1
 
 
-def displacement(field, shape, step):
-    """(dx, dy) float64 [oh, ow] of a field [gh, gw, 2] at every pixel: j = r // step, j1 = min(j + 1, gh - 1), fy = (r - j step) /
-    step, columns alike; per component top = a + (b - a) fx, bot = c + (d - c) fx, top + (bot - top) fy."""
-    field = np.asarray(field, dtype=np.float64)
+def _cells(shape, step):
+    """(gh, gw, j, j1, i, i1, fx, fy) of every pixel's cell: j = r // step, j1 = min(j + 1, gh - 1), fy = (r - j step) / step as a
+    column, i, i1 and fx alike as a row."""
     oh, ow = shape
     gh, gw = lattice_shape(shape, step)
-    assert field.shape == (gh, gw, 2)
     r, c = np.arange(oh, dtype=np.int64), np.arange(ow, dtype=np.int64)
     j, i = r // step, c // step
     j1, i1 = np.minimum(j + 1, gh - 1), np.minimum(i + 1, gw - 1)
     fy = ((r - j * step).astype(np.float64) / np.float64(step))[:, None]
     fx = ((c - i * step).astype(np.float64) / np.float64(step))[None, :]
+    return gh, gw, j, j1, i, i1, fx, fy
+
+
+def displacement(field, shape, step):
+    """(dx, dy) float64 [oh, ow] of a field [gh, gw, 2] at every pixel: j = r // step, j1 = min(j + 1, gh - 1), fy = (r - j step) /
+    step, columns alike; per component top = a + (b - a) fx, bot = c + (d - c) fx, top + (bot - top) fy."""
+    field = np.asarray(field, dtype=np.float64)
+    gh, gw, j, j1, i, i1, fx, fy = _cells(shape, step)
+    assert field.shape == (gh, gw, 2)
     out = []
     with np.errstate(invalid='ignore', over='ignore'):
         for k in (0, 1):

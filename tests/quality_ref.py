@@ -44,14 +44,8 @@ def node_weight(lattice, shape, step):
     """w float64 [oh, ow] of a lattice [gh, gw] at every pixel: the cell of align_ref.displacement, top = a + (b - a) fx,
     bot = c + (d - c) fx, top + (bot - top) fy."""
     lattice = np.asarray(lattice, dtype=np.float64)
-    oh, ow = shape
-    gh, gw = ar.lattice_shape(shape, step)
+    gh, gw, j, j1, i, i1, fx, fy = ar._cells(shape, step)
     assert lattice.shape == (gh, gw)
-    r, c = np.arange(oh, dtype=np.int64), np.arange(ow, dtype=np.int64)
-    j, i = r // step, c // step
-    j1, i1 = np.minimum(j + 1, gh - 1), np.minimum(i + 1, gw - 1)
-    fy = ((r - j * step).astype(np.float64) / np.float64(step))[:, None]
-    fx = ((c - i * step).astype(np.float64) / np.float64(step))[None, :]
     with np.errstate(invalid='ignore', over='ignore'):
         a, b = lattice[j][:, i], lattice[j][:, i1]
         cc, d = lattice[j1][:, i], lattice[j1][:, i1]

@@ -6,6 +6,7 @@ combine: null and all-zero fields against shg_stack_combine_u16 itself, every ca
 on grids that exercise both store paths, the clamp of the last lattice row and steps that do not divide the size, samples pushed off
 a source, a NaN node, odd pitches, the refusals.  End to end: local_fields, stack_disks and stack_scans on the synthetic series and
 on three scans against the restatement, and the command line with and without --local."""
+import functools
 import math
 import shutil
 
@@ -14,51 +15,15 @@ import pytest
 
 from tests import align_ref as ar
 from tests import stack_ref as sr
+from tests import stack_util as su
 from tests.linemaps_util import run_json, write_scan
+from tests.stack_util import (E_ARG, E_UNSUPPORTED, GRIDS, LAYOUTS, MODES, PAD, SPECIAL, SSD_FILL, H, W, bits, combine, down16, mods,  # noqa: F401
+                              planted_table, random_fields, random_sources, same_fields, same_records, skewed, up16)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
-E_ARG, E_UNSUPPORTED = -1, -3
-PAD, OUT_FILL, COUNT_FILL, SSD_FILL = 0xBEEF, 0x5A5A, 0xA5, 0x7EADBEEF7EADBEEF
-GUARD = 3                                   # planted words behind the tables
-MODES = ('mean', 'median', 'sigma')
-
-
-@pytest.fixture(scope='module')
-def mods():
-    if not torch.cuda.is_available():
-        pytest.skip('no GPU')
-    from solex_ser_recon_en_amd import ops, stack
-    from solex_ser_recon_en_amd._lib import lib
-    return stack, ops, lib
-
-
-def up16(a):
-    return torch.from_numpy(np.array(a, dtype=np.uint16).view(np.int16)).cuda().view(torch.uint16)
-
-
-def down16(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def skewed(img, extra, skew=1, fill=PAD):
-    """img in a device buffer of pitch w + extra that starts `skew` elements into its allocation, everything else `fill` ->
-    (the allocation, the image's address)."""
-    h, w = img.shape
-    buf = np.full(skew + h * (w + extra), fill, np.uint16)
-    buf[skew:].reshape(h, w + extra)[:, :w] = img
-    dev = up16(buf)
-    return dev, dev.data_ptr() + 2 * skew
-
-
-def void_array(values):
-    import ctypes
-    return (ctypes.c_void_p * len(values))(*values)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+check = functools.partial(su.check, ar.stack_combine_field)
 
 
 # ---- patch SSD ----
@@ -72,8 +37,7 @@ def patch_ssd(lib, ref, img, points, half, search, circle='none', extra=(1, 3), 
     n = over.get('n', len(pts))
     words = (2 * search + 1) ** 2 + 3 if 0 <= search <= 8 else 4
     dev_pts = torch.from_numpy(pts).cuda()
-    table = torch.from_numpy(np.full(len(pts) * words + GUARD, SSD_FILL, np.uint64).view(np.int64)).cuda()
-    c3 = None if circle == 'none' else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    table, c3 = planted_table(len(pts) * words), su.circle3(circle)
     st = lib.shg_patch_ssd_u16(over.get('ref_ptr', a_ptr), over.get('ref_pitch', w + extra[0]), over.get('img_ptr', b_ptr),
                                over.get('img_pitch', w + extra[1]), over.get('h', h), over.get('w', w), over.get('points_ptr', dev_pts.data_ptr()), n,
                                half, search, None if c3 is None else c3.ctypes.data, over.get('table', table.data_ptr()), None)
@@ -91,16 +55,8 @@ def check_patch_ssd(lib, ref, img, points, half, search, circle='none'):
     want = ar.patch_ssd(ref, img, points, half, search, None if circle == 'none' else circle)
     st, got, intact = patch_ssd(lib, ref, img, points, half, search, circle)
     assert st == 0 and intact
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, '%d words differ, first at %s: %d vs %d' % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+    su.same(got, want, 'words')
     return want
-
-
-H, W = 70, 90
-SPECIAL = [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1),                       # the corners
-           (0, 45), (35, 0), (H - 1, 44), (34, W - 1),                           # the edges
-           (-1, -1), (-33, 45), (35, W + 32), (H, W), (1000, 1000), (-2 ** 31, 2 ** 31 - 1), (2 ** 31 - 1, -2 ** 31),    # outside
-           (35, 45), (35, 45), (20, 30), (41, 52)]                               # inside, two of them equal
 
 
 @pytest.fixture(scope='module')
@@ -193,72 +149,6 @@ def test_patch_ssd_refusals_leave_the_table_untouched(mods, pair):
 
 
 # ---- field combine ----
-def random_sources(n, shapes, seed, spread=3.0, scale=0.03, gains=(0.8, 1.2)):
-    """n sources, their shapes cycling through `shapes`: a common ramp plus noise and here and there an outlier, with transforms a
-    few pixels and per cent apart."""
-    rng = np.random.default_rng(seed)
-    srcs, xforms = [], []
-    for j in range(n):
-        h, w = shapes[j % len(shapes)]
-        img = 20000.0 + 150.0 * np.arange(w)[None, :] + 90.0 * np.arange(h)[:, None] + rng.normal(0.0, 300.0, (h, w))
-        srcs.append(np.clip(img + (rng.random((h, w)) < 0.03) * 20000.0, 0, 65535).astype(np.uint16))
-        xforms.append((1.0 + rng.uniform(-scale, scale), rng.uniform(-spread, spread), rng.uniform(-spread, spread), rng.uniform(*gains)))
-    return srcs, xforms
-
-
-def random_fields(n, shape, step, seed, size=3.0, none=()):
-    rng = np.random.default_rng(seed)
-    gh, gw = ar.lattice_shape(shape, step)
-    return [None if j in none else rng.uniform(-size, size, (gh, gw, 2)) for j in range(n)]
-
-
-def combine(lib, srcs, xforms, fields, step, shape, mode='mean', kappa=2.5, iterations=2, out_extra=1, count_extra=3, skew=0, plain=False,
-            **over):
-    """shg_stack_combine_field_u16 (plain: shg_stack_combine_u16) on the sources in padded buffers into planted outputs that start
-    `skew` elements into their buffers -> (status, out [oh, ow], count [oh, ow], everything else intact)."""
-    oh, ow = shape
-    n = len(srcs)
-    bufs = [up16(np.pad(s, ((0, 0), (0, 1 + j % 3)), constant_values=PAD)) for j, s in enumerate(srcs)]
-    dims = np.array([(s.shape[0], s.shape[1], s.shape[1] + 1 + j % 3) for j, s in enumerate(srcs)], np.int64)
-    xf = np.ascontiguousarray(xforms, dtype=np.float64)
-    dev_fields = [None if f is None else torch.from_numpy(np.ascontiguousarray(f, dtype=np.float64)).cuda() for f in fields]
-    gh, gw = ar.lattice_shape(shape, step) if 1 <= step else (1, 1)
-    out_pitch, count_pitch = ow + out_extra, ow + count_extra
-    out = up16(np.full(oh * out_pitch + skew + 8, OUT_FILL))
-    cnt = torch.full((oh * count_pitch + skew + 8,), COUNT_FILL, dtype=torch.uint8, device='cuda')
-    ptrs = void_array([b.data_ptr() for b in bufs])
-    tail = (n, sr.MODES.get(mode, mode), kappa, iterations, over.get('out', out.data_ptr() + 2 * skew), oh, ow, out_pitch,
-            over.get('count', cnt.data_ptr() + skew), count_pitch, None)
-    if plain:
-        st = lib.shg_stack_combine_u16(ptrs, dims.ctypes.data, xf.ctypes.data, *tail)
-    else:
-        fptrs = void_array([over.get('field_ptr', {}).get(j, None if f is None else f.data_ptr()) for j, f in enumerate(dev_fields)])
-        st = lib.shg_stack_combine_field_u16(ptrs, dims.ctypes.data, xf.ctypes.data, None if over.get('no_fields') else fptrs,
-                                             over.get('gh', gh), over.get('gw', gw), step, *tail)
-    torch.cuda.synchronize()
-    got, got_c = down16(out), cnt.cpu().numpy()
-    planes = got[skew:skew + oh * out_pitch].reshape(oh, out_pitch), got_c[skew:skew + oh * count_pitch].reshape(oh, count_pitch)
-    intact = (got[:skew] == OUT_FILL).all() and (got_c[:skew] == COUNT_FILL).all()
-    intact = intact and (got[skew + (oh - 1) * out_pitch + ow:] == OUT_FILL).all() and (got_c[skew + (oh - 1) * count_pitch + ow:] == COUNT_FILL).all()
-    intact = intact and (planes[0][:, ow:][:-1] == OUT_FILL).all() and (planes[1][:, ow:][:-1] == COUNT_FILL).all()
-    if st != 0:
-        intact = intact and (got == OUT_FILL).all() and (got_c == COUNT_FILL).all()
-    for f, d in zip(fields, dev_fields):
-        assert f is None or np.array_equal(bits(d.cpu().numpy()), bits(f)), 'a field changed'
-    return st, planes[0][:, :ow].copy(), planes[1][:, :ow].copy(), bool(intact)
-
-
-def check(lib, srcs, xforms, fields, step, shape, mode, kappa=2.5, iterations=2, **how):
-    want, want_count = ar.stack_combine_field(srcs, xforms, fields, step, shape, mode, kappa, iterations)
-    st, got, got_count, intact = combine(lib, srcs, xforms, fields, step, shape, mode, kappa, iterations, **how)
-    assert st == 0 and intact
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, '%d pixels differ, first at %s: %d vs %d' % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
-    bad = np.argwhere(got_count != want_count)
-    assert bad.size == 0, '%d counts differ, first at %s: %d vs %d' % (len(bad), bad[0], got_count[tuple(bad[0])], want_count[tuple(bad[0])])
-    return want, want_count
-
-
 @pytest.mark.parametrize('mode', MODES)
 @pytest.mark.parametrize('n', [3, 5, 9, 17])
 def test_null_and_zero_fields_are_the_plain_combine(mods, mode, n):
@@ -268,14 +158,11 @@ def test_null_and_zero_fields_are_the_plain_combine(mods, mode, n):
     shape = (70, 67)
     zero = np.zeros(ar.lattice_shape(shape, 16) + (2,))
     for how in (dict(out_extra=5, count_extra=5), dict(out_extra=2, count_extra=1, skew=1)):
-        st, want, want_count, intact = combine(lib, srcs, xforms, [None] * n, 16, shape, mode, 1.3, 2, plain=True, **how)
+        st, want, want_count, intact = combine(lib, srcs, xforms, shape, [None] * n, None, 16, mode, 1.3, 2, plain=True, **how)
         assert st == 0 and intact and want_count.max() > 1
         for fields in ([None] * n, [zero] * n, [zero if j % 2 else None for j in range(n)], [-zero] * n):
-            st, got, got_count, intact = combine(lib, srcs, xforms, fields, 16, shape, mode, 1.3, 2, **how)
+            st, got, got_count, intact = combine(lib, srcs, xforms, shape, fields, None, 16, mode, 1.3, 2, **how)
             assert st == 0 and intact and np.array_equal(got, want) and np.array_equal(got_count, want_count)
-
-
-GRIDS = [((1, 1), 'odd'), ((1, 7), 'odd'), ((9, 8), 'aligned'), ((37, 263), 'odd'), ((64, 256), 'aligned'), ((64, 256), 'skewed')]
 
 
 @pytest.mark.parametrize('step', [8, 16])
@@ -285,11 +172,11 @@ def test_random_fields_match_the_restatement(mods, shape, layout, step):
     and column lie beyond the grid), 64 and 256 are (the last row and column of nodes are the clamp's: j1 = gh - 1 is never read with
     a weight); aligned: rows on 16 bytes, the 16-byte stores; the others by element.  A mix of null and non-null fields."""
     _, _, lib = mods
-    how = {'aligned': dict(out_extra=0, count_extra=0), 'odd': dict(out_extra=1, count_extra=3), 'skewed': dict(out_extra=0, count_extra=0, skew=1)}[layout]
+    how = LAYOUTS[layout]
     srcs, xforms = random_sources(5, [(70, 270), (66, 260)], step + shape[1], spread=2.0, scale=0.01)
     fields = random_fields(5, shape, step, 3 * step + shape[0], none=(1, 3))
     for mode in MODES:
-        want, count = check(lib, srcs, xforms, fields, step, shape, mode, 1.2, 2, **how)
+        want, count = check(lib, srcs, xforms, shape, mode, 1.2, 2, fields=fields, step=step, **how)
     if shape[0] > 1:
         plain = sr.stack_combine(srcs, xforms, shape, 'mean')[0]
         assert (ar.stack_combine_field(srcs, xforms, fields, step, shape, 'mean')[0] != plain).mean() > 0.5         # the fields do something
@@ -302,7 +189,7 @@ def test_every_capacity_with_fields(mods, n):
     fields = random_fields(n, (20, 19), 8, n, 2.0, none=(0, n - 2))
     for mode in MODES if n < 32 else ('sigma',):
         for iterations in (1, 3) if mode == 'sigma' else (2,):
-            want, count = check(lib, srcs, xforms, fields, 8, (20, 19), mode, 1.3, iterations)
+            want, count = check(lib, srcs, xforms, (20, 19), mode, 1.3, iterations, fields=fields, step=8)
             assert count.max() <= n
 
 
@@ -315,15 +202,15 @@ def test_a_field_that_pushes_samples_off_a_source_and_a_nan_node(mods):
     assert (gh, gw) == (4, 6)
     push = np.zeros((gh, gw, 2))
     push[:, 3:, 0] = 30.0                                                        # columns from 24 on read 30 px to the right: off the source
-    want, count = check(lib, [img, img], [(1.0, 0.0, 0.0, 1.0)] * 2, [push, None], step, shape, 'mean')
+    want, count = check(lib, [img, img], [(1.0, 0.0, 0.0, 1.0)] * 2, shape, 'mean', fields=[push, None], step=step)
     assert (count[:, :17] == 2).all() and (count[:, 24:] == 1).all() and np.array_equal(want[:, 24:], img[:, 24:])
     assert sorted(set(count[:, 17:24].ravel().tolist())) == [1, 2]               # the ramp between the nodes at 16 and 24 crosses the edge
-    want, count = check(lib, [img], [(1.0, 0.0, 0.0, 1.0)], [push], step, shape, 'sigma')
+    want, count = check(lib, [img], [(1.0, 0.0, 0.0, 1.0)], shape, 'sigma', fields=[push], step=step)
     assert (count[:, 24:] == 0).all() and (want[:, 24:] == 0).all()
     for bad in (np.nan, np.inf, -np.inf):
         field = np.zeros((gh, gw, 2))
         field[1, 2, 1] = bad                                                     # the node at (8, 16): the four cells around it
-        want, count = check(lib, [img, img], [(1.0, 0.0, 0.0, 1.0)] * 2, [field, None], step, shape, 'median', out_extra=0, count_extra=0)
+        want, count = check(lib, [img, img], [(1.0, 0.0, 0.0, 1.0)] * 2, shape, 'median', fields=[field, None], step=step, out_extra=0, count_extra=0)
         # (on row 0 and column 8 the node's weight is 0, yet 0 * inf is no number: the four cells are absent whole)
         assert (count[0:16, 8:24] == 1).all() and (count[16:, :] == 2).all() and (count[:, 24:] == 2).all() and (count[:, :8] == 2).all()
         assert np.array_equal(want, img)
@@ -336,7 +223,7 @@ def test_field_combine_refusals_leave_the_outputs_untouched(mods):
     fields = random_fields(2, shape, 8, 4)
 
     def refused(code, step=8, **over):
-        st, _, _, intact = combine(lib, srcs, xforms, fields, step, shape, 'sigma', over.pop('kappa', 2.5), over.pop('iterations', 2), **over)
+        st, _, _, intact = combine(lib, srcs, xforms, shape, fields, None, step, 'sigma', over.pop('kappa', 2.5), over.pop('iterations', 2), **over)
         assert st == code and intact, (step, over)
 
     for step in (7, 129, 0, -8):
@@ -383,22 +270,6 @@ def test_ops_wrapper(mods):
 
 
 # ---- end to end: the synthetic series ----
-def same_records(got, want):
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        for key in ('s', 'tx', 'ty', 'gain', 'ssd_per_pixel'):
-            assert np.float64(g[key]).view(np.uint64) == np.float64(w[key]).view(np.uint64), (key, g[key], w[key])
-        assert tuple(g['offset']) == tuple(w['offset']) and g['pixels'] == w['pixels'] and g['rejected'] == w['rejected']
-
-
-def same_fields(got, want):
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        assert (g is None) == (w is None)
-        if w is not None:
-            assert g.dtype == torch.float64 and g.is_cuda and np.array_equal(bits(g.cpu().numpy()), bits(w))
-
-
 @pytest.fixture(scope='module')
 def series():
     """The synthetic series, its records and its fields by the restatement: computed once, never written to."""

@@ -1,11 +1,12 @@
 """Ranking scans by sharpness on the GPU: shg_patch_sharpness_u16 and shg_stack_combine_weighted_u16 bit for bit against the restatement
-written from the header (tests/quality_ref.py), in the buffer style of tests/test_align_gpu.py (whose helpers are imported): odd
+written from the header (tests/quality_ref.py), in the buffer style of tests/test_align_gpu.py (the helpers are tests/stack_util.py's): odd
 pitches, skewed base pointers, planted guard words, inputs verified untouched.  Sharpness: the special centres, the smallest and the
 largest patch and arm, circles that cut and that empty, one point and more points than a wave of workgroups, images smaller than
 the Laplacian, the largest sums, a constant image, the wrapper, the refusals.  Weighted combine: every capacity, the grids of both
 store paths, null and non-null fields and lattices mixed, mean and sigma; the three exact properties against the existing kernels
 themselves; NaN, negative and all-zero nodes; the refusals; the wrapper.  End to end: disk_quality, local_quality and stack_disks on
 the quadrant series, stack_scans on three scans with and without `quality`, and the command line."""
+import functools
 import shutil
 
 import numpy as np
@@ -14,24 +15,16 @@ import pytest
 from tests import align_ref as ar
 from tests import quality_ref as qr
 from tests import stack_ref as sr
+from tests import stack_util as su
 from tests.linemaps_util import run_json, write_scan
-from tests.test_align_gpu import (COUNT_FILL, GRIDS, GUARD, OUT_FILL, PAD, SPECIAL, SSD_FILL, H, W, bits, combine, down16, random_fields,
-                                  random_sources, same_fields, same_records, skewed, up16, void_array)
+from tests.stack_util import (E_ARG, E_UNSUPPORTED, GRIDS, LAYOUTS, PAD, SPECIAL, SSD_FILL, H, W, bits, combine, down16, mods,  # noqa: F401
+                              planted_table, random_fields, random_sources, random_weights, same_fields, same_records, skewed, up16)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
-E_ARG, E_UNSUPPORTED = -1, -3
 IDENTITY = (1.0, 0.0, 0.0, 1.0)
-
-
-@pytest.fixture(scope='module')
-def mods():
-    if not torch.cuda.is_available():
-        pytest.skip('no GPU')
-    from solex_ser_recon_en_amd import ops, stack
-    from solex_ser_recon_en_amd._lib import lib
-    return stack, ops, lib
+check_weighted = functools.partial(su.check, qr.stack_combine_weighted)
 
 
 # ---- sharpness ----
@@ -43,8 +36,7 @@ def sharpness(lib, img, points, half, arm, circle='none', extra=3, **over):
     pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)
     n = over.get('n', len(pts))
     dev_pts = torch.from_numpy(pts).cuda()
-    table = torch.from_numpy(np.full(len(pts) * 4 + GUARD, SSD_FILL, np.uint64).view(np.int64)).cuda()
-    c3 = None if circle == 'none' else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    table, c3 = planted_table(len(pts) * 4), su.circle3(circle)
     st = lib.shg_patch_sharpness_u16(over.get('img_ptr', a_ptr), over.get('pitch', w + extra), over.get('h', h), over.get('w', w),
                                      over.get('points_ptr', dev_pts.data_ptr()), n, half, arm, None if c3 is None else c3.ctypes.data,
                                      over.get('table', table.data_ptr()), None)
@@ -61,8 +53,7 @@ def check_sharpness(lib, img, points, half, arm, circle='none'):
     want = qr.patch_sharpness(img, points, half, arm, None if circle == 'none' else circle)
     st, got, intact = sharpness(lib, img, points, half, arm, circle)
     assert st == 0 and intact
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, '%d words differ, first at %s: %d vs %d' % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+    su.same(got, want, 'words')
     return want
 
 
@@ -156,65 +147,6 @@ def test_sharpness_refusals_leave_the_table_untouched(mods, image):
 
 
 # ---- weighted combine ----
-def random_weights(n, shape, step, seed, none=(), top=2.0):
-    rng = np.random.default_rng(seed)
-    gh, gw = ar.lattice_shape(shape, step)
-    return [None if j in none else rng.uniform(0.0, top, (gh, gw)) * (rng.random((gh, gw)) > 0.15) for j in range(n)]
-
-
-def weighted(lib, srcs, xforms, fields, weights, step, shape, mode='mean', kappa=2.5, iterations=2, out_extra=1, count_extra=3, skew=0,
-             **over):
-    """shg_stack_combine_weighted_u16 on the sources in padded buffers into planted outputs that start `skew` elements into their
-    buffers -> (status, out [oh, ow], count [oh, ow], everything else intact); fields and lattices are verified untouched."""
-    oh, ow = shape
-    n = len(srcs)
-    bufs = [up16(np.pad(s, ((0, 0), (0, 1 + j % 3)), constant_values=PAD)) for j, s in enumerate(srcs)]
-    dims = np.array([(s.shape[0], s.shape[1], s.shape[1] + 1 + j % 3) for j, s in enumerate(srcs)], np.int64)
-    xf = np.ascontiguousarray(xforms, dtype=np.float64)
-    dev_fields = None if fields is None else [None if f is None else torch.from_numpy(np.ascontiguousarray(f, dtype=np.float64)).cuda()
-                                              for f in fields]
-    dev_weights = [None if w is None else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).cuda() for w in weights]
-    gh, gw = ar.lattice_shape(shape, step) if 1 <= step else (1, 1)
-    out_pitch, count_pitch = ow + out_extra, ow + count_extra
-    out = up16(np.full(oh * out_pitch + skew + 8, OUT_FILL))
-    cnt = torch.full((oh * count_pitch + skew + 8,), COUNT_FILL, dtype=torch.uint8, device='cuda')
-    ptrs = void_array([b.data_ptr() for b in bufs])
-    fptrs = None if dev_fields is None else void_array([over.get('field_ptr', {}).get(j, None if f is None else f.data_ptr())
-                                                        for j, f in enumerate(dev_fields)])
-    wptrs = void_array([over.get('weight_ptr', {}).get(j, None if w is None else w.data_ptr()) for j, w in enumerate(dev_weights)])
-    st = lib.shg_stack_combine_weighted_u16(ptrs, dims.ctypes.data, xf.ctypes.data, fptrs, None if over.get('no_weights') else wptrs,
-                                            over.get('gh', gh), over.get('gw', gw), step, n, sr.MODES.get(mode, mode), kappa, iterations,
-                                            over.get('out', out.data_ptr() + 2 * skew), oh, ow, out_pitch,
-                                            over.get('count', cnt.data_ptr() + skew), count_pitch, None)
-    torch.cuda.synchronize()
-    got, got_c = down16(out), cnt.cpu().numpy()
-    planes = got[skew:skew + oh * out_pitch].reshape(oh, out_pitch), got_c[skew:skew + oh * count_pitch].reshape(oh, count_pitch)
-    intact = (got[:skew] == OUT_FILL).all() and (got_c[:skew] == COUNT_FILL).all()
-    intact = intact and (got[skew + (oh - 1) * out_pitch + ow:] == OUT_FILL).all() and (got_c[skew + (oh - 1) * count_pitch + ow:] == COUNT_FILL).all()
-    intact = intact and (planes[0][:, ow:][:-1] == OUT_FILL).all() and (planes[1][:, ow:][:-1] == COUNT_FILL).all()
-    if st != 0:
-        intact = intact and (got == OUT_FILL).all() and (got_c == COUNT_FILL).all()
-    for host, dev in list(zip(fields or [], dev_fields or [])) + list(zip(weights, dev_weights)):
-        assert host is None or np.array_equal(bits(dev.cpu().numpy()), bits(host)), 'a field or a lattice changed'
-    for j, (b, s) in enumerate(zip(bufs, srcs)):
-        assert np.array_equal(down16(b)[:, :s.shape[1]], s) and (down16(b)[:, s.shape[1]:] == PAD).all(), 'source %d changed' % j
-    return st, planes[0][:, :ow].copy(), planes[1][:, :ow].copy(), bool(intact)
-
-
-def check_weighted(lib, srcs, xforms, fields, weights, step, shape, mode, kappa=2.5, iterations=2, **how):
-    want, want_count = qr.stack_combine_weighted(srcs, xforms, fields, weights, step, shape, mode, kappa, iterations)
-    st, got, got_count, intact = weighted(lib, srcs, xforms, fields, weights, step, shape, mode, kappa, iterations, **how)
-    assert st == 0 and intact
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, '%d pixels differ, first at %s: %d vs %d' % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
-    bad = np.argwhere(got_count != want_count)
-    assert bad.size == 0, '%d counts differ, first at %s: %d vs %d' % (len(bad), bad[0], got_count[tuple(bad[0])], want_count[tuple(bad[0])])
-    return want, want_count
-
-
-LAYOUTS = {'aligned': dict(out_extra=0, count_extra=0), 'odd': dict(out_extra=1, count_extra=3), 'skewed': dict(out_extra=0, count_extra=0, skew=1)}
-
-
 @pytest.mark.parametrize('step', [8, 16])
 @pytest.mark.parametrize('shape, layout', GRIDS, ids=['%dx%d_%s' % (g[0] + (g[1],)) for g in GRIDS])
 def test_random_weights_match_the_restatement(mods, shape, layout, step):
@@ -226,8 +158,8 @@ def test_random_weights_match_the_restatement(mods, shape, layout, step):
     fields = random_fields(5, shape, step, 3 * step + shape[0], none=(1, 3))
     weights = random_weights(5, shape, step, 5 * step + shape[0], none=(0, 3))
     for mode, kappa, iterations in (('mean', 2.5, 2), ('sigma', 1.2, 1), ('sigma', 1.2, 3)):
-        want, count = check_weighted(lib, srcs, xforms, fields, weights, step, shape, mode, kappa, iterations, **how)
-    check_weighted(lib, srcs, xforms, None, weights, step, shape, 'sigma', 1.2, 2, **how)
+        want, count = check_weighted(lib, srcs, xforms, shape, mode, kappa, iterations, fields=fields, weights=weights, step=step, **how)
+    check_weighted(lib, srcs, xforms, shape, 'sigma', 1.2, 2, fields=None, weights=weights, step=step, **how)
     if shape[0] > 1:
         plain = ar.stack_combine_field(srcs, xforms, fields, step, shape, 'mean')[0]
         assert (qr.stack_combine_weighted(srcs, xforms, fields, weights, step, shape, 'mean')[0] != plain).mean() > 0.5    # the weights do something
@@ -243,28 +175,28 @@ def test_every_capacity_and_the_three_properties_against_the_existing_kernels(mo
     gh, gw = ar.lattice_shape(shape, step)
     ones, zeros = np.ones((gh, gw)), np.zeros((gh, gw))
     for mode, kappa, iterations in (('mean', 2.5, 2), ('sigma', 1.3, 1), ('sigma', 1.3, 3)):
-        want, count = check_weighted(lib, srcs, xforms, fields, weights, step, shape, mode, kappa, iterations)
+        want, count = check_weighted(lib, srcs, xforms, shape, mode, kappa, iterations, fields=fields, weights=weights, step=step)
         assert count.max() <= n
         # (a) null lattices, or ones: shg_stack_combine_field_u16 itself
-        st, field_out, field_count, intact = combine(lib, srcs, xforms, fields, step, shape, mode, kappa, iterations)
+        st, field_out, field_count, intact = combine(lib, srcs, xforms, shape, fields, None, step, mode, kappa, iterations)
         assert st == 0 and intact
         for lattices in ([None] * n, [ones] * n, [ones if j % 2 else None for j in range(n)]):
-            st, got, got_count, intact = weighted(lib, srcs, xforms, fields, lattices, step, shape, mode, kappa, iterations)
+            st, got, got_count, intact = combine(lib, srcs, xforms, shape, fields, lattices, step, mode, kappa, iterations)
             assert st == 0 and intact and np.array_equal(got, field_out) and np.array_equal(got_count, field_count)
         # (b) a lattice of zeros: the field combine (unit weights elsewhere) without that source
         for gone in (0, n // 2, n - 1):
             rest = [j for j in range(n) if j != gone]
-            st, less, less_count, intact = combine(lib, [srcs[j] for j in rest], [xforms[j] for j in rest], [fields[j] for j in rest], step,
-                                                   shape, mode, kappa, iterations)
+            st, less, less_count, intact = combine(lib, [srcs[j] for j in rest], [xforms[j] for j in rest], shape, [fields[j] for j in rest],
+                                                   None, step, mode, kappa, iterations)
             assert st == 0 and intact
             # (the padded buffers' pitches follow the position: the sources are the same images either way)
-            st, got, got_count, intact = weighted(lib, srcs, xforms, fields, [zeros if j == gone else None for j in range(n)], step, shape,
-                                                  mode, kappa, iterations)
+            st, got, got_count, intact = combine(lib, srcs, xforms, shape, fields, [zeros if j == gone else None for j in range(n)], step,
+                                                 mode, kappa, iterations)
             assert st == 0 and intact and np.array_equal(got, less) and np.array_equal(got_count, less_count)
         # (c) a common power of two changes no bit (a null lattice is one of ones)
         for factor in (2.0 ** -3, 2.0 ** 4):
-            st, got, got_count, intact = weighted(lib, srcs, xforms, fields, [factor * (ones if w is None else w) for w in weights], step, shape,
-                                                  mode, kappa, iterations)
+            st, got, got_count, intact = combine(lib, srcs, xforms, shape, fields, [factor * (ones if w is None else w) for w in weights], step,
+                                                 mode, kappa, iterations)
             assert st == 0 and intact and np.array_equal(got, want) and np.array_equal(got_count, count)
 
 
@@ -278,7 +210,7 @@ def test_nan_negative_and_zero_nodes(mods):
         lattice = np.ones((gh, gw))
         lattice[1, 2] = bad                                                      # the node at (8, 16): the four cells around it
         for mode in ('mean', 'sigma'):
-            want, count = check_weighted(lib, [img, img], [IDENTITY] * 2, None, [lattice, None], step, shape, mode, out_extra=0, count_extra=0)
+            want, count = check_weighted(lib, [img, img], [IDENTITY] * 2, shape, mode, fields=None, weights=[lattice, None], step=step, out_extra=0, count_extra=0)
             assert (count[16:, :] == 2).all() and (count[:, 24:] == 2).all() and (count[:, :8] == 2).all()
             # (a NaN, or a weight that is not > 0; on row 0 and column 8 of the cells the node has the share 0, yet 0 * nan and
             # 0 * inf are no numbers; a finite negative node leaves that rim to the other three nodes)
@@ -289,7 +221,7 @@ def test_nan_negative_and_zero_nodes(mods):
     zero = np.ones((gh, gw))
     zero[:, :3] = 0.0
     for mode in ('mean', 'sigma'):
-        want, count = check_weighted(lib, [img, img, img], [IDENTITY] * 3, None, [zero] * 3, step, shape, mode)
+        want, count = check_weighted(lib, [img, img, img], [IDENTITY] * 3, shape, mode, fields=None, weights=[zero] * 3, step=step)
         assert (count[:, :17] == 0).all() and (want[:, :17] == 0).all() and (count[:, 17:] == 3).all() and np.array_equal(want[:, 17:], img[:, 17:])
 
 
@@ -300,7 +232,7 @@ def test_weighted_combine_refusals_leave_the_outputs_untouched(mods):
     fields, weights = random_fields(2, shape, 8, 4), random_weights(2, shape, 8, 6)
 
     def refused(code, step=8, mode='sigma', **over):
-        st, _, _, intact = weighted(lib, srcs, xforms, fields, weights, step, shape, mode, over.pop('kappa', 2.5), over.pop('iterations', 2), **over)
+        st, _, _, intact = combine(lib, srcs, xforms, shape, fields, weights, step, mode, over.pop('kappa', 2.5), over.pop('iterations', 2), **over)
         assert st == code and intact, (step, mode, over)
 
     refused(E_ARG, mode='median')

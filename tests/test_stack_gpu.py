@@ -4,6 +4,7 @@ pixel, one column and one row, several sizes at once, every capacity of the kern
 samples exactly on and a rounding step beyond the last column, pixels no source covers; values whose sum depends on its order, ties,
 saturation, every mode and pass count; the refused arguments; the SSD's window sizes, its empty and one-pixel sets, circles, the
 largest term; register_disks against its restatement; and three scans through stack_scans and the command line."""
+import functools
 import math
 import os
 import shutil
@@ -12,114 +13,15 @@ import numpy as np
 import pytest
 
 from tests import stack_ref as sr
+from tests import stack_util as su
 from tests.linemaps_util import run_json, write_scan
+from tests.stack_util import (COUNT_FILL, E_ARG, E_UNSUPPORTED, MODES, OUT_FILL, PAD, SSD_FILL, combine, down16, mods, padded,  # noqa: F401
+                              planted_table, random_sources, same_records, up16, void_array)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
-E_ARG, E_UNSUPPORTED = -1, -3
-PAD, OUT_FILL, COUNT_FILL, SSD_FILL = 0xBEEF, 0x5A5A, 0xA5, 0x7EADBEEF7EADBEEF
-GUARD = 3                                   # planted elements behind the SSD table
-MODES = ('mean', 'median', 'sigma')
-
-
-@pytest.fixture(scope='module')
-def mods():
-    if not torch.cuda.is_available():
-        pytest.skip('no GPU')
-    from solex_ser_recon_en_amd import ops, stack
-    from solex_ser_recon_en_amd._lib import lib
-    return stack, ops, lib
-
-
-def up16(a):
-    return torch.from_numpy(np.array(a, dtype=np.uint16).view(np.int16)).cuda().view(torch.uint16)
-
-
-def down16(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def padded(img, extra, fill=PAD):
-    """img in a device buffer whose pitch is w + extra, the rest `fill` -> the buffer [h, w + extra]."""
-    h, w = img.shape
-    buf = np.full((h, w + extra), fill, np.uint16)
-    buf[:, :w] = img
-    return up16(buf)
-
-
-def combine(lib, srcs, xforms, shape, mode='mean', kappa=2.5, iterations=2, out_extra=1, count_extra=3, skew=0, want_count=True, **over):
-    """shg_stack_combine_u16 on the sources in padded buffers (pitch w + 1 + j % 3) into planted outputs; skew: the output starts
-    that many elements into its buffer -> (status, out [oh, ow], count [oh, ow] or None, everything else intact)."""
-    oh, ow = shape
-    n = over.pop('n', len(srcs))
-    bufs = [padded(np.asarray(s, np.uint16), 1 + j % 3) for j, s in enumerate(srcs)]
-    ptrs = (ctypes_void_array(32))(*([b.data_ptr() for b in bufs] + [0] * (32 - len(bufs))))
-    dims = np.zeros((32, 3), np.int64)
-    xf = np.zeros((32, 4), np.float64)
-    for j, s in enumerate(srcs):
-        dims[j] = (s.shape[0], s.shape[1], s.shape[1] + 1 + j % 3)
-        xf[j] = xforms[j]
-    for j, row in over.pop('dims', {}).items():
-        dims[j] = row
-    if 'null_src' in over:
-        ptrs[over.pop('null_src')] = None
-    out_pitch, count_pitch = ow + out_extra, ow + count_extra
-    out = up16(np.full(oh * out_pitch + skew + 8, OUT_FILL))
-    cnt = torch.full((oh * count_pitch + skew + 8,), COUNT_FILL, dtype=torch.uint8, device='cuda')
-    st = lib.shg_stack_combine_u16(over.get('srcs_ptr', ptrs), over.get('dims_ptr', dims.ctypes.data), over.get('xf_ptr', xf.ctypes.data), n,
-                                   sr.MODES.get(mode, mode), kappa, iterations, over.get('out', out.data_ptr() + 2 * skew),
-                                   over.get('oh', oh), over.get('ow', ow), over.get('out_pitch', out_pitch),
-                                   over.get('count', cnt.data_ptr() + skew if want_count else None), over.get('count_pitch', count_pitch), None)
-    torch.cuda.synchronize()
-    got = down16(out)
-    got_c = cnt.cpu().numpy()
-    planes = got[skew:skew + oh * out_pitch].reshape(oh, out_pitch), got_c[skew:skew + oh * count_pitch].reshape(oh, count_pitch)
-    intact = (got[:skew] == OUT_FILL).all() and (got_c[:skew] == COUNT_FILL).all()
-    intact = intact and (got[skew + (oh - 1) * out_pitch + ow:] == OUT_FILL).all() and (got_c[skew + (oh - 1) * count_pitch + ow:] == COUNT_FILL).all()
-    intact = intact and (planes[0][:, ow:][:-1] == OUT_FILL).all() and (planes[1][:, ow:][:-1] == COUNT_FILL).all()
-    if st != 0 or not want_count:
-        intact = intact and (got_c == COUNT_FILL).all()
-    if st != 0:
-        intact = intact and (got == OUT_FILL).all()
-    for j, (b, s) in enumerate(zip(bufs, srcs)):
-        back = down16(b)
-        assert np.array_equal(back[:, :s.shape[1]], s) and (back[:, s.shape[1]:] == PAD).all(), 'source %d changed' % j
-    return st, planes[0][:, :ow].copy(), planes[1][:, :ow].copy() if want_count else None, bool(intact)
-
-
-def ctypes_void_array(n):
-    import ctypes
-    return ctypes.c_void_p * n
-
-
-def check(lib, srcs, xforms, shape, mode, kappa=2.5, iterations=2, **how):
-    want, want_count = sr.stack_combine(srcs, xforms, shape, mode, kappa, iterations)
-    st, got, got_count, intact = combine(lib, srcs, xforms, shape, mode, kappa, iterations, **how)
-    assert st == 0 and intact
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, '%d pixels differ, first at %s: %d vs %d' % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
-    if got_count is not None:
-        bad = np.argwhere(got_count != want_count)
-        assert bad.size == 0, '%d counts differ, first at %s: %d vs %d' % (len(bad), bad[0], got_count[tuple(bad[0])], want_count[tuple(bad[0])])
-    return want, want_count
-
-
-def random_sources(n, shapes, seed, spread=3.0, scale=0.03, gains=(0.8, 1.2), smooth=True):
-    """n sources, their shapes cycling through `shapes`, with transforms a few pixels and per cent apart.  smooth: a common ramp plus
-    noise, and here and there an outlier, so that the clipping has something to clip; else white."""
-    rng = np.random.default_rng(seed)
-    srcs, xforms = [], []
-    for j in range(n):
-        h, w = shapes[j % len(shapes)]
-        if smooth:
-            base = 20000.0 + 150.0 * np.arange(w)[None, :] + 90.0 * np.arange(h)[:, None]
-            img = base + rng.normal(0.0, 300.0, (h, w)) + (rng.random((h, w)) < 0.03) * 20000.0
-        else:
-            img = rng.integers(0, 65536, (h, w))
-        srcs.append(np.clip(img, 0, 65535).astype(np.uint16))
-        xforms.append((1.0 + rng.uniform(-scale, scale), rng.uniform(-spread, spread), rng.uniform(-spread, spread), rng.uniform(*gains)))
-    return srcs, xforms
+check = functools.partial(su.check, sr.stack_combine)
 
 
 # ---- combine: shapes and transforms ----
@@ -255,7 +157,7 @@ def test_refused_arguments_leave_the_outputs_untouched(mods):
         xf = list(xforms)
         if xform is not None:
             xf[1] = xform
-        st, _, _, intact = combine(lib, srcs, xf, (18, 20), 'sigma', over.pop('kappa', 2.5), over.pop('iterations', 2), **over)
+        st, _, _, intact = combine(lib, srcs, xf, (18, 20), mode='sigma', kappa=over.pop('kappa', 2.5), iterations=over.pop('iterations', 2), **over)
         assert st == code and intact, (over, xform)
 
     for over in (dict(oh=0), dict(ow=16385), dict(dims={1: (16385, 22, 23)}), dict(dims={0: (20, 0, 23)})):
@@ -265,14 +167,14 @@ def test_refused_arguments_leave_the_outputs_untouched(mods):
                  dict(iterations=0), dict(iterations=4)):
         refused(E_ARG, **over)
     for mode in (3, -1):
-        st, _, _, intact = combine(lib, srcs, xforms, (18, 20), mode)
+        st, _, _, intact = combine(lib, srcs, xforms, (18, 20), mode=mode)
         assert st == E_ARG and intact
     for xform in ((0.0, 0.0, 0.0, 1.0), (-1.0, 0.0, 0.0, 1.0), (nan, 0.0, 0.0, 1.0), (inf, 0.0, 0.0, 1.0), (1.0, nan, 0.0, 1.0),
                   (1.0, 0.0, -inf, 1.0), (1.0, 0.0, 0.0, -1e-300), (1.0, 0.0, 0.0, nan), (1.0, 0.0, 0.0, inf)):
         refused(E_ARG, xform)
     # an output that aliases a source: the source's own buffer, its last element, and the count plane on the source
     buf = padded(srcs[0], 1)
-    ptrs = ctypes_void_array(2)(buf.data_ptr(), buf.data_ptr())
+    ptrs = void_array([buf.data_ptr(), buf.data_ptr()])
     dims = np.array([[20, 22, 23], [20, 22, 23]], np.int64)
     xf = np.array(xforms, np.float64)
     other = up16(np.full(20 * 23, OUT_FILL))
@@ -290,8 +192,7 @@ def ssd(lib, ref, img, search, circle='none', extra=(1, 3), **over):
     h, w = ref.shape
     a, b = padded(ref, extra[0]), padded(img, extra[1])
     words = (2 * search + 1) ** 2 + 1 if 0 <= search <= 8 else 1
-    table = torch.from_numpy(np.full(words + GUARD, SSD_FILL, np.uint64).view(np.int64)).cuda()
-    c3 = None if circle == 'none' else np.ascontiguousarray([float(v) for v in circle], dtype=np.float64)
+    table, c3 = planted_table(words), su.circle3(circle)
     st = lib.shg_shift_ssd_u16(over.get('ref_ptr', a.data_ptr()), over.get('ref_pitch', w + extra[0]), over.get('img_ptr', b.data_ptr()),
                                over.get('img_pitch', w + extra[1]), over.get('h', h), over.get('w', w), search,
                                None if c3 is None else c3.ctypes.data, over.get('table', table.data_ptr()), None)
@@ -306,8 +207,7 @@ def check_ssd(lib, ref, img, search, circle='none'):
     want = sr.shift_ssd(ref, img, search, None if circle == 'none' else circle)
     st, got, intact = ssd(lib, ref, img, search, circle)
     assert st == 0 and intact
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, '%d sums differ, first at %d: %d vs %d' % (bad.size, bad[0], got[bad[0]], want[bad[0]])
+    su.same(got, want, 'sums')
     return want
 
 
@@ -395,14 +295,6 @@ def test_ops_wrappers(mods):
         ops.shift_ssd_u16(ref, views[1], 3)
     with pytest.raises(ValueError):
         ops.shift_ssd_u16(ref, img, 9)
-
-
-def same_records(got, want):
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        for key in ('s', 'tx', 'ty', 'gain', 'ssd_per_pixel'):
-            assert np.float64(g[key]).view(np.uint64) == np.float64(w[key]).view(np.uint64), (key, g[key], w[key])
-        assert tuple(g['offset']) == tuple(w['offset']) and g['pixels'] == w['pixels'] and g['rejected'] == w['rejected']
 
 
 @pytest.fixture(scope='module')
