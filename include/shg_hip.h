@@ -878,6 +878,25 @@ int shg_contrast_products_vec_fits(const uint16_t* frame, int64_t frame_pitch, c
                                    int64_t h, int64_t w, const uint16_t* high_contrast, const uint16_t* protus,
                                    const uint16_t* cc, int64_t dst_pitch);
 
+/* What the contrast stage of shg_stage_process_frames would do with k disks [h][w] (rows `pitch` apart, the CLAHE images rows
+ * `dst_pitch` apart; ptr_bits: the OR of the low four bits of every image pointer, 0 for 16-byte aligned images) at this clip limit
+ * and tile grid: the plan of its first launch (the first 32 disks), as plan_clahe makes it -- the same function, the same
+ * environment knobs, nothing decided differently for being asked.  fused != 0: the images are still to be formed by the histogram
+ * kernel (taken only where the stage batches); want_ranks != 0: np.percentile(frame, 99.9999)'s two order statistics ride on the
+ * LUT kernel (the batched route always asks for them); want_window: 0 / 1, or negative for what the stage asks for at this many
+ * disks.  A pure host function, as shg_warp_rows_wide_fits: no pointer is followed, no GPU touched, the workspace taken as roomy.
+ * out[SHG_PLAN_FIELDS]:
+ *   [0] 1 = all disks through one launch per kernel, 0 = disk by disk (shg_contrast_stats_u16)      [1] disks in that launch
+ *   [2] route: 0 / 1 = 8- / 16-bit atomics, 2 / 3 / 4 = slices with u16 / byte / nibble counters     [3] counter bits (0: atomics)
+ *   [4] clip (pixels a bin; 0 = no clipping)   [5] rows a slice   [6] slices a tile   [7] rows between two clamps (a chunk)
+ *   [8], [9] the frame's ranks as the LUT kernel takes them (0 where none ride along)   [10] 1 = they count from the top
+ *   [11] pixels a lane of the blend   [12] 1 = its lanes dealt in tiles   [13] 1 = a LUT workgroup builds every tile's entries
+ *   [14] 1 = the percentile window is counted   [15] 1 = the histogram kernel forms the images
+ * Returns 0, or the code the launch would fail with (shg_last_error has the text). */
+#define SHG_PLAN_FIELDS 16
+int shg_contrast_plan_query(int64_t k, int64_t h, int64_t w, int64_t pitch, int64_t dst_pitch, int ptr_bits, double clip_limit,
+                            int tiles, int fused, int want_ranks, int want_window, int64_t* out);
+
 /* ---- the limb stage's kernels fused through LDS tiles ------ ellipse_to_circle.py:148-291, 299-302 (csrc/limb_fused.hip)
  * The same arithmetic as shg_downscale_mean_u16 / shg_box_blur_key_f64 / shg_select_keys_u32 / shg_flood_stats_lerp_f64 and
  * shg_canny_masks_f64 / shg_edge_components, bit for bit, in 5 + 3 launches instead of 12 + 11.

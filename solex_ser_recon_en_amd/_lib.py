@@ -157,6 +157,7 @@ SIGNATURES = {
     'shg_contrast_stats_u16': (c_int, [P, c_int64, c_int64, c_int64, c_double, c_int, P, c_int64, P, P, P, P, c_size_t, P]),
     'shg_contrast_products_u16': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
     'shg_contrast_products_vec_fits': (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, P, P, c_int64]),
+    'shg_contrast_plan_query': (c_int, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_double, c_int, c_int, c_int, c_int, PI64]),
     'shg_fill_disc_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_uint16, P, P]),
     'shg_downscale_mean_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, P, P]),
     'shg_box_blur_f64': (c_int, [P, c_int64, c_int64, c_int, P, P, P]),

@@ -2224,6 +2224,46 @@ extern "C" int shg_contrast_stats_u16(const uint16_t* frame, int64_t h, int64_t 
 
 bool shg::contrast_stats_batches(int64_t h, int64_t w, int tiles, double clip_limit) { return batched_route(h, w, tiles, clip_limit, read_tuning()); }
 
+// What contrast_stats_batch (below) and shg_contrast_stats_u16 (above) would hand plan_clahe for these disks, and what it answers:
+// the requests are built as those two build theirs -- the images' pointers reduced to their alignment bits, the workspace roomy.
+extern "C" int shg_contrast_plan_query(int64_t k, int64_t h, int64_t w, int64_t pitch, int64_t dst_pitch, int ptr_bits, double clip_limit,
+                                       int tiles, int fused, int want_ranks, int want_window, int64_t* out) {
+    SHG_REQUIRE(out && k > 0 && h > 0 && w > 0, SHG_E_ARG, "shg_contrast_plan_query: null pointer or empty stack");
+    const Tuning tune = read_tuning();
+    const bool batched = (k > 1 || fused) && batched_route(h, w, tiles, clip_limit, tune);
+    const void* bits = reinterpret_cast<const void*>((uintptr_t)(ptr_bits & 15));
+    Disks d = {};
+    d.src.p[0] = d.dst.p[0] = bits;
+    d.n = batched ? (int)std::min<int64_t>(shg::kMaxBatch, k) : 1;
+    d.fused = batched && fused;
+    if (d.fused) {
+        d.from.raw.p[0] = bits;
+        d.from.raw_pitch = pitch, d.from.ncopy = w;
+    }
+    int64_t ranks_frame[2];
+    double gamma;
+    if (int e = shg_host_percentile_plan(h * w, 99.9999, &ranks_frame[0], &ranks_frame[1], &gamma)) return e;
+    const RanksJob job{{ranks_frame[0], ranks_frame[1]}, nullptr, 5};
+    ClaheRequest r{d, Shape{h, w, pitch, dst_pitch, 2, clip_limit, tiles}, nullptr, SIZE_MAX, nullptr};
+    r.want_chunks = true;
+    r.sel_hist = reinterpret_cast<uint32_t*>((uintptr_t)256);     // (only asked whether there is one)
+    r.sel_stride = (1 + 3) * 256;
+    r.want_window = want_window < 0 ? tune.window_for(d.n) : want_window != 0;
+    if (batched && want_ranks) r.ranks = &job;
+    const Plan p = plan_clahe(r, tune);
+    if (p.err) {
+        shg::set_error("%s", p.msg);
+        return p.err;
+    }
+    const bool slices = is_slices(p.route), top = slices && p.bits != 16 && r.ranks;
+    const int64_t fields[SHG_PLAN_FIELDS] = {batched, d.n, (int64_t)p.route, slices ? p.bits : 0, p.clip, slices ? p.slice_rows : 0, slices ? p.slices : 0,
+                                             slices ? p.chunk_rows : 0, r.ranks && slices ? p.lut_rank[0] : 0, r.ranks && slices ? p.lut_rank[1] : 0, top,
+                                             slices ? p.blend_px : 1, slices && p.blend_tiled != 0, slices && p.lut_all_tiles,
+                                             slices && p.window && p.blend_counts, d.fused};
+    for (int i = 0; i < SHG_PLAN_FIELDS; ++i) out[i] = fields[i];
+    return 0;
+}
+
 // image_process's CLAHE + order statistics for the k disks of a file in one launch per kernel (shg_stage_process_frames; a
 // Doppler stack, Solex_recon.py:105-133).  host_frames / host_cl1: device pointers of k images of one shape; out5: [k][5];
 // workspace: k areas of shg_contrast_stats_workspace_bytes_for(h, w, tiles) bytes.  Shapes that batched_route() refuses, a single

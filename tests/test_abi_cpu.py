@@ -195,6 +195,47 @@ def test_products_route_predicate_truth_table():
         assert fits(**change) == want, change
 
 
+def test_contrast_plan_query_truth_table(monkeypatch):
+    """shg_contrast_plan_query is plan_clahe asked as the contrast stage asks it (csrc/clahe.hip): from two aligned 2000 x 2096 disks
+    at the default clip limit (12 pixels a bin, the 5th and 6th largest: nibble counters, ranks from the top), each row flips one
+    input.  Fields: batched, disks, route (2 u16 / 3 bytes / 4 nibbles / 1 atomics), bits, clip, ..., from_top [10], blend pixels [11],
+    LUT for all tiles [13], window [14], fused [15]."""
+    from solex_ser_recon_en_amd import _lib
+    for name in ('SHG_CLAHE_SAT', 'SHG_CLAHE_SAT_PX', 'SHG_SELECT_WINDOW', 'SHG_CONTRAST_BATCH', 'SHG_INTERP_SHAPE', 'SHG_FUSE_SCALE'):
+        monkeypatch.delenv(name, raising=False)
+    good = dict(k=2, h=2000, w=2096, pitch=2112, dst_pitch=2112, bits=0, clip_limit=0.8, tiles=2, fused=1, ranks=1, window=-1)
+
+    def plan(**change):
+        a = dict(good, **change)
+        out = (ctypes.c_int64 * 16)()
+        err = _lib.lib.shg_contrast_plan_query(a['k'], a['h'], a['w'], a['pitch'], a['dst_pitch'], a['bits'], a['clip_limit'], a['tiles'], a['fused'],
+                                               a['ranks'], a['window'], out)
+        return err, list(out)
+    err, p = plan()
+    assert err == 0 and p[:5] == [1, 2, 4, 4, 12] and p[8:11] == [6, 5, 1] and p[11:] == [4, 1, 0, 0, 1]
+    assert p[6] == -(-1000 // p[5]) and p[7] == 65280 // 1048
+    table = [
+        (dict(k=1), {0: 1, 1: 1, 15: 1}), (dict(k=1, fused=0), {0: 0, 1: 1, 2: 2, 3: 16, 10: 0, 15: 0}),       # one disk: batched only to be made on the way
+        (dict(k=4), {1: 4, 11: 8, 14: 1}), (dict(k=8), {13: 1}), (dict(k=40), {1: 32}),
+        (dict(clip_limit=0.0), {0: 0, 2: 1, 3: 0, 4: 0}), (dict(clip_limit=1.01), {2: 3, 3: 8, 4: 16}), (dict(clip_limit=15.98), {2: 3, 4: 255}),
+        (dict(clip_limit=16.02), {2: 2, 3: 16, 4: 256, 10: 0}), (dict(clip_limit=0.3), {2: 2, 4: 4, 10: 0}),     # the 6th largest is out of reach of clip 4
+        (dict(ranks=0), {2: 2, 3: 16, 8: 0, 9: 0, 10: 0}), (dict(window=1), {14: 1}), (dict(k=4, window=0), {14: 0}),
+        (dict(fused=0), {0: 1, 15: 0}), (dict(bits=8, k=4), {11: 4}), (dict(bits=2), {11: 1, 14: 0}), (dict(pitch=2100, dst_pitch=2100, k=4), {11: 4}),
+        (dict(tiles=4, k=8), {13: 1}), (dict(tiles=5, k=8), {13: 0}),
+    ]
+    for change, want in table:
+        err, p = plan(**change)
+        assert err == 0 and {i: p[i] for i in want} == want, (change, p)
+    monkeypatch.setenv('SHG_CLAHE_SAT', '8')
+    assert plan()[1][2:4] == [3, 8]
+    monkeypatch.setenv('SHG_CLAHE_SAT', '0')
+    assert plan()[1][2:4] == [2, 16]
+    monkeypatch.setenv('SHG_CONTRAST_BATCH', '0')
+    assert plan()[1][:2] == [0, 1]
+    assert plan(tiles=17)[0] != 0 and 'tiles' in _lib.last_error()
+    assert plan(h=0)[0] == -1 and _lib.lib.shg_contrast_plan_query(2, 10, 10, 16, 16, 0, 0.8, 2, 1, 1, -1, None) == -1
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from solex_ser_recon_en_amd import ops

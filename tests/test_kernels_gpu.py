@@ -1580,7 +1580,7 @@ def test_contrast_stage_on_a_tile_grid_that_does_not_divide_the_image(shape, k, 
     kernel counts the border pixels without storing them, and np.percentile(frame, 99.9999)'s order statistics, read off the tile
     histograms, leave them out again (BorderPx) -- with saturated counters only while that can be told, else the stage selects over
     the image (a streak of equal, brightest pixels in the row / column the border mirrors forces that).  Every product must equal
-    what the disk-by-disk route gives (SHG_CONTRAST_BATCH=0: shg_contrast_stats_u16, held against the oracle elsewhere), with u16,
+    what the disk-by-disk route gives (SHG_CONTRAST_BATCH=0: shg_contrast_stats_u16; both held against the oracle in tests/test_contrast_oracle_gpu.py), with u16,
     byte and nibble counters: odd widths, odd heights, both, a crop to an odd width, a small image (clip 1), five disks."""
     if not torch.cuda.is_available():
         pytest.skip('no GPU')
