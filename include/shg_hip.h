@@ -561,6 +561,16 @@ int shg_rl_deconvolve_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pit
                           uint16_t* out, int64_t out_pitch, float* estimate, void* workspace, size_t workspace_bytes,
                           shg_stream_t stream);
 
+/* shg_rl_deconvolve_xy_u16: the same iteration with a tap set an axis -- kx[-Rx .. Rx] (host_taps_x) in the row pass, along the
+ * columns of a row, and ky[-Ry .. Ry] (host_taps_y) in the column pass: B(a) reads t = row pass with kx, then column pass with ky; the
+ * adjoint reverses each set (kx~[i] = kx[-i], ky~[i] = ky[-i]).  Everything else -- the order of the sums, the roundings, steps 1 to 5,
+ * out, estimate, the workspace, the properties (a) to (d) -- is as stated above with k replaced per pass, and every limit on radius and
+ * taps holds for each axis.  By (c) the shorter set is padded with zeros to the longer one's radius.  Equal sets give the bits of
+ * shg_rl_deconvolve_u16.  Codes as there; a null host_taps_y is SHG_E_ARG. */
+int shg_rl_deconvolve_xy_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const float* host_taps_x, int radius_x,
+                             const float* host_taps_y, int radius_y, int iterations, uint16_t* out, int64_t out_pitch, float* estimate,
+                             void* workspace, size_t workspace_bytes, shg_stream_t stream);
+
 /* ---- limb protection for the two filters above: the image split into a disk plane and a sky plane that have no step at the limb, and
  * the filtered planes put back around the untouched limb (not reference stages; tests/limbguard_ref.py restates both calls in NumPy,
  * bit for bit).  Everything is float64, one IEEE operation a step, no contraction; sqrt and / are correctly rounded.
@@ -594,6 +604,31 @@ int shg_limb_split_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch,
 int shg_limb_merge_u16(const uint16_t* img, int64_t pitch, const uint16_t* disk, int64_t disk_pitch, const uint16_t* sky, int64_t sky_pitch,
                        int64_t h, int64_t w, const double* circle3, double margin, double blend, uint16_t* out, int64_t out_pitch,
                        shg_stream_t stream);
+
+/* ---- measuring the blur from the limb: the edge-spread tables of the annulus around the fitted circle, one row a sector (not a
+ * reference stage; tests/psf_ref.py restates the call in NumPy, bit for bit).  Everything is float64, one IEEE operation a step, no
+ * contraction; sqrt and / are correctly rounded.  circle3 (host) = (cx, cy, rad); reach, sub and sectors = S are integers;
+ * bins = 2 * reach * sub.  For the pixel in row r, column c, with dx, dy and d2 as in shg_ring_medians_u16:
+ *   THE BIN.     rho = sqrt(d2);  v = (rho - (rad - (double)reach)) * (double)sub.  The pixel COUNTS iff 0 <= v < (double)bins, and its bin
+ *                is b = floor(v): bin b spans the distances t in [b / sub - reach, (b + 1) / sub - reach) from the circle.
+ *   THE SECTOR.  No transcendental function is evaluated.  ax = |dx|, ay = |dy|; swap = ay > ax; hi = swap ? ay : ax, lo = swap ? ax : ay
+ *                (hi >= rho / sqrt(2) > 0 for a pixel that counts, because reach <= rad - 1);  q = lo / hi, in [0, 1];
+ *                i = the number of k with thresholds[k] <= q, over the n - 1 thresholds, n = S / 8  (host doubles, strictly increasing,
+ *                inside (0, 1); the caller supplies them, tan((k + 1) * pi / (4 n)) for sectors of equal angle);
+ *                o = swap ? 1 : 0, rev = swap;  if dx < 0: o = 3 - o, rev = !rev;  then if dy < 0: o = 7 - o, rev = !rev;
+ *                sector = o * n + (rev ? n - 1 - i : i).
+ *                o is the octant of the angle theta of (dx, dy), counted from the +column axis towards the +row axis -- clockwise on a
+ *                screen whose rows run downwards --, so sector s covers theta in [s, s + 1) * 2 pi / S and its middle is at
+ *                (s + 1/2) * 2 pi / S.  The boundaries: dy = 0 belongs to octants 0 and 3, dx = 0 to octants 1 and 6, |dx| = |dy| to
+ *                octants 0, 3, 4 and 7 (no swap), and q equal to a threshold to the index above it.
+ *   count[s][b] += 1 (uint32), sum[s][b] += img (uint64), sumsq[s][b] += img * img (uint64): exact integers, dense [S][bins] device
+ *   tables that the call clears itself; neither the launch grid, nor the order of an atomic, nor any early-out can change a bit.
+ * 1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG, with nothing written, for a null pointer (thresholds may be NULL when S = 8),
+ * pitch < w, a circle outside the limits of shg_ring_medians_u16, reach outside [1, 64] or above rad - 1, sub outside [1, 8], S not a
+ * multiple of 8 from 8 to 64, a threshold that is not finite, not inside (0, 1) or not above the one before it, and a table that
+ * overlaps the image or another table.  The call allocates nothing, waits for nothing and copies nothing from the device. */
+int shg_limb_profile_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, int reach, int sub, int sectors,
+                         const double* thresholds, uint32_t* count, uint64_t* sum, uint64_t* sumsq, shg_stream_t stream);
 
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every

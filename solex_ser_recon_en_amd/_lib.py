@@ -117,6 +117,8 @@ SIGNATURES = {
     'shg_wavelet_noise_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, c_size_t, P]),
     'shg_rl_workspace_bytes': (c_size_t, [c_int64, c_int64]),
     'shg_rl_deconvolve_u16': (c_int, [P, c_int64, c_int64, c_int64, P, c_int, c_int, P, c_int64, P, P, c_size_t, P]),
+    'shg_rl_deconvolve_xy_u16': (c_int, [P, c_int64, c_int64, c_int64, P, c_int, P, c_int, c_int, P, c_int64, P, P, c_size_t, P]),
+    'shg_limb_profile_u16': (c_int, [P, c_int64, c_int64, c_int64, P, c_int, c_int, c_int, P, P, P, P, P]),
     'shg_limb_split_u16': (c_int, [P, c_int64, c_int64, c_int64, P, c_double, c_double, P, c_int64, P, c_int64, P]),
     'shg_limb_merge_u16': (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int64, c_int64, P, c_double, c_double, P, c_int64, P]),
     'shg_blur_fits_fused': (c_int, [c_int64, c_int]),

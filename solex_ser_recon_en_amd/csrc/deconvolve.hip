@@ -23,6 +23,8 @@
 
 #include <math.h>
 
+#include <type_traits>
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -59,6 +61,17 @@ struct RlArgs {
     float taps[2 * RP + 1];
 };
 
+// shg_rl_deconvolve_xy_u16: taps is the row pass's set, taps_y the column pass's.
+template <int RP>
+struct RlArgsXY : RlArgs<RP> {
+    float taps_y[2 * RP + 1];
+};
+
+template <int RP>
+__device__ __forceinline__ const float (&column_taps(const RlArgs<RP>& a))[2 * RP + 1] { return a.taps; }
+template <int RP>
+__device__ __forceinline__ const float (&column_taps(const RlArgsXY<RP>& a))[2 * RP + 1] { return a.taps_y; }
+
 // R(i, n) of the header.
 __device__ __forceinline__ int reflect(int i, int n) {
     if (i < 0) i = -i;
@@ -83,8 +96,8 @@ __device__ __forceinline__ void slide(const float (&win)[kRun + 2 * RP], const f
     }
 }
 
-template <int RP, int MODE>
-__global__ __launch_bounds__(kThreads) void k_rl_blur(const RlArgs<RP> a) {
+template <int RP, int MODE, class ARGS = RlArgs<RP>>
+__global__ __launch_bounds__(kThreads) void k_rl_blur(const ARGS a) {
     using G = Tile<RP>;
     __shared__ __attribute__((aligned(16))) float A[G::AH * G::AP];
     __shared__ __attribute__((aligned(16))) float T[G::AH * G::TP];
@@ -125,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void k_rl_blur(const RlArgs<RP> a) {
     const int lx = (int)threadIdx.x % kTW, ly = (int)threadIdx.x / kTW, c = tx0 + lx;
 #pragma unroll
     for (int v = 0; v < G::kWin; ++v) win[v] = T[(kRun * ly + v) * G::TP + lx];
-    slide<RP>(win, a.taps, acc);
+    slide<RP>(win, column_taps<RP>(a), acc);
     if (c >= a.w) return;
 #pragma unroll
     for (int o = 0; o < kRun; ++o) {
@@ -159,56 +172,73 @@ size_t workspace_bytes(int64_t h, int64_t w) { return shg::kWorkspaceAlign + 2 *
 struct Call {
     const uint16_t* img;
     int64_t h, w, pitch;
-    const float* taps;
+    const float* taps;                // the row pass's; the column pass's too unless taps_y is given
     int radius, iterations;
     uint16_t* out;
     int64_t out_pitch;
     float* estimate;
     float* planes;                    // e | q
     hipStream_t st;
+    const float* taps_y = nullptr;    // shg_rl_deconvolve_xy_u16
+    int radius_y = 0;
 };
 
+// taps[-radius .. radius] in the middle of dst[-RP .. RP] (the rest stays zero), or reversed about the centre
 template <int RP>
-int run(const Call& c) {
-    RlArgs<RP> fwd{}, adj{};
-    fwd.img = c.img, fwd.pitch = c.pitch, fwd.h = (int)c.h, fwd.w = (int)c.w;
-    fwd.e = c.planes, fwd.q = c.planes + (size_t)c.h * (size_t)c.w;
-    fwd.out = c.out, fwd.out_pitch = c.out_pitch, fwd.estimate = c.estimate;
-    for (int i = 0; i <= 2 * c.radius; ++i) fwd.taps[RP - c.radius + i] = c.taps[i];                // (the rest: zeros)
-    adj = fwd;
-    for (int t = 0; t <= 2 * RP; ++t) adj.taps[t] = fwd.taps[2 * RP - t];
+void place_taps(float (&dst)[2 * RP + 1], const float* taps, int radius, bool reversed) {
+    for (int i = 0; i <= 2 * radius; ++i) dst[reversed ? RP + radius - i : RP - radius + i] = taps[i];
+}
+
+template <int RP, class ARGS>
+int iterate(const Call& c, ARGS& fwd, ARGS& adj) {
     const dim3 tiles((unsigned)((c.w + kTW - 1) / kTW), (unsigned)((c.h + kTH - 1) / kTH));
     for (int n = 0; n < c.iterations; ++n) {
         adj.first = n == 0, adj.last = n == c.iterations - 1;
-        if (const int e = n == 0 ? shg::launch(k_rl_blur<RP, kForwardImg>, tiles, dim3(kThreads), 0, c.st, fwd, "k_rl_blur (forward, from the image)")
-                                 : shg::launch(k_rl_blur<RP, kForward>, tiles, dim3(kThreads), 0, c.st, fwd, "k_rl_blur (forward)"))
+        if (const int e = n == 0 ? shg::launch(k_rl_blur<RP, kForwardImg, ARGS>, tiles, dim3(kThreads), 0, c.st, fwd, "k_rl_blur (forward, from the image)")
+                                 : shg::launch(k_rl_blur<RP, kForward, ARGS>, tiles, dim3(kThreads), 0, c.st, fwd, "k_rl_blur (forward)"))
             return e;
-        if (const int e = shg::launch(k_rl_blur<RP, kAdjoint>, tiles, dim3(kThreads), 0, c.st, adj, "k_rl_blur (adjoint)")) return e;
+        if (const int e = shg::launch(k_rl_blur<RP, kAdjoint, ARGS>, tiles, dim3(kThreads), 0, c.st, adj, "k_rl_blur (adjoint)")) return e;
     }
     return 0;
 }
 
-}  // namespace
+template <int RP, class ARGS>
+int run(const Call& c) {
+    ARGS fwd{}, adj{};
+    fwd.img = c.img, fwd.pitch = c.pitch, fwd.h = (int)c.h, fwd.w = (int)c.w;
+    fwd.e = c.planes, fwd.q = c.planes + (size_t)c.h * (size_t)c.w;
+    fwd.out = c.out, fwd.out_pitch = c.out_pitch, fwd.estimate = c.estimate;
+    adj = fwd;
+    place_taps<RP>(fwd.taps, c.taps, c.radius, false);
+    place_taps<RP>(adj.taps, c.taps, c.radius, true);
+    if constexpr (std::is_same<ARGS, RlArgsXY<RP>>::value) {
+        place_taps<RP>(fwd.taps_y, c.taps_y, c.radius_y, false);
+        place_taps<RP>(adj.taps_y, c.taps_y, c.radius_y, true);
+    }
+    return iterate<RP>(c, fwd, adj);
+}
 
-extern "C" size_t shg_rl_workspace_bytes(int64_t h, int64_t w) { return shg::image_dims_ok(h, w) ? workspace_bytes(h, w) : 0; }
-
-extern "C" int shg_rl_deconvolve_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const float* host_taps, int radius,
-                                     int iterations, uint16_t* out, int64_t out_pitch, float* estimate, void* workspace,
-                                     size_t workspace_bytes_given, shg_stream_t stream) {
-    const char* fn = "shg_rl_deconvolve_u16";
-    if (const int e = shg::check_image(fn, img, h, w, pitch)) return e;
-    SHG_REQUIRE(host_taps && out && workspace, SHG_E_ARG, "%s: null pointer", fn);
-    SHG_REQUIRE(out_pitch >= w, SHG_E_ARG, "%s: output pitch < w", fn);
-    SHG_REQUIRE(radius >= 0 && radius <= kMaxRadius, SHG_E_ARG, "%s: a radius of %d (0 to %d)", fn, radius, kMaxRadius);
-    SHG_REQUIRE(iterations >= 1 && iterations <= kMaxIterations, SHG_E_ARG, "%s: %d iterations (1 to %d)", fn, iterations, kMaxIterations);
+int check_taps(const char* fn, const char* axis, const float* taps, int radius) {
+    SHG_REQUIRE(radius >= 0 && radius <= kMaxRadius, SHG_E_ARG, "%s: a radius of %d%s (0 to %d)", fn, radius, axis, kMaxRadius);
     double sum = 0.0;
     for (int i = 0; i <= 2 * radius; ++i) {
-        const float k = host_taps[i];
-        SHG_REQUIRE(isfinite(k) && (k == 0.0f || (k >= kMinTap && k <= 1.0f)), SHG_E_ARG, "%s: tap %d = %g is neither 0 nor in [2^-30, 1]", fn,
-                    i - radius, (double)k);
+        const float k = taps[i];
+        SHG_REQUIRE(isfinite(k) && (k == 0.0f || (k >= kMinTap && k <= 1.0f)), SHG_E_ARG, "%s: tap %d%s = %g is neither 0 nor in [2^-30, 1]", fn,
+                    i - radius, axis, (double)k);
         sum += (double)k;
     }
-    SHG_REQUIRE(fabs(sum - 1.0) <= kSumSlack, SHG_E_ARG, "%s: the taps sum to %.9g, more than 2^-10 off 1", fn, sum);
+    SHG_REQUIRE(fabs(sum - 1.0) <= kSumSlack, SHG_E_ARG, "%s: the taps%s sum to %.9g, more than 2^-10 off 1", fn, axis, sum);
+    return 0;
+}
+
+// What the two entry points share: every check but the taps', then the launches.  taps_y NULL: one tap set for both passes.
+int deconvolve(const char* fn, const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const float* taps_x, int radius_x,
+               const float* taps_y, int radius_y, int iterations, uint16_t* out, int64_t out_pitch, float* estimate, void* workspace,
+               size_t workspace_bytes_given, shg_stream_t stream) {
+    SHG_REQUIRE(iterations >= 1 && iterations <= kMaxIterations, SHG_E_ARG, "%s: %d iterations (1 to %d)", fn, iterations, kMaxIterations);
+    if (const int e = check_taps(fn, taps_y ? " along x" : "", taps_x, radius_x)) return e;
+    if (taps_y)
+        if (const int e = check_taps(fn, " along y", taps_y, radius_y)) return e;
     const size_t need = workspace_bytes(h, w);
     SHG_REQUIRE(workspace_bytes_given >= need, SHG_E_ARG, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes_given, need);
     const Span img_span = span_of(img, h, w, pitch, sizeof(uint16_t)), out_span = span_of(out, h, w, out_pitch, sizeof(uint16_t));
@@ -224,8 +254,37 @@ extern "C" int shg_rl_deconvolve_u16(const uint16_t* img, int64_t h, int64_t w, 
         SHG_REQUIRE(!overlap(est_span, ws_span), SHG_E_ARG, "%s: the estimate overlaps the workspace", fn);
     }
     hipStream_t st = shg::as_stream(stream);
-    SHG_PROF("rl_deconvolve", st);
-    const Call c{img, h, w, pitch, host_taps, radius, iterations, out, out_pitch, estimate,
-                 reinterpret_cast<float*>(shg::align_up(workspace, shg::kWorkspaceAlign)), st};
-    return radius <= 2 ? run<2>(c) : radius <= 6 ? run<6>(c) : radius <= 10 ? run<10>(c) : run<16>(c);
+    SHG_PROF(taps_y ? "rl_deconvolve_xy" : "rl_deconvolve", st);
+    Call c{img, h, w, pitch, taps_x, radius_x, iterations, out, out_pitch, estimate,
+           reinterpret_cast<float*>(shg::align_up(workspace, shg::kWorkspaceAlign)), st};
+    if (!taps_y) return radius_x <= 2 ? run<2, RlArgs<2>>(c) : radius_x <= 6 ? run<6, RlArgs<6>>(c) : radius_x <= 10 ? run<10, RlArgs<10>>(c) : run<16, RlArgs<16>>(c);
+    c.taps_y = taps_y, c.radius_y = radius_y;
+    const int radius = radius_x > radius_y ? radius_x : radius_y;          // RP from the larger; the shorter set is padded with zeros
+    return radius <= 2 ? run<2, RlArgsXY<2>>(c) : radius <= 6 ? run<6, RlArgsXY<6>>(c) : radius <= 10 ? run<10, RlArgsXY<10>>(c) : run<16, RlArgsXY<16>>(c);
+}
+
+}  // namespace
+
+extern "C" size_t shg_rl_workspace_bytes(int64_t h, int64_t w) { return shg::image_dims_ok(h, w) ? workspace_bytes(h, w) : 0; }
+
+extern "C" int shg_rl_deconvolve_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const float* host_taps, int radius,
+                                     int iterations, uint16_t* out, int64_t out_pitch, float* estimate, void* workspace,
+                                     size_t workspace_bytes_given, shg_stream_t stream) {
+    const char* fn = "shg_rl_deconvolve_u16";
+    if (const int e = shg::check_image(fn, img, h, w, pitch)) return e;
+    SHG_REQUIRE(host_taps && out && workspace, SHG_E_ARG, "%s: null pointer", fn);
+    SHG_REQUIRE(out_pitch >= w, SHG_E_ARG, "%s: output pitch < w", fn);
+    return deconvolve(fn, img, h, w, pitch, host_taps, radius, nullptr, 0, iterations, out, out_pitch, estimate, workspace, workspace_bytes_given,
+                      stream);
+}
+
+extern "C" int shg_rl_deconvolve_xy_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const float* host_taps_x, int radius_x,
+                                        const float* host_taps_y, int radius_y, int iterations, uint16_t* out, int64_t out_pitch,
+                                        float* estimate, void* workspace, size_t workspace_bytes_given, shg_stream_t stream) {
+    const char* fn = "shg_rl_deconvolve_xy_u16";
+    if (const int e = shg::check_image(fn, img, h, w, pitch)) return e;
+    SHG_REQUIRE(host_taps_x && host_taps_y && out && workspace, SHG_E_ARG, "%s: null pointer", fn);
+    SHG_REQUIRE(out_pitch >= w, SHG_E_ARG, "%s: output pitch < w", fn);
+    return deconvolve(fn, img, h, w, pitch, host_taps_x, radius_x, host_taps_y, radius_y, iterations, out, out_pitch, estimate, workspace,
+                      workspace_bytes_given, stream);
 }

@@ -4,7 +4,7 @@ rad - margin continued outwards by a point reflection along every ray, and the s
 way (ops.limb_split_u16) --, runs the unchanged filter on each, and puts the results back around the band of the limb itself, which
 stays as observed (ops.limb_merge_u16).  Both steps are HIP kernels whose arithmetic include/shg_hip.h states exactly.
 
-Out of scope: sharpening the limb itself, an ellipse instead of a circle, measuring the blur from the limb."""
+Out of scope: sharpening the limb itself, an ellipse instead of a circle."""
 import math
 
 DEFAULT_BLEND = 4.0

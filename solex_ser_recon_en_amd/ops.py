@@ -1278,6 +1278,68 @@ def rl_deconvolve_u16(img, taps, iterations, out=None, want_estimate=False, work
     return out, estimate
 
 
+def _rl_taps(taps, axis):
+    k = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    if k.size % 2 != 1 or k.size > 33:
+        raise ValueError('2 R + 1 taps along %s with R from 0 to 16, got %d' % (axis, k.size))
+    if not (np.isfinite(k).all() and ((k == 0) | ((k >= np.float32(2.0 ** -30)) & (k <= 1))).all()):
+        raise ValueError('a tap along %s is 0 or lies in [2^-30, 1]' % axis)
+    if abs(float(k.astype(np.float64).sum()) - 1.0) > 2.0 ** -10:
+        raise ValueError('the taps along %s sum to %r, more than 2^-10 off 1' % (axis, float(k.astype(np.float64).sum())))
+    return k
+
+
+def rl_deconvolve_xy_u16(img, taps_x, taps_y, iterations, out=None, want_estimate=False, workspace=None):
+    """shg_rl_deconvolve_xy_u16: rl_deconvolve_u16 with a tap set an axis -- `taps_x` (2 Rx + 1 float32 values) blurs along the columns
+    of a row, `taps_y` (2 Ry + 1) down the rows of a column; each set under rl_deconvolve_u16's limits -> (out uint16 [h, w], the
+    estimate float32 [h, w] or None).  Equal sets give rl_deconvolve_u16's bits."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    kx, ky = _rl_taps(taps_x, 'x'), _rl_taps(taps_y, 'y')
+    if not (isinstance(iterations, (int, np.integer)) and 1 <= iterations <= 200):
+        raise ValueError('iterations is an integer from 1 to 200, got %r' % (iterations,))
+    out, optr, opitch = _out_like(out, h, w, torch.uint16, img.device)
+    estimate = torch.empty((h, w), dtype=torch.float32, device=img.device) if want_estimate else None
+    ws, ws_bytes = _workspace(workspace, lib.shg_rl_workspace_bytes(h, w), img.device)
+    _lib.check(lib.shg_rl_deconvolve_xy_u16(ptr, h, w, pitch, _host_ptr(kx), kx.size // 2, _host_ptr(ky), ky.size // 2, int(iterations),
+                                            optr, opitch, None if estimate is None else estimate.data_ptr(), ws.data_ptr(), ws_bytes,
+                                            _stream()), 'shg_rl_deconvolve_xy_u16')
+    return out, estimate
+
+
+# ---- measuring the blur from the limb: the edge-spread tables of the annulus around the circle ----
+def sector_thresholds(sectors):
+    """The S / 8 - 1 thresholds of shg_limb_profile_u16 for `sectors` = S sectors of equal angle: tan((k + 1) pi / (4 S / 8)) as host
+    float64 -- computed once here, so that the library and a restatement are handed the same doubles."""
+    if not (isinstance(sectors, (int, np.integer)) and 8 <= sectors <= 64 and sectors % 8 == 0):
+        raise ValueError('sectors is a multiple of 8 from 8 to 64, got %r' % (sectors,))
+    n = int(sectors) // 8
+    return np.tan(np.arange(1, n, dtype=np.float64) * (np.pi / (4.0 * n)))
+
+
+def limb_profile_u16(img, circle, reach, sub, sectors, thresholds=None):
+    """shg_limb_profile_u16: the pixels of the uint16 image within `reach` (1 to 64, at most r - 1) pixels of the limb of `circle`
+    (cx, cy, r), binned by sector (`sectors`: a multiple of 8 from 8 to 64, counted from the +column axis towards the +row axis) and by
+    distance from the centre in bins of 1 / `sub` (1 to 8) pixel -> (count uint32, sum uint64, sumsq uint64), each
+    [sectors, 2 reach sub] on the image's device.  thresholds: sector_thresholds(sectors) unless given."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    c3, _ = _circle3(circle)
+    for name, v, lo, hi in (('reach', reach, 1, 64), ('sub', sub, 1, 8)):
+        if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
+            raise ValueError('%s is an integer from %d to %d, got %r' % (name, lo, hi, v))
+    if not reach <= c3[2] - 1.0:
+        raise ValueError('reach is at most rad - 1 = %r, got %r' % (float(c3[2] - 1.0), reach))
+    t = sector_thresholds(sectors) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    if t.size != sectors // 8 - 1:
+        raise ValueError('%d sectors take %d thresholds, got %d' % (sectors, sectors // 8 - 1, t.size))
+    shape = (int(sectors), 2 * int(reach) * int(sub))
+    count = torch.empty(shape, dtype=torch.uint32, device=img.device)
+    total = torch.empty(shape, dtype=torch.uint64, device=img.device)
+    sumsq = torch.empty(shape, dtype=torch.uint64, device=img.device)
+    _lib.check(lib.shg_limb_profile_u16(ptr, h, w, pitch, _host_ptr(c3), int(reach), int(sub), int(sectors), _host_ptr(t) if t.size else None,
+                                        count.data_ptr(), total.data_ptr(), sumsq.data_ptr(), _stream()), 'shg_limb_profile_u16')
+    return count, total, sumsq
+
+
 # ---- limb protection: the image as a disk plane and a sky plane without the limb's step, and the filtered planes put back ----
 def _limb_ring(circle, margin):
     """(circle as a host float64 [3] array, margin as a float); ValueError unless rad > 0, margin >= 0 and rad - margin >= 1."""
