@@ -630,6 +630,41 @@ int shg_limb_merge_u16(const uint16_t* img, int64_t pitch, const uint16_t* disk,
 int shg_limb_profile_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, int reach, int sub, int sectors,
                          const double* thresholds, uint32_t* count, uint64_t* sum, uint64_t* sumsq, shg_stream_t stream);
 
+/* ---- scan jitter along the slit: the two limb crossings of every column of a raw disk, and every column resampled along itself by
+ * its own shift (not reference stages; tests/dejitter_ref.py restates both calls in NumPy, bit for bit).  Everything on the device is
+ * an integer: the result depends neither on the launch grid, nor on how a column's rows are split, nor on the order of anything.
+ * shg_column_limb_u16: img is a uint16 image of h x w (pitch in elements); K = window, odd, 1 <= K <= 15; T = threshold,
+ * 0 <= T <= 65535.  For column c, as uint32:
+ *   s[i] = sum over k = 0 .. K - 1 of img[i + k][c]   for 0 <= i <= h - K    (below 2^20);      A[i] = (s[i] >= K * T).
+ *   THE TOP CROSSING is the smallest i >= 1 with !A[i - 1] && A[i], provided A[0] is false;
+ *   THE BOTTOM CROSSING is the largest i <= h - K - 1 with A[i] && !A[i + 1], provided A[h - K] is false.
+ *   The column HAS A MEASUREMENT iff h >= K + 2, A[0] and A[h - K] are false and some A[i] is true (both crossings then exist).
+ * out6 (device) = [w][6] int32: (i_top, s[i_top - 1], s[i_top], i_bot, s[i_bot], s[i_bot + 1]) for a column with a measurement, -1 in
+ * all six otherwise.  Every word is written once, by a plain store: the call needs no clearing pass and accumulates nothing across
+ * workgroups.  The sub-pixel crossings are the caller's, in float64, one IEEE operation a step:
+ *   top = ((double)(i_top - 1) + (double)(K * T - s[i_top - 1]) / (double)(s[i_top] - s[i_top - 1])) + (double)(K - 1) / 2.0;
+ *   bot = ((double)i_bot + (double)(s[i_bot] - K * T) / (double)(s[i_bot] - s[i_bot + 1])) + (double)(K - 1) / 2.0;
+ * both denominators are > 0 by construction.  SHG_E_ARG for an even window or one outside [1, 15], a threshold outside [0, 65535]
+ * and a table that overlaps the image.
+ * shg_column_shift_u16: img is n planes (1 <= n <= 64) of h x w uint16, rows `pitch` and planes `plane_stride` elements apart; out
+ * likewise with out_pitch and out_plane_stride.  host_offset (host) = [w] int32, |offset| <= 16384; host_weight4 (host) = [w][4]
+ * int32 in Q14, each in [-4096, 20480], the four of a column summing to 16384.  For plane p, row r, column c, as int64:
+ *   acc = sum over k = 0 .. 3 of weight[c][k] * img[p][clamp(r + offset[c] + k - 1, 0, h - 1)][c]      (|acc| < 2^31);
+ *   out[p][r][c] = (uint16)clip((acc + 8192) >> 14, 0, 65535)            (the shift is arithmetic: a floor towards -infinity).
+ *   A column with offset 0 and weights (0, 16384, 0, 0) leaves as it came, bit for bit.
+ * The per-column arrays travel to the device by value, in the arguments of the launches (256 columns a launch, every launch for all
+ * planes): they are read before the call returns and may be reused at once.  SHG_E_ARG for n outside [1, 64], an offset or a weight
+ * out of range, weights of a column that do not sum to 16384, with n > 1 a plane stride below (h - 1) * pitch + w, a plane stride
+ * outside [0, 2^40], and an out that overlaps img (a resampling cannot run in place).
+ * Both calls: 1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG for a null pointer and a pitch below the width.  On any error
+ * nothing is written.  The calls allocate nothing, wait for nothing and copy nothing from the device.  Elements between w and a
+ * pitch are never touched. */
+int shg_column_limb_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, int window, int threshold, int32_t* out6,
+                        shg_stream_t stream);
+int shg_column_shift_u16(const uint16_t* img, int n, int64_t h, int64_t w, int64_t pitch, int64_t plane_stride,
+                         const int32_t* host_offset, const int32_t* host_weight4, uint16_t* out, int64_t out_pitch,
+                         int64_t out_plane_stride, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -127,12 +127,14 @@ def _sigma_of(sigma, image, circle):
     return tuple(min(max(est[k], MIN_SIGMA), MAX_SIGMA) for k in ('sigma_x', 'sigma_y')), measured
 
 
-def deconvolve_scan(file_or_reader, options=None, shift=0, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None, limb=None):
+def deconvolve_scan(file_or_reader, options=None, shift=0, sigma=None, iterations=DEFAULT_ITERATIONS, taps=None, radius=None, limb=None,
+                    dejitter=None):
     """A scan's disk at `shift` (disk.scan_disk, with its refusals: ratio_fixe / slant_fix, de-vignette, a frame shard),
     deconvolved by deconvolve_disk -> {'image', 'deconv' (uint16 device tensors), 'circle', 'record', 'shift', 'ratio', 'phi',
     'crop'}.  limb: deconvolve_disk's dict without 'circle': the scan's own limb fit is the circle.  sigma 'auto': the widths
-    psf.estimate_psf measures on the scan's own limb, and the record gains 'psf', what it measured."""
-    scan = disk.scan_disk(file_or_reader, options, shift, 'deconvolution')
+    psf.estimate_psf measures on the scan's own limb, and the record gains 'psf', what it measured.  dejitter: disk.scan_disk's; the
+    result then holds 'jitter'."""
+    scan = disk.scan_disk(file_or_reader, options, shift, 'deconvolution', dejitter)
     sigma, measured = _sigma_of(sigma, scan['image'], scan['circle'])
     if limb is not None:
         if not isinstance(limb, dict) or limb.get('circle') is not None:
@@ -141,8 +143,11 @@ def deconvolve_scan(file_or_reader, options=None, shift=0, sigma=None, iteration
     deconv, record = deconvolve_disk(scan['image'], sigma, iterations, taps, radius, limb)
     if measured is not None:
         record['psf'] = measured
-    return {'image': scan['image'], 'deconv': deconv, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
-            'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
+    res = {'image': scan['image'], 'deconv': deconv, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
+           'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
+    if 'jitter' in scan:
+        res['jitter'] = scan['jitter']
+    return res
 
 
 # ---- command line ---------------------------------------------------------------------------------
@@ -172,7 +177,7 @@ def main(argv=None):
     p = argparse.ArgumentParser(
         prog='python -m solex_ser_recon_en_amd.deconvolve',
         usage='%(prog)s INPUT [--psf-sigma X | SX,SY | auto] [--iterations N] [--radius R] [--shift S] [--contrast] [--circle cx,cy,rad] '
-              '[--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only] [SHG_MAIN flags]',
+              '[--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only] [--dejitter] [SHG_MAIN flags]',
         description='Deconvolve a disk: Richardson-Lucy iterations with a Gaussian point-spread function.  INPUT is a SER or AVI scan, or '
                     'a 16-bit grey PNG this package wrote (_stack.png, _flat.png, _uncontrasted.png).  The iterations amplify noise: '
                     'give a stack many, a single scan few.  The limb rings unless --limb-protect is given.')
@@ -185,6 +190,7 @@ def main(argv=None):
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the deconvolved image (<base>_deconv_clahe.png, ...)')
     p.add_argument('--circle', type=_floats, default=None, help='cx,cy,rad of the disk in a PNG: what --limb-protect and --contrast go by')
     limbguard.add_arguments(p, 'the radius of the taps')
+    disk.add_dejitter_argument(p)
     limb = []
 
     def checks(args):
@@ -200,6 +206,7 @@ def main(argv=None):
         limb.append(limbguard.from_arguments(p, args, args.circle, float(reach)))
 
     def file_checks(args, files):
+        disk.check_dejitter(p, args, files)
         if limb[0] is not None and args.circle is None and any(f.lower().endswith('.png') for f in files):
             p.error('--limb-protect on a PNG needs --circle cx,cy,rad')
         if args.psf_sigma == 'auto' and args.circle is None and any(f.lower().endswith('.png') for f in files):
@@ -221,7 +228,8 @@ def main(argv=None):
             if args.circle is not None:
                 raise ValueError('--circle goes with a PNG: a scan brings its own limb fit')
             header_source = video_reader(path)
-            res = deconvolve_scan(header_source, opts, args.shift, args.psf_sigma, args.iterations, radius=args.radius, limb=limb)
+            res = deconvolve_scan(header_source, opts, args.shift, args.psf_sigma, args.iterations, radius=args.radius, limb=limb,
+                                  dejitter={} if args.dejitter else None)
             measured = res['record'].pop('psf', None)
             deconv, record = res['deconv'], res['record']
             stem = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift'])
@@ -237,6 +245,8 @@ def main(argv=None):
         out['limb'] = record['limb']
     if measured is not None:
         out['psf'] = measured
+    if args.dejitter:
+        out['jitter'] = disk.jitter_summary(res['jitter'])
     if args.contrast:
         out['contrast'] = disk.contrast_products(deconv, tuple(res['circle']), opts, header_source, stem + '_deconv')
     return _print_json(out, res)

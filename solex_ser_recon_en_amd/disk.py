@@ -17,12 +17,15 @@ def host_u(t, dtype):
     return t.view(signed).cpu().numpy().view(dtype)
 
 
-def scan_disk(file_or_reader, options=None, shift=0, purpose='flattening'):
+def scan_disk(file_or_reader, options=None, shift=0, purpose='flattening', dejitter=None):
     """A scan's disk at `shift`: the image _uncontrasted.png shows for that shift before img_rotate -- through the package's own
     stages as Solex_recon.solex_process composes them: line fit, the disks of the ellipse-fit shift and of `shift`, the limb fit,
     the ellipse -> circle warp, transversalium, crop -- and its circle.  -> {'image' (a uint16 device tensor), 'circle' (of the
     image), 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe / slant_fix (no limb fit, hence no circle), de-vignette (a
-    float64 frame) and a frame-sharded reader; `purpose` names the caller in the messages ('stacking', 'sharpening')."""
+    float64 frame) and a frame-sharded reader; `purpose` names the caller in the messages ('stacking', 'sharpening').
+    dejitter: None, or the keyword arguments of dejitter.measure ({}: its defaults) -- the jitter along the slit is measured on the raw
+    disk of the ellipse-fit shift, the one the limb fit reads, every extracted plane is corrected by those shifts before anything
+    else sees it, and the record gains 'jitter', measure's."""
     from . import SHG_MAIN, dist
     from .device import DeviceImage, to_device_u16
     from .ellipse_to_circle import correct_image, ellipse_to_circle
@@ -45,6 +48,11 @@ def scan_disk(file_or_reader, options=None, shift=0, purpose='flattening'):
         _, fit, _, _ = compute_mean_return_fit(rdr, opts, make_header(rdr), iw, ih, '')
         shifts = list(dict.fromkeys([opts['ellipse_fit_shift'], shift]))
         disks, mm = extract_disks(rdr, fit, shifts, flip_x=bool(opts['flip_x']), want_minmax=True)
+        jitter = None
+        if dejitter is not None:
+            from . import dejitter as dj
+            jitter = dj.measure(disks[0], **dict(dejitter))
+            disks, mm = dj.apply(disks, jitter['shift']), None              # (the cubic overshoots: the extrema are no longer known)
         disk_list = [DeviceImage(disks[i], minmax=None if mm is None else mm[i]) for i in range(len(shifts))]
         own = shifts.index(shift)
         frame, circle, ratio, phi, borders = ellipse_to_circle(disk_list[0], opts, '', need_image=own == 0)
@@ -56,8 +64,28 @@ def scan_disk(file_or_reader, options=None, shift=0, purpose='flattening'):
         h, w = to_device_u16(frame).shape
         crop, _ = crop_plan(h, w, circle, opts)
         (frame,), circle_out = crop_to_width([frame], circle, opts)
-    return {'image': to_device_u16(frame), 'circle': tuple(float(v) for v in circle_out), 'shift': shift, 'ratio': float(ratio),
-            'phi': float(phi), 'crop': crop}
+    res = {'image': to_device_u16(frame), 'circle': tuple(float(v) for v in circle_out), 'shift': shift, 'ratio': float(ratio),
+           'phi': float(phi), 'crop': crop}
+    if jitter is not None:
+        res['jitter'] = jitter
+    return res
+
+
+# ---- --dejitter, the flag the scan products share ----------------------------------------------------
+def add_dejitter_argument(p):
+    p.add_argument('--dejitter', action='store_true',
+                   help='take the scan\'s jitter along the slit out of the raw disks first (dejitter.py; a scan, not a PNG)')
+
+
+def check_dejitter(p, args, files):
+    if args.dejitter and any(f.lower().endswith('.png') for f in files):
+        p.error('--dejitter goes with a scan: a PNG has no raw disk to measure')
+
+
+def jitter_summary(jitter):
+    """What a command line prints of dejitter.measure's record."""
+    return {'threshold': jitter['threshold'], 'window': jitter['window'], 'n_measured': jitter['n_measured'], 'rms': jitter['rms'],
+            'max': jitter['max'], 'line': [jitter['slope'], jitter['intercept']]}
 
 
 # ---- the frame of the four command lines ------------------------------------------------------------

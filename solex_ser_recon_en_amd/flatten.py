@@ -83,16 +83,20 @@ def flatten_disk(image, circle, smooth=1, level=None, max_gain=8.0):
     return ops.ring_flatten_u16(t, circle, gain), profile, gain
 
 
-def flatten_scan(file_or_reader, options=None, shift=0, smooth=1, level=None, max_gain=8.0):
+def flatten_scan(file_or_reader, options=None, shift=0, smooth=1, level=None, max_gain=8.0, dejitter=None):
     """A scan's disk at `shift` (disk.scan_disk), flattened by flatten_disk.  -> {'image', 'flat' (uint16 device tensors),
     'circle' (of the image), 'profile', 'gain', 'level', 'shift', 'ratio', 'phi', 'crop'}.  ValueError for ratio_fixe / slant_fix (no
-    limb fit, hence no circle), de-vignette (a float64 frame) and a frame-sharded reader."""
-    scan = disk.scan_disk(file_or_reader, options, shift)
+    limb fit, hence no circle), de-vignette (a float64 frame) and a frame-sharded reader.  dejitter: disk.scan_disk's; the record then
+    holds 'jitter'."""
+    scan = disk.scan_disk(file_or_reader, options, shift, dejitter=dejitter)
     image, circle_out = scan['image'], scan['circle']
     flat, profile, gain = flatten_disk(image, circle_out, smooth, level, max_gain)
     used = float(level) if level is not None else float(default_level(filled_profile(profile, smooth)))
-    return {'image': image, 'flat': flat, 'circle': circle_out, 'profile': profile, 'gain': gain, 'level': used, 'shift': scan['shift'],
-            'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop'], 'smooth': int(smooth), 'max_gain': float(max_gain)}
+    res = {'image': image, 'flat': flat, 'circle': circle_out, 'profile': profile, 'gain': gain, 'level': used, 'shift': scan['shift'],
+           'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop'], 'smooth': int(smooth), 'max_gain': float(max_gain)}
+    if 'jitter' in scan:
+        res['jitter'] = scan['jitter']
+    return res
 
 
 # ---- command line ---------------------------------------------------------------------------------
@@ -101,13 +105,14 @@ def main(argv=None):
     from .solex_util import output_path
     from .video_reader import video_reader
     p = argparse.ArgumentParser(prog='python -m solex_ser_recon_en_amd.flatten',
-                                usage='%(prog)s FILE [--shift S] [--smooth N] [--max-gain G] [--contrast] [SHG_MAIN flags]',
+                                usage='%(prog)s FILE [--shift S] [--smooth N] [--max-gain G] [--contrast] [--dejitter] [SHG_MAIN flags]',
                                 description='Flatten a scan\'s disk: divide it by the median of every one-pixel ring around the fitted '
                                             'centre, and write that centre-to-limb profile.')
     p.add_argument('--shift', type=int, default=0, help='pixel shift of the disk to flatten (the -w shift; default 0: the line centre)')
     p.add_argument('--smooth', type=int, default=1, help='running mean over N rings (odd; default 1: none)')
     p.add_argument('--max-gain', type=float, default=8.0, help='the largest gain a ring may get (default 8)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the flat image (<base>_flat_clahe.png, ...)')
+    disk.add_dejitter_argument(p)
 
     def checks(args):
         if args.smooth < 1 or args.smooth % 2 == 0:
@@ -118,7 +123,7 @@ def main(argv=None):
     args, opts, (path,) = disk.parse(p, argv, 'flatten', 'flattening', checks)
     try:
         rdr = video_reader(path)
-        res = flatten_scan(rdr, opts, args.shift, args.smooth, None, args.max_gain)
+        res = flatten_scan(rdr, opts, args.shift, args.smooth, None, args.max_gain, {} if args.dejitter else None)
     except ValueError as e:
         print('error: %s' % e, file=sys.stderr)
         return 1
@@ -140,6 +145,8 @@ def main(argv=None):
                centre_median=float(profile['median'][have[0]]) if have.size else None,
                limb_median=float(profile['median'][have[-1]]) if have.size else None,
                saturated=int(((flat == 65535) & (image != 65535)).sum()))
+    if args.dejitter:
+        out['jitter'] = disk.jitter_summary(res['jitter'])
     if args.contrast:
         out['contrast'] = disk.contrast_products(res['flat'], res['circle'], opts, rdr, stem + '_flat')
     return _print_json(out, res)

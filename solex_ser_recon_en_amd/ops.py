@@ -1394,3 +1394,67 @@ def limb_merge_u16(img, disk, sky, circle, margin, blend, out=None):
     _lib.check(lib.shg_limb_merge_u16(ptr, pitch, dptr, dpitch, sptr, spitch, h, w, _host_ptr(c3), margin, float(blend), optr, opitch,
                                       _stream()), 'shg_limb_merge_u16')
     return out
+
+
+# ---- scan jitter along the slit: the limb crossings of every column, and every column resampled along itself ----
+COLUMN_LIMB_SEGMENTS = 128        # the row segments a workgroup of shg_column_limb_u16 splits its columns into (csrc/dejitter.hip)
+COLUMN_LIMB_COLUMNS = 64          # the columns a workgroup owns
+COLUMN_SHIFT_COLUMNS = 256        # the columns a launch of shg_column_shift_u16 carries in its arguments
+COLUMN_SHIFT_ROWS = 128           # the rows a workgroup of it handles
+
+
+def column_limb_segment(h, window):
+    """The rows a segment of shg_column_limb_u16 owns for an image of h rows: segment g owns the window sums s[g L .. (g + 1) L - 1],
+    L = ceil((h - window + 1) / COLUMN_LIMB_SEGMENTS) -> L (0 when h < window)."""
+    ni = int(h) - int(window) + 1
+    return max(0, (ni + COLUMN_LIMB_SEGMENTS - 1) // COLUMN_LIMB_SEGMENTS)
+
+
+def column_limb_u16(img, window, threshold, out=None):
+    """shg_column_limb_u16: the two limb crossings of every column of the uint16 image, with s[i] the sum of the `window` (odd, 1 to
+    15) rows from i on and A[i] = s[i] >= window * threshold (0 to 65535) -> int32 [w, 6] on the image's device: (i_top, s[i_top - 1],
+    s[i_top], i_bot, s[i_bot], s[i_bot + 1]), -1 in all six for a column without a measurement.  out: the caller's, overwritten."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    if not (isinstance(window, (int, np.integer)) and 1 <= window <= 15 and window % 2 == 1):
+        raise ValueError('window is an odd integer from 1 to 15, got %r' % (window,))
+    if not (isinstance(threshold, (int, np.integer)) and 0 <= threshold <= 65535):
+        raise ValueError('threshold is an integer from 0 to 65535, got %r' % (threshold,))
+    if out is None:
+        out = torch.empty((w, 6), dtype=torch.int32, device=img.device)
+    if _dev(out, 'out').dtype != torch.int32 or tuple(out.shape) != (w, 6) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 [%d, 6] tensor' % w)
+    _lib.check(lib.shg_column_limb_u16(ptr, h, w, pitch, int(window), int(threshold), out.data_ptr(), _stream()), 'shg_column_limb_u16')
+    return out
+
+
+def column_shift_u16(planes, offset, weight, out=None):
+    """shg_column_shift_u16: every column of the uint16 planes -- [h, w], or [n, h, w] with n from 1 to 64, unit column stride --
+    resampled along itself: out[p, r, c] = clip((sum_k weight[c, k] * planes[p, clamp(r + offset[c] + k - 1, 0, h - 1), c] + 8192) >> 14,
+    0, 65535).  offset: int32 [w], |offset| <= 16384; weight: int32 [w, 4] in Q14, each in [-4096, 20480], a column's summing to 16384
+    (host arrays: they travel in the launches' arguments) -> uint16 of the planes' shape.  out: the caller's view, which must not
+    overlap the planes."""
+    _dev(planes, 'planes')
+    if planes.dtype != torch.uint16:
+        raise TypeError('planes must be torch.uint16, got %s' % planes.dtype)
+    single = planes.dim() == 2
+    stack = planes[None] if single else planes
+    if stack.dim() != 3 or (stack.shape[2] > 1 and stack.stride(2) != 1):
+        raise ValueError('planes must be an [h, w] or [n, h, w] view with contiguous rows')
+    n, h, w = (int(v) for v in stack.shape)
+    if not 1 <= n <= 64:
+        raise ValueError('1 to 64 planes, got %d' % n)
+    o = np.ascontiguousarray(offset, dtype=np.int64).reshape(-1)
+    q = np.ascontiguousarray(weight, dtype=np.int64)
+    if o.shape != (w,) or q.shape != (w, 4):
+        raise ValueError('offset [%d] and weight [%d, 4], got %s and %s' % (w, w, o.shape, q.shape))
+    if w and (np.abs(o).max() > 16384 or q.min() < -4096 or q.max() > 20480 or (q.sum(axis=1) != 16384).any()):
+        raise ValueError('|offset| <= 16384, every weight in [-4096, 20480] and a column\'s weights summing to 16384')
+    o, q = o.astype(np.int32), np.ascontiguousarray(q.astype(np.int32))
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.uint16, device=planes.device)
+    dst = out[None] if out.dim() == 2 else out
+    if _dev(out, 'out').dtype != torch.uint16 or tuple(dst.shape) != (n, h, w) or (w > 1 and dst.stride(2) != 1):
+        raise ValueError('out must be a uint16 view of the planes\' shape with contiguous rows')
+    _lib.check(lib.shg_column_shift_u16(stack.data_ptr(), n, h, w, stack.stride(1), stack.stride(0), _host_ptr(o), _host_ptr(q), dst.data_ptr(),
+                                        dst.stride(1), dst.stride(0), _stream()), 'shg_column_shift_u16')
+    return out[0] if single and out.dim() == 3 else out

@@ -150,17 +150,20 @@ def wavelet_planes(image, levels):
 
 
 def sharpen_scan(file_or_reader, options=None, shift=0, gains=DEFAULT_GAINS, denoise=DEFAULT_DENOISE, sigma=None, region=DEFAULT_REGION,
-                 limb=None):
+                 limb=None, dejitter=None):
     """A scan's disk at `shift` (disk.scan_disk, with its refusals: ratio_fixe / slant_fix, de-vignette, a frame
     shard), sharpened by sharpen_disk with the noise measured inside region * rad of the fitted circle -> {'image', 'sharp' (uint16
     device tensors), 'circle', 'record', 'shift', 'ratio', 'phi', 'crop'}.  limb: sharpen_disk's dict without 'circle': the scan's own
-    limb fit is the circle."""
-    scan = disk.scan_disk(file_or_reader, options, shift, 'sharpening')
+    limb fit is the circle.  dejitter: disk.scan_disk's; the result then holds 'jitter'."""
+    scan = disk.scan_disk(file_or_reader, options, shift, 'sharpening', dejitter)
     if limb is not None and (not isinstance(limb, dict) or limb.get('circle') is not None):
         raise ValueError('a scan brings its own limb fit: limb is a dict without a circle')
     sharp, record = sharpen_disk(scan['image'], gains, denoise, sigma, scan['circle'], region, limb)
-    return {'image': scan['image'], 'sharp': sharp, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
-            'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
+    res = {'image': scan['image'], 'sharp': sharp, 'circle': scan['circle'], 'record': record, 'shift': scan['shift'],
+           'ratio': scan['ratio'], 'phi': scan['phi'], 'crop': scan['crop']}
+    if 'jitter' in scan:
+        res['jitter'] = scan['jitter']
+    return res
 
 
 # ---- command line ---------------------------------------------------------------------------------
@@ -177,7 +180,7 @@ def main(argv=None):
     p = argparse.ArgumentParser(
         prog='python -m solex_ser_recon_en_amd.sharpen',
         usage='%(prog)s INPUT [--levels L] [--gains g1,..] [--denoise k1,..] [--sigma X] [--circle cx,cy,rad] [--region F] [--shift S] '
-              '[--contrast] [--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only] [SHG_MAIN flags]',
+              '[--contrast] [--limb-protect [MARGIN]] [--limb-blend B] [--limb-reach Q] [--limb-disk-only] [--dejitter] [SHG_MAIN flags]',
         description='Sharpen a disk with B3-spline a-trous wavelet layers: one gain a layer and a soft noise gate on the finest layers.  '
                     'INPUT is a SER or AVI scan, or a 16-bit grey PNG this package wrote (_stack.png, _flat.png, _uncontrasted.png).  '
                     'For a PNG without --circle the noise is measured over the whole image: a black sky biases the estimate low '
@@ -194,9 +197,11 @@ def main(argv=None):
     p.add_argument('--shift', type=int, default=0, help='pixel shift of a scan\'s disk (the -w shift; default 0: the line centre)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the sharpened image (<base>_sharp_clahe.png, ...)')
     limbguard.add_arguments(p, '%g' % DEFAULT_LIMB_MARGIN)
+    disk.add_dejitter_argument(p)
     limb = []
 
     def file_checks(args, files):
+        disk.check_dejitter(p, args, files)
         if limb[0] is not None and args.circle is None and any(f.lower().endswith('.png') for f in files):
             p.error('--limb-protect on a PNG needs --circle cx,cy,rad')
 
@@ -238,7 +243,8 @@ def main(argv=None):
             header_source = video_reader(path)
             if limb is not None:
                 limb.pop('circle', None)
-            res = sharpen_scan(header_source, opts, args.shift, args.gains, args.denoise, args.sigma, args.region, limb)
+            res = sharpen_scan(header_source, opts, args.shift, args.gains, args.denoise, args.sigma, args.region, limb,
+                               {} if args.dejitter else None)
             sharp, record = res['sharp'], res['record']
             stem = '%s_shift=%d' % (os.path.splitext(path)[0], res['shift'])
     except ValueError as e:
@@ -251,6 +257,8 @@ def main(argv=None):
            'fits': fits, 'contrast': None}
     if limb is not None:
         out['limb'] = record['limb']
+    if args.dejitter:
+        out['jitter'] = disk.jitter_summary(res['jitter'])
     if args.contrast:
         out['contrast'] = disk.contrast_products(sharp, tuple(res['circle']), opts, header_source, stem + '_sharp')
     return _print_json(out, res)

@@ -509,7 +509,7 @@ def check_combine(mode, kappa, iterations):
 
 
 def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2.5, iterations=2, search=8, region=0.9, local=None,
-                quality=None):
+                quality=None, dejitter=None):
     """The scans' disks at `shift` registered to the one of files[reference] and stacked -> {'stack' uint16, 'count' uint8 (device
     tensors on the reference's grid), 'circle' (the reference's), 'records' (register_disks', one a file), 'used', 'rejected' (indices
     into files), 'images', 'circles', 'shift', 'mode', 'ratio', 'phi', 'crop' (the reference's), 'local'}.  local: None, or a dict of
@@ -525,7 +525,8 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
     the weighted one.  With `local` the quality lattice's step is local['step'] (the combine has one lattice): giving quality['step']
     as well is a ValueError, as are weights with mode 'median'.  'quality' is None, or the parameters and 'figures' (a float a
     file), 'maps' (disk_quality's, a file), 'selected' (a bool a file), 'local_maps', 'weights' (host lattices a file, None for a
-    file that is not stacked; both None without lucky / power) and 'shares' (node_shares of the kept scans' maps a file, or None)."""
+    file that is not stacked; both None without lucky / power) and 'shares' (node_shares of the kept scans' maps a file, or None).
+    dejitter: disk.scan_disk's, for every scan; the result then holds 'jitter', dejitter.measure's record a file."""
     files = list(files)
     if len(files) < 2:
         raise ValueError('stacking needs at least two scans, got %d' % len(files))
@@ -554,7 +555,7 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
             raise ValueError('local knows %s, got %s' % (', '.join(LOCAL_DEFAULTS), ', '.join(unknown)))
         local = dict(LOCAL_DEFAULTS, **local)
         check_local(local['step'], local['size'], local['search'], local['min_contrast'])
-    disks = [scan_disk(f, options, shift) for f in files]
+    disks = [disk.scan_disk(f, options, shift, 'stacking', dejitter) for f in files]
     images, circles = [d['image'] for d in disks], [d['circle'] for d in disks]
     measured = None
     if quality is not None:
@@ -595,11 +596,14 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
             quality.update(local_maps=per_file(maps), weights=per_file(weights), shares=per_file(node_shares(maps)))
     stack, count = stack_disks([images[i] for i in used], [records[i] for i in used], mode, kappa, iterations, tuple(ref['image'].shape),
                                fields, step, weights)
-    return {'quality': quality, 'unselected': unselected, 'local': local, 'stack': stack, 'count': count, 'circle': ref['circle'],
-            'records': records, 'used': used,
-            'rejected': [i for i in range(len(files)) if i not in used], 'images': images, 'circles': circles, 'shift': ref['shift'],
-            'mode': mode, 'kappa': float(kappa), 'iterations': int(iterations), 'reference': int(reference), 'ratio': ref['ratio'],
-            'phi': ref['phi'], 'crop': ref['crop']}
+    res = {'quality': quality, 'unselected': unselected, 'local': local, 'stack': stack, 'count': count, 'circle': ref['circle'],
+           'records': records, 'used': used,
+           'rejected': [i for i in range(len(files)) if i not in used], 'images': images, 'circles': circles, 'shift': ref['shift'],
+           'mode': mode, 'kappa': float(kappa), 'iterations': int(iterations), 'reference': int(reference), 'ratio': ref['ratio'],
+           'phi': ref['phi'], 'crop': ref['crop']}
+    if dejitter is not None:
+        res['jitter'] = [d['jitter'] for d in disks]
+    return res
 
 
 # ---- command line ---------------------------------------------------------------------------------
@@ -612,7 +616,7 @@ def main(argv=None):
                                 usage='%(prog)s FILE FILE ... [--shift S] [--reference K|best] [--mode mean|median|sigma] [--kappa X] '
                                       '[--iterations I] [--search S] [--local [--ap-size P] [--ap-step D] [--ap-search S] '
                                       '[--ap-min-contrast X]] [--quality] [--best K] [--min-quality X] [--lucky K] [--quality-power P] '
-                                      '[--quality-arm D] [--quality-size N] [--quality-step N] [--coverage] [--contrast] [SHG_MAIN flags]',
+                                      '[--quality-arm D] [--quality-size N] [--quality-step N] [--coverage] [--contrast] [--dejitter] [SHG_MAIN flags]',
                                 description='Stack a series of scans of one line: register every scan\'s disk to the reference scan\'s '
                                             'and combine them into one image.')
     p.add_argument('--shift', type=int, default=0, help='pixel shift of the disks to stack (the -w shift; default 0: the line centre)')
@@ -645,6 +649,7 @@ def main(argv=None):
                                                                   'with --local the alignment points\' step is used)')
     p.add_argument('--coverage', action='store_true', help='also the number of frames behind every pixel (<base>_stack_count.png)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the stack (<base>_stack_clahe.png, ...)')
+    disk.add_dejitter_argument(p)
 
     def checks(args):
         if not args.kappa >= 1:
@@ -703,7 +708,7 @@ def main(argv=None):
         quality = None
     try:
         res = stack_scans(files, opts, args.shift, args.reference, args.mode, args.kappa, args.iterations, args.search, local=local,
-                          quality=quality)
+                          quality=quality, dejitter={} if args.dejitter else None)
     except ValueError as e:
         print('error: %s' % e, file=sys.stderr)
         return 1
@@ -727,6 +732,8 @@ def main(argv=None):
         out['quality'] = {'step': q['step'], 'size': q['size'], 'arm': q['arm'], 'region': q['region'], 'best': q['best'],
                           'min_quality': q['min_quality'], 'lucky': q['lucky'], 'power': q['power'], 'reference': res['reference'],
                           'unselected': [files[i] for i in res['unselected']], 'shares': q['shares']}
+    if args.dejitter:
+        out['jitter'] = [disk.jitter_summary(j) for j in res['jitter']]
     if args.coverage:
         out['count_png'] = output_path(stem + '_count.png', opts)
         write_png(out['count_png'], np.ascontiguousarray(np.rot90(res['count'].contiguous().cpu().numpy(), opts['img_rotate'] // 90)), 0)
