@@ -665,6 +665,46 @@ int shg_column_shift_u16(const uint16_t* img, int n, int64_t h, int64_t w, int64
                          const int32_t* host_offset, const int32_t* host_weight4, uint16_t* out, int64_t out_pitch,
                          int64_t out_plane_stride, shg_stream_t stream);
 
+/* ---- differential rotation: a finished disk carried to another time, every on-disk pixel turned back about the solar pole by the
+ * angle its latitude rotates in the time difference (not a reference stage; tests/derotate_ref.py restates the call in NumPy, bit for
+ * bit).  circle3 = (cx, cy, rad), matrix9 = M (row-major 3 x 3) and rate3 = (k0, k1, k2) are host arrays, read before the call
+ * returns; clv is NULL or device memory of n_rings positive, finite doubles (the host cannot check them: the caller guarantees it).
+ * M is orthonormal: it takes image coordinates (right, up, towards the observer) to (west, the north pole, the central meridian).
+ * k0, k1, k2 are radians: the rotation law A + B sin^2(latitude) + C sin^4(latitude) times the time difference, target minus image.
+ * Everything is float64, one IEEE operation a step, no contraction; sqrt and / are correctly rounded; the device calls no
+ * trigonometric function.  For the output pixel in row r, column c, with v0 = img[r * pitch + c]:
+ *   1  u = ((double)c - cx) / rad;  v = (cy - (double)r) / rad;  d2 = u * u + v * v.  If not d2 < 1: out = v0 (the sky, a prominence).
+ *      Else z = sqrt(1 - d2).
+ *   2  q_i = (M[i][0] * u + M[i][1] * v) + M[i][2] * z for i = x, y, z.
+ *   3  s2 = q_y * q_y;  a = (k2 * s2 + k1) * s2 + k0.  If a == 0: out = v0 (a time difference of 0 is the identity).
+ *   4  a2 = a * a;  sa = a * P(a2);  ca = Q(a2), Horner forms from the highest term down with the float64 nearest to +-1 / k!:
+ *        P = ((((((S15 a2 + S13) a2 + S11) a2 + S9) a2 + S7) a2 + S5) a2 + S3) a2 + 1,
+ *          S3 = -0.16666666666666666, S5 = 0.008333333333333333, S7 = -0.0001984126984126984, S9 = 2.7557319223985893e-06,
+ *          S11 = -2.505210838544172e-08, S13 = 1.6059043836821613e-10, S15 = -7.647163731819816e-13;
+ *        Q = (((((((C16 a2 + C14) a2 + C12) a2 + C10) a2 + C8) a2 + C6) a2 + C4) a2 + C2) a2 + 1,
+ *          C2 = -0.5, C4 = 0.041666666666666664, C6 = -0.001388888888888889, C8 = 2.48015873015873e-05,
+ *          C10 = -2.755731922398589e-07, C12 = 2.08767569878681e-09, C14 = -1.1470745597729725e-11, C16 = 4.779477332387385e-14.
+ *      The truncation is below 2^-53 for |a| <= 0.5.
+ *   5  the source point: x' = q_x * ca - q_z * sa;  z' = q_x * sa + q_z * ca;  y' = q_y;  p = M^T q':
+ *      p_u = (M[0][0] * x' + M[1][0] * y') + M[2][0] * z', p_v and p_z with the columns 1 and 2.  If not p_z > 0 (the source lies
+ *      behind the limb): out = v0.
+ *   6  x = cx + p_u * rad;  y = cy - p_v * rad;  x0 = floor(x), tx = x - x0, y0 = floor(y), ty = y - y0.  The Keys cubic weights
+ *      (a = -0.5) of t, in float64: ((-0.5 t + 1) t - 0.5) t, (1.5 t - 2.5) (t t) + 1, ((-1.5 t + 2) t + 0.5) t, (0.5 t - 0.5) (t t),
+ *      each rint(. * 16384), what is missing to 16384 added to the second: wx[0..3] of tx, wy[0..3] of ty.  As int64:
+ *      H_j = sum over k of wx[k] * img[clamp(y0 + j - 1, 0, h - 1)][clamp(x0 + k - 1, 0, w - 1)];  T = sum over j of wy[j] * H_j;
+ *      val = (T + 2^27) >> 28 (the shift is arithmetic).
+ *   7  clv NULL: out = clip(val, 0, 65535).  Else, with g(rho) the rule of shg_ring_flatten_u16 on the table (u = rho - 0.5, its two
+ *      end clamps, the truncation, the linear step): rho_out = sqrt(d2) * rad, rho_src = sqrt(p_u * p_u + p_v * p_v) * rad,
+ *      out = (uint16)clip(rint((double)val * (g(rho_out) / g(rho_src))), 0, 65535): limb darkening belongs to the view, not to the
+ *      surface, so a pixel that moves is rescaled by the profile of its new radius over that of its old one.
+ * 1 <= h, w <= 16384, else SHG_E_UNSUPPORTED.  SHG_E_ARG for a null pointer other than clv, a pitch below w, a circle outside the
+ * limits of shg_ring_medians_u16, n_rings != floor(rad) + 1 (with clv NULL as well), a matrix that is not finite or whose rows'
+ * products differ from the identity by more than 1e-12, a rate3 that is not finite or has |k0| + |k1| + |k2| > 0.5 (about 1.9 days at
+ * the default law: the polynomials' range), and an out that overlaps img.  On any error nothing is written.  The call allocates
+ * nothing, waits for nothing and copies nothing from the device.  Elements between w and a pitch are never touched. */
+int shg_derotate_u16(const uint16_t* img, int64_t h, int64_t w, int64_t pitch, const double* circle3, const double* matrix9,
+                     const double* rate3, const double* clv, int64_t n_rings, uint16_t* out, int64_t out_pitch, shg_stream_t stream);
+
 /* The two uses of cv2.blur on the path in fused form (the blurred image never leaves the workgroup): row means of
  * blur(img, (kw, kh)) for detect_bord (solex_util.py:166-167), and the first arg-minimum over [x0, x1) of every
  * blurred row together with the first arg-minimum of the unblurred row (solex_util.py:230-231, 242).  Identical

@@ -123,6 +123,7 @@ SIGNATURES = {
     'shg_limb_merge_u16': (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int64, c_int64, P, c_double, c_double, P, c_int64, P]),
     'shg_column_limb_u16': (c_int, [P, c_int64, c_int64, c_int64, c_int, c_int, P, P]),
     'shg_column_shift_u16': (c_int, [P, c_int, c_int64, c_int64, c_int64, c_int64, P, P, P, c_int64, c_int64, P]),
+    'shg_derotate_u16': (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P, c_int64, P, c_int64, P]),
     'shg_blur_fits_fused': (c_int, [c_int64, c_int]),
     'shg_blur_row_mean_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, P, P]),
     'shg_blur_argmin_u16': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int64, c_int64, P, P, P]),

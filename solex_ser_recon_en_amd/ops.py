@@ -1458,3 +1458,30 @@ def column_shift_u16(planes, offset, weight, out=None):
     _lib.check(lib.shg_column_shift_u16(stack.data_ptr(), n, h, w, stack.stride(1), stack.stride(0), _host_ptr(o), _host_ptr(q), dst.data_ptr(),
                                         dst.stride(1), dst.stride(0), _stream()), 'shg_column_shift_u16')
     return out[0] if single and out.dim() == 3 else out
+
+
+# ---- differential rotation: a finished disk carried to another time ------------------------------------
+DEROTATE_MAX_RATE = 0.5           # |k0| + |k1| + |k2| in radians: the range of shg_derotate_u16's sine and cosine polynomials
+
+
+def derotate_u16(img, circle, matrix, rate3, clv=None, out=None):
+    """shg_derotate_u16: every on-disk pixel of the uint16 image taken from where it was the time difference ago -- carried to the
+    sphere by circle (cx, cy, r) and the orthonormal matrix [3, 3] (image right / up / observer -> west / pole / central meridian),
+    turned back about the pole by a = (k2 s2 + k1) s2 + k0 with s2 = sin^2(latitude) and rate3 = (k0, k1, k2) in radians, sampled
+    with a Keys cubic in Q14 both ways -- and, with clv (a float64 [K] device tensor of positive, finite values, K = floor(r) + 1,
+    clv[k] at radius k + 1/2 as ring_flatten_u16's gain), times clv(new radius) / clv(old radius).  Pixels off the disk, with a = 0
+    or with a source behind the limb stay as they are -> uint16 [h, w].  out: the caller's view, which must not overlap the image."""
+    ptr, h, w, pitch = _img(img, 'img', torch.uint16)
+    c3, k = _circle3(circle)
+    m9 = np.ascontiguousarray(matrix, dtype=np.float64).reshape(-1)
+    k3 = np.ascontiguousarray([float(v) for v in rate3], dtype=np.float64)
+    if m9.size != 9 or k3.size != 3:
+        raise ValueError('matrix is [3, 3] and rate3 is (k0, k1, k2)')
+    if not (np.isfinite(k3).all() and np.abs(k3).sum() <= DEROTATE_MAX_RATE):
+        raise ValueError('rate3 %r must be finite with |k0| + |k1| + |k2| <= %g radians' % (tuple(k3), DEROTATE_MAX_RATE))
+    if clv is not None and (_dev(clv, 'clv').dtype != torch.float64 or tuple(clv.shape) != (k,) or not clv.is_contiguous()):
+        raise ValueError('clv must be a contiguous float64 [%d] device tensor (floor(r) + 1 rings)' % k)
+    out, optr, opitch = _out_like(out, h, w, torch.uint16, img.device)
+    _lib.check(lib.shg_derotate_u16(ptr, h, w, pitch, _host_ptr(c3), _host_ptr(m9), _host_ptr(k3), None if clv is None else clv.data_ptr(), k,
+                                    optr, opitch, _stream()), 'shg_derotate_u16')
+    return out

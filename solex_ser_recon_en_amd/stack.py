@@ -509,7 +509,7 @@ def check_combine(mode, kappa, iterations):
 
 
 def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2.5, iterations=2, search=8, region=0.9, local=None,
-                quality=None, dejitter=None):
+                quality=None, dejitter=None, derotate=None):
     """The scans' disks at `shift` registered to the one of files[reference] and stacked -> {'stack' uint16, 'count' uint8 (device
     tensors on the reference's grid), 'circle' (the reference's), 'records' (register_disks', one a file), 'used', 'rejected' (indices
     into files), 'images', 'circles', 'shift', 'mode', 'ratio', 'phi', 'crop' (the reference's), 'local'}.  local: None, or a dict of
@@ -526,7 +526,12 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
     as well is a ValueError, as are weights with mode 'median'.  'quality' is None, or the parameters and 'figures' (a float a
     file), 'maps' (disk_quality's, a file), 'selected' (a bool a file), 'local_maps', 'weights' (host lattices a file, None for a
     file that is not stacked; both None without lucky / power) and 'shares' (node_shares of the kept scans' maps a file, or None).
-    dejitter: disk.scan_disk's, for every scan; the result then holds 'jitter', dejitter.measure's record a file."""
+    dejitter: disk.scan_disk's, for every scan; the result then holds 'jitter', dejitter.measure's record a file.
+    derotate: None, or a dict of derotate.series_plan's arguments ('north', 'b0', and 'mirror', 'times', 'interval', 'law', 'clv'):
+    once the reference is chosen, every other scan's disk is derotated to the reference's time on its own grid with its own circle
+     and the registration and everything after it see the derotated images; the reference is not resampled.
+    The result then holds 'derotate', derotate_disk's record a file (derotate.derotate_series: the reference's with rates of zero and
+    nothing moved, 'behind_limb' None for the others), and 'images' are the derotated ones."""
     files = list(files)
     if len(files) < 2:
         raise ValueError('stacking needs at least two scans, got %d' % len(files))
@@ -555,6 +560,12 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
             raise ValueError('local knows %s, got %s' % (', '.join(LOCAL_DEFAULTS), ', '.join(unknown)))
         local = dict(LOCAL_DEFAULTS, **local)
         check_local(local['step'], local['size'], local['search'], local['min_contrast'])
+    if derotate is not None:
+        from . import derotate as dr
+        unknown = sorted(set(derotate) - set(dr.SERIES_KEYS))
+        if unknown:
+            raise ValueError('derotate knows %s, got %s' % (', '.join(dr.SERIES_KEYS), ', '.join(unknown)))
+        derotate = dr.series_plan(files, options, **derotate)
     disks = [disk.scan_disk(f, options, shift, 'stacking', dejitter) for f in files]
     images, circles = [d['image'] for d in disks], [d['circle'] for d in disks]
     measured = None
@@ -563,6 +574,8 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
                     for i in range(len(files))]
         if reference == 'best':
             reference = max(range(len(files)), key=lambda i: (measured[i]['quality'], -i))
+    if derotate is not None:
+        images, derotated = dr.derotate_series(images, circles, derotate, int(reference))
     records = register_disks(images, circles, reference, search, region)
     used = [i for i, rec in enumerate(records) if not rec['rejected']]
     if len(used) < 2:
@@ -603,6 +616,8 @@ def stack_scans(files, options=None, shift=0, reference=0, mode='sigma', kappa=2
            'phi': ref['phi'], 'crop': ref['crop']}
     if dejitter is not None:
         res['jitter'] = [d['jitter'] for d in disks]
+    if derotate is not None:
+        res['derotate'] = derotated
     return res
 
 
@@ -616,7 +631,9 @@ def main(argv=None):
                                 usage='%(prog)s FILE FILE ... [--shift S] [--reference K|best] [--mode mean|median|sigma] [--kappa X] '
                                       '[--iterations I] [--search S] [--local [--ap-size P] [--ap-step D] [--ap-search S] '
                                       '[--ap-min-contrast X]] [--quality] [--best K] [--min-quality X] [--lucky K] [--quality-power P] '
-                                      '[--quality-arm D] [--quality-size N] [--quality-step N] [--coverage] [--contrast] [--dejitter] [SHG_MAIN flags]',
+                                      '[--quality-arm D] [--quality-size N] [--quality-step N] [--coverage] [--contrast] [--dejitter] '
+                                      '[--derotate --north P --b0 B [--mirror] [--times T0,T1,.. | --interval SECONDS] [--rotation A,B,C] '
+                                      '[--no-clv]] [SHG_MAIN flags]',
                                 description='Stack a series of scans of one line: register every scan\'s disk to the reference scan\'s '
                                             'and combine them into one image.')
     p.add_argument('--shift', type=int, default=0, help='pixel shift of the disks to stack (the -w shift; default 0: the line centre)')
@@ -650,8 +667,12 @@ def main(argv=None):
     p.add_argument('--coverage', action='store_true', help='also the number of frames behind every pixel (<base>_stack_count.png)')
     p.add_argument('--contrast', action='store_true', help='also the contrast products of the stack (<base>_stack_clahe.png, ...)')
     disk.add_dejitter_argument(p)
+    from . import derotate as dr
+    dr.add_series_arguments(p)
+    series = []
 
     def checks(args):
+        series.append(dr.series_from_arguments(p, args))
         if not args.kappa >= 1:
             p.error('--kappa must be >= 1')
         if not 1 <= args.iterations <= 3:
@@ -694,6 +715,8 @@ def main(argv=None):
             p.error('at most %d scans are stacked at a time (got %d)' % (MAX_SCANS, len(files)))
         if args.reference != 'best' and not 0 <= args.reference < len(files):
             p.error('--reference must be 0 to %d' % (len(files) - 1))
+        if series[0] is not None and series[0]['times'] is not None and len(series[0]['times']) != len(files):
+            p.error('--times names %d times for %d scans' % (len(series[0]['times']), len(files)))
 
     args, opts, files = disk.parse(p, argv, 'stack', 'stacking', checks, file_checks, least=2, most=None,
                                    need='at least two SER or AVI files are needed')
@@ -708,7 +731,7 @@ def main(argv=None):
         quality = None
     try:
         res = stack_scans(files, opts, args.shift, args.reference, args.mode, args.kappa, args.iterations, args.search, local=local,
-                          quality=quality, dejitter={} if args.dejitter else None)
+                          quality=quality, dejitter={} if args.dejitter else None, derotate=series[0])
     except ValueError as e:
         print('error: %s' % e, file=sys.stderr)
         return 1
@@ -734,6 +757,9 @@ def main(argv=None):
                           'unselected': [files[i] for i in res['unselected']], 'shares': q['shares']}
     if args.dejitter:
         out['jitter'] = [disk.jitter_summary(j) for j in res['jitter']]
+    if args.derotate:
+        for frame, record in zip(out['frames'], res['derotate']):
+            frame['derotate'] = {'dt_minutes': record['dt_days'] * 1440.0, 'a_equator': record['a_equator'], 'max_px': record['max_px']}
     if args.coverage:
         out['count_png'] = output_path(stem + '_count.png', opts)
         write_png(out['count_png'], np.ascontiguousarray(np.rot90(res['count'].contiguous().cpu().numpy(), opts['img_rotate'] // 90)), 0)
